@@ -11,9 +11,15 @@ Multi-GPU (weak scaling): utterances are independent; each rank 
 utterance per step with a full replica, and the only exchange is one RCCL all-gather of the
 (2, 8, T) output token tensors per step, inside the timed region.
 
-Extra objects in the JSON line: "roofline" for the dominant kernel (the fused RMSNorm + fc_1/fc_2
-+ SwiGLU weight-streaming GEMM) from HIP-event timing of exactly the launch mix one frame issues;
-"cpu_baseline" = the CPU oracle (fp32 port of the reference algorithm as shipped) on this host.
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+headline line (`value`, `ms_per_step` = wall ms of one timed step).  `--dump-outputs DIR` writes the
+last timed step's id log as DIR/frame_ids.npy (inputs and weights are seeded: identical run to run).
+
+`--full` adds the information legs to the same line: decode-only ms per frame and p50 / p99, the
+skip-text-head rate, the fp32 contract, "roofline" for the dominant kernel (the fused RMSNorm +
+fc_1/fc_2 + SwiGLU weight-streaming GEMM) from HIP-event timing of exactly the launch mix one frame
+issues, "cpu_baseline" = the CPU oracle (fp32 port of the reference algorithm as shipped) on this
+host, and the codec / stage-2 / batched / config-3, 4, 5 legs (`--no-*` and `--config4-leg` refine it).
 """
 import argparse
 import json
@@ -797,16 +803,35 @@ def _respawn_under_torchrun(n):
     sys.exit(subprocess.call(cmd, env=env))
 
 
+def dump_outputs(out_dir, logs):
+    """What the timed path handed its caller in the last step: the (FRAMES, 1, 9) id log of every rank (the all-gather's result
+    under torchrun), as one float32 array (ranks, FRAMES, 1, 9) — column 0 the text id, columns 1-8 the audio ids.  Ids are
+    < 2^24, so float32 holds them exactly."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.stack([l.cpu().numpy() for l in logs]).astype(np.float32)
+    np.save(os.path.join(out_dir, "frame_ids.npy"), ids)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the codec / batched / config-3 / config-5 information legs")
-    ap.add_argument("--config4-leg", action="store_true", help="with --no-legs: still run the config-4 leg (the product's sharded runner + its all-gather)")
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (utterances per rank)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before the timed ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: decode-only rate and p50/p99, skip-text-head rate, fp32 contract, "
+                         "roofline, CPU baseline, config-3/4/5, batched, codec and stage-2 legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the codec / batched / config-3 / config-5 information legs")
+    ap.add_argument("--config4-leg", action="store_true", help="with --full --no-legs: still run the config-4 leg (the product's sharded runner + its all-gather)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.config4_leg and not a.full:
+        ap.error("--config4-leg selects a leg of --full; pass --full too")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if a.gpus > 1 and not launched:
@@ -836,7 +861,8 @@ def main():
         if use_dist:
             out = [torch.empty_like(log) for _ in range(world)]
             dist.all_gather(out, log.contiguous())              # the path's only exchange
-        return log
+            return log, out
+        return log, [log]
 
     def fence():
         if use_dist:
@@ -848,14 +874,37 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        log = step()
+        log, logs = step()
     fence()
     dt = time.perf_counter() - t0
     if use_dist:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, logs)
 
+    audio_tokens = 8 * FRAMES * a.steps * world
+    res = {"metric": "audio tokens/sec (TTS greedy)", "value": round(audio_tokens / dt, 1), "unit": "audio tokens/s",
+           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+           "config": {"workload": "TTS --stage all (BASELINE config 2), single utterance, greedy (topk=1), bf16, B=1 per GPU: "
+                                  f"{PROMPT_LEN}-token prompt + {FRAMES} frames x (8 audio + 1 text) tokens; `value` = the stage-1 "
+                                  "audio-token rate (multi_task_inference.py:486-525), stage 2 (codes -> waveform, :527-548) = "
+                                  "top-level `codec_rtf` (--full), `stage_all_ms_per_utterance` = both; "
+                                  "Llama-3.2-3B backbone + 3L/2L experts + 4L local decoder x8, V_a=12296, random init",
+                      "parallelism": (f"dp{world} (one utterance per GPU, RCCL all-gather of token tensors inside the timed region)" if use_dist else
+                                      "dp1, no collective (a single rank outside torchrun; `torchrun --nproc-per-node=1 bench.py --gpus 1` runs the RCCL path)")}}
+    if a.full:
+        full_legs(a, model, dev, tokens, mask, log, dt, res, world, rank)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if use_dist:
+        dist.destroy_process_group()
+
+
+def full_legs(a, model, dev, tokens, mask, log, dt, res, world, rank):
+    """--full: everything the result line carries beyond the headline, measured after the timed steps on the same model."""
     # decode-only rate (information): frames after the prefill, graph replay
     utterance(model, tokens, mask, frames=2)
     torch.cuda.synchronize()
@@ -897,20 +946,9 @@ def main():
                 "skip_text_head_audio_ids_identical": same}
     except Exception as e:  # noqa: BLE001 — information
         skip = {"value_skip_text_head": repr(e)[:200]}
-    audio_tokens = 8 * FRAMES * a.steps * world
-    res = {"metric": "audio tokens/sec (TTS greedy)", "value": round(audio_tokens / dt, 1), "unit": "audio tokens/s",
-           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-           "config": {"workload": "TTS --stage all (BASELINE config 2), single utterance, greedy (topk=1), bf16, B=1 per GPU: "
-                                  f"{PROMPT_LEN}-token prompt + {FRAMES} frames x (8 audio + 1 text) tokens; `value` = the stage-1 "
-                                  "audio-token rate (multi_task_inference.py:486-525), stage 2 (codes -> waveform, :527-548) = "
-                                  "top-level `codec_rtf`, `stage_all_ms_per_utterance` = both; "
-                                  "Llama-3.2-3B backbone + 3L/2L experts + 4L local decoder x8, V_a=12296, random init",
-                      "parallelism": (f"dp{world} (one utterance per GPU, RCCL all-gather of token tensors inside the timed region)" if use_dist else
-                                      "dp1, no collective (a single rank outside torchrun; `torchrun --nproc-per-node=1 bench.py --gpus 1` runs the RCCL path)")},
-           **skip,
-           "decode_ms_per_frame": round(ms_frame, 3), "decode_frames_per_s": round(1e3 / ms_frame, 1),
-           "decode_ms_per_frame_p50": round(p50, 3), "decode_ms_per_frame_p99": round(p99, 3)}
+    res.update(skip)
+    res.update({"decode_ms_per_frame": round(ms_frame, 3), "decode_frames_per_s": round(1e3 / ms_frame, 1),
+                "decode_ms_per_frame_p50": round(p50, 3), "decode_ms_per_frame_p99": round(p99, 3)})
     solo = rank == 0 and world == 1
     if solo and not a.no_legs:
         # the contract on which ids are IDENTICAL to the reference's (UA2_F32: the reference ships fp32, multi_task_inference.py:181-183)
@@ -972,10 +1010,6 @@ def main():
             res["config3_asr_batch32_order_free"] = config3_leg(model, dev, order_free_rows=2048)
         except Exception as e:  # noqa: BLE001
             res["config3_asr_batch32_order_free"] = {"error": repr(e)[:200]}
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if use_dist:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -38,3 +38,11 @@ def test_gpus_flag_is_checked_against_visible_devices_and_world_size():
     env.update(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_steps_and_leg_flags_are_validated_before_any_work():
+    """--steps 0 would divide by zero; --config4-leg only selects a leg of --full (a plain run is the headline alone)."""
+    for argv, msg in ((["--steps", "0"], "--steps must be >= 1"), (["--warmup", "-1"], "--warmup >= 0"),
+                      (["--config4-leg"], "pass --full too")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True)
+        assert r.returncode == 2 and msg in r.stderr, (argv, r.stderr[-500:])

@@ -9,9 +9,9 @@ OUT=$R/gpurun_out/final
 mkdir -p $OUT
 export TMPDIR=/tmp
 (timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -15) > $OUT/pytest_gpu.log
-(timeout 1200 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err)
+(timeout 1200 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err)
 # one rank under torchrun: init_process_group("nccl"), all_gather and barrier execute on this box (VERDICT r4 #6a)
-(timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --no-legs --config4-leg --no-cpu-baseline --steps 3 --warmup 1 > $OUT/bench_line_torchrun_1rank.json 2> $OUT/bench_torchrun.err)
+(timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --full --no-legs --config4-leg --no-cpu-baseline --steps 3 --warmup 1 > $OUT/bench_line_torchrun_1rank.json 2> $OUT/bench_torchrun.err)
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/prof_codec -- python $R/tools/ubench/codec_decode.py > $OUT/codec_decode.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -- python $R/tools/ubench/codec_decode.py > /dev/null 2>&1
@@ -21,7 +21,7 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_sw_write -- python $R/tool
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT/pmc_g2_a -- python $R/tools/ubench/pmc_gemm2.py > /dev/null 2>&1
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --kernel-trace -d $OUT/pmc_g2_b -- python $R/tools/ubench/pmc_gemm2.py > /dev/null 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_g2_c -- python $R/tools/ubench/pmc_gemm2.py > /dev/null 2>&1
-rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -- python $R/bench.py --no-cpu-baseline --no-legs --steps 2 > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -- python $R/bench.py --full --no-cpu-baseline --no-legs --steps 2 > /dev/null 2>&1
 for leg in batched batched256 config3 stage2; do
   rocprofv3 --kernel-trace --stats -d $OUT/prof_$leg -- python $R/tools/ubench/prof_legs.py $leg > $OUT/leg_$leg.log 2>&1
 done
