@@ -498,6 +498,18 @@ int ua2_time_film(float* out, const float* params, const float* x, const uint8_t
                   int32_t rows_per_batch, int32_t C, float gamma_scale, void* stream);
 /* F.layer_norm over the last axis of [R, C]; w, b optional (NULL = elementwise_affine=False, transformer_1d_flow.py:252). */
 int ua2_layernorm_rows(float* out, const float* x, const float* w, const float* b, int64_t R, int32_t C, float eps, void* stream);
+/* out[r, :] = rec[r, :] + reason[src[r], :] in fp32 (one rounding), r < rows; D % 4 == 0, out / rec / reason 16-byte aligned,
+ * out may equal rec.  feature_combine of the reasoning-conditioned decode (AudioDiffusion1D.py:440-456): the reason_adaptor
+ * rows up-sampled x2.5 by nearest neighbour (src = the host-built index table, every entry a valid row of `reason`) and
+ * added to the summed RVQ look-ups. */
+int ua2_reason_merge(float* out, const float* rec, const float* reason, const int32_t* src, int64_t rows, int32_t D, void* stream);
+/* Linear cross-fade + crop of n_seg decoded windows (reason_tokenizer.py:210-224): window k (row k of seg, seg_stride
+ * floats apart, first `win` samples used) starts at k * (win - ovlp); in the ovlp samples shared with window k - 1 the
+ * result is (float)((double)old * (1 - ramp[i]) + (double)new * ramp[i]), ramp = np.linspace(0, 1, ovlp), without fused
+ * multiply-adds — the host's float64 blend bit for bit.  out [target_len], target_len <= (n_seg - 1) * (win - ovlp) + win;
+ * requires 0 < ovlp <= win - ovlp and seg_stride >= win. */
+int ua2_crossfade(float* out, const float* seg, int32_t n_seg, int64_t seg_stride, int64_t win, int64_t ovlp, int64_t target_len,
+                  void* stream);
 /* q/k LayerNorm over the head dim + partial rotary embedding + K/V append to the paged cache for the x-transformers
  * style attention of the AudioThinking encoder (modules/transformer.py:447-485, 146-170).  qkv [R, 3*n_head*hs] =
  * (q | k | v); q_out [R, n_head*hs] fp32; cos_t / sin_t [max_pos, rot_dim/2]; norm weights NULL = no q/k norm;

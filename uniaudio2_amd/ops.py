@@ -410,6 +410,33 @@ def gather_rows(x, idx):
     return out
 
 
+def reason_merge(rec, reason, src, out=None, src_checked=False):
+    """rec [R, D] + reason[src] -> [R, D] fp32 (ua2_reason_merge): feature_combine's `rec_feature + reasoning_feature` after
+    the x2.5 nearest up-sampling (AudioDiffusion1D.py:440-456).  src [R] int32 on the device; out may be rec (in place).
+    Unless the caller vouches for the table (src_checked=True, built once and checked on the host), it is checked here
+    against reason's row count — one small device-to-host copy."""
+    R, D = rec.shape
+    if src.numel() != R or src.dtype != torch.int32 or reason.shape[-1] != D:
+        raise ValueError(f"reason_merge: rec {tuple(rec.shape)}, reason {tuple(reason.shape)}, src {tuple(src.shape)} {src.dtype}")
+    if not src_checked:
+        lo, hi = (int(v) for v in src.aminmax())
+        if lo < 0 or hi >= reason.shape[0]:
+            raise ValueError(f"reason_merge: src entries in [{lo}, {hi}] but reason has {reason.shape[0]} rows")
+    if out is None:
+        out = torch.empty(R, D, dtype=torch.float32, device=rec.device)
+    check(lib.ua2_reason_merge(ptr(out), ptr(rec), ptr(reason), ptr(src), R, D, stream()), "ua2_reason_merge")
+    return out
+
+
+def crossfade(seg, win, ovlp, target_len):
+    """seg [n_seg, N >= win] fp32 decoded windows -> [target_len] joined waveform (ua2_crossfade): the float64 linear
+    cross-fade of reason_tokenizer.py:210-224 (== reason_tokenizer.crossfade_concat bit for bit) and the crop."""
+    n_seg, stride = seg.shape
+    out = torch.empty(int(target_len), dtype=torch.float32, device=seg.device)
+    check(lib.ua2_crossfade(ptr(out), ptr(seg), n_seg, stride, int(win), int(ovlp), int(target_len), stream()), "ua2_crossfade")
+    return out
+
+
 def time_film(params, x, batch_mask, rows_per_batch, gamma_scale):
     R, Cc = x.shape
     out = torch.empty_like(x)

@@ -187,6 +187,7 @@ class AudioDiffusion1D(nn.Module):
             self.cfm_wrapper = BASECFM(Transformer1DModel.from_config(unet_model_config_path))
         self.audio_thinking = AudioThinking(dim=D, interval=5, encoder_depth=encoder_depth, whisper_fea_dim=whisper_fea_dim)
         self._p = None
+        self._reason_rows = {}
 
     def init_device_dtype(self, device, dtype):
         self.device, self.dtype = device, dtype
@@ -326,9 +327,26 @@ class AudioDiffusion1D(nn.Module):
     def prepare_latents(self, batch_size, num_frames, dtype, device):
         return torch.randn(batch_size, num_frames, self.sq_codec_latent, device=device, dtype=torch.float32)      # :651-656
 
+    def reason_rows(self, T_q, T, B, device):
+        """Row table of feature_combine's x2.5 nearest up-sampling + crop (:449-453) for B utterances: row b * T + t of the
+        up-sampled features is reason_adaptor row b * T_q + nearest_indices(T_q, 2.5)[t].  Built and checked on the host
+        once per (T_q, T, B, device)."""
+        key = (T_q, T, B, str(device))
+        cache = self._reason_rows
+        if key not in cache:
+            up = nearest_indices(T_q, 2.5, "cpu")
+            if up.numel() < T:
+                raise ValueError(f"inference_codes: {T_q} reasoning codes up-sample to {up.numel()} rows, fewer than the {T} "
+                                 f"reconstruction codes (the reference's feature_combine fails on this shape mismatch too)")
+            up = up[:T]
+            cache[key] = torch.cat([up + b * T_q for b in range(B)]).to(torch.int32).to(device)
+        return cache[key]
+
     @torch.inference_mode()
-    def codes_to_condition(self, codes):
-        """:563-590 without reasoning codes: (B, 8, T) -> (B, 2T, D): sum of the three look-ups, cond_feature_emb, x2 nearest."""
+    def codes_to_condition(self, codes, reason=None):
+        """:563-590: (B, 8, T) -> (B, 2T, D): sum of the three look-ups, cond_feature_emb, x2 nearest.  reason (B, 8, T_q)
+        (the two-stream form of token2audio): feature_combine (:440-456) before cond_feature_emb — reasoning_vq look-up,
+        reason_adaptor, x2.5 nearest up-sampling cropped to T, added to the sum (ua2_reason_merge, in place)."""
         p = self._plan()
         B, _, T = codes.shape
         parts = ((self.vq_pronunciation_semantic, codes[:, 0:1]), (self.vq_structure_semantic, codes[:, 1:2]), (self.vq_acoustic, codes[:, 2:]))
@@ -336,19 +354,35 @@ class AudioDiffusion1D(nn.Module):
         for vq, c in parts:
             r = vq.get_output_from_indices(c.transpose(1, 2).contiguous()).reshape(-1)
             q = r if q is None else ops.ew_fma(q, c=r)
+        if reason is not None:
+            if reason.shape[0] != B:
+                raise ValueError(f"inference_codes: reasoning codes of batch {reason.shape[0]}, reconstruction codes of batch {B}")
+            T_q = reason.shape[-1]
+            src = self.reason_rows(T_q, T, B, q.device)
+            rq = self.audio_thinking.reasoning_vq.get_output_from_indices(reason.transpose(1, 2).contiguous())
+            rf = p["reason_adaptor"](rq.reshape(B * T_q, self.codec_dim).float().contiguous())
+            q = q.view(B * T, self.codec_dim)
+            ops.reason_merge(q, rf, src, out=q, src_checked=True)
         m = p["cond_feature_emb"](q.view(B * T, self.codec_dim))
         up = nearest_indices(T, 2, m.device)
         return ops.gather_rows(m, torch.cat([up + b * T for b in range(B)])).view(B, up.numel(), self.codec_dim)
 
     @torch.inference_mode()
     def inference_codes(self, codes, spk_embeds, true_latents, latent_length, incontext_length, additional_feats=None, guidance_scale=2,
-                        num_steps=20, disable_progress=True, scenario="start_seg", noise=None, estimator=None):
-        """:554-624.  codes = [rec_codes (1, 8, T)] (token2audio_no_reason's form); returns latents (1, 2T, 136)."""
-        if len(codes) != 1:
-            raise NotImplementedError("reasoning-code conditioning (feature_combine, :440-456) is used by token2audio only; "
-                                      "the CLI decodes with token2audio_no_reason (multi_task_inference.py:545-548)")
+                        num_steps=20, disable_progress=True, scenario="start_seg", noise=None, estimator=None, return_reasoning_text=False):
+        """:554-624.  codes = [rec_codes (B, 8, T)] (token2audio_no_reason's form) or [reason_codes (B, 8, T_q), rec_codes (B, 8, T)]
+        (token2audio's, :563-585: the reasoning features join the condition through feature_combine; T_q * 2.5 >= T or
+        ValueError); returns latents (B, 2T, 136).  return_reasoning_text is accepted because the reference's token2audio
+        passes it from its second window on (reason_tokenizer.py:201) although its inference_codes has no such parameter
+        (a TypeError there); the reasoning-text LLM is not built, so only False is accepted."""
+        if return_reasoning_text:
+            raise NotImplementedError("the reasoning-text LLM of AudioThinking is not part of the token path and is not built")
+        if len(codes) not in (1, 2):
+            raise ValueError(f"inference_codes: codes = [rec] or [reason, rec], got {len(codes)} tensors")
         p = self._plan()
-        merge = self.codes_to_condition(codes[0].to(p["zero_cond"].device))
+        dev = p["zero_cond"].device
+        reason = codes[0].to(dev) if len(codes) == 2 else None
+        merge = self.codes_to_condition(codes[-1].to(dev), reason)
         B, T, D = merge.shape
         dev = merge.device
         lat = noise if noise is not None else self.prepare_latents(B, T, torch.float32, dev)

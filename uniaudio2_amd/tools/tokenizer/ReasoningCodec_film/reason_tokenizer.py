@@ -8,6 +8,11 @@ Mirror of the reference's tools/tokenizer/ReasoningCodec_film/reason_tokenizer.p
     flow-matching DiT + guided Euler ODE, the previous window's last 32 latent frames as in-context
     frames) -> `SQCodec.decode` (ScalarModel) -> linear cross-fade of the 25 % overlap in float64 on the
     host, crop to T / 12.5 * 24000 samples.
+  * `detokenize(reason (8, T_q), rec (8, T), ...) -> wave (1, N) float32 CPU` (:393-397) through `token2audio` (:132-226):
+    the same pipeline at 30-s windows (375 codes, hop 279, overlap 96, 750 latent frames), each window also conditioned on
+    150 reasoning codes (feature_combine); the decoded windows are joined on the device (ua2_crossfade).  Window k >= 1 takes
+    reason codes [111 k, 111 k + 150), where the reference stays at [0, 150) and fails (reason_window_plan); `detokenize_batch`
+    runs window k of several utterances in one solve.
   * `tokenize(wav path) -> (reason (8, T_r), rec (8, T_s))` (:377-387): load, down-mix, resample to 24 kHz
     (torchaudio's windowed-sinc algorithm restated as one MFMA GEMM, `resample`), then `audio2token`
     (:86-129): tile the clip to 30-s segments (+240 samples), `model.fetch_codes_batch` per batch of 6
@@ -40,6 +45,30 @@ def window_plan(rec_codes_len, duration=20, rec_frame_rate=12.5, sample_rate=240
     return dict(tiled_len=n, min_codes=min_samples, hop_codes=hop_samples, ovlp_codes=ovlp_samples, starts=starts,
                 ovlp_frames=ovlp_samples // 2, latent_length=int(duration * sq_codec_hz), target_len=target_len,
                 wav_window=wav_min, wav_hop=wav_hop, wav_ovlp=wav_min - wav_hop)
+
+
+def reason_window_plan(reason_codes_len, n_windows, duration=30, reason_frame_rate=5):
+    """Index arithmetic of token2audio's reasoning stream (:150-153, 162-178, 185-187) — pure function.  The reference tiles the
+    5-Hz reason codes on their own length by the rec stream's rule (min 150, hop 111, overlap 39 at 30 s) to
+    `reference_tiled_len`, and conditions EVERY window on reason[:, :, 0:150]: its window counter `cnt` (:184) is never
+    incremented, and from the second window on the call raises TypeError anyway (:201 passes `return_reasoning_text=` to an
+    inference_codes without that parameter), so it decodes at most one window.  Divergence, following the evident intent:
+    window k takes reason[:, :, 111 k : 111 k + 150], and the tiled stream is self-concatenated further (tile_codes on the
+    reference's tiled stream) until it covers (n_windows - 1) * 111 + 150 codes.  Window 0 is the reference's."""
+    min_q = int(duration * reason_frame_rate)
+    hop_q = min_q // 4 * 3
+    ovlp_q = min_q - hop_q
+    n = max(reason_codes_len, min_q)                                 # :162-165
+    if (n - ovlp_q) % hop_q > 0:
+        n = math.ceil((n - ovlp_q) / float(hop_q)) * hop_q + ovlp_q   # :174-178
+    starts = [k * hop_q for k in range(n_windows)]
+    return dict(reference_tiled_len=n, tiled_len=max(n, starts[-1] + min_q if starts else n), min_codes=min_q, hop_codes=hop_q,
+                ovlp_codes=ovlp_q, starts=starts)
+
+
+def tile_reason_codes(reason_codec, qplan):
+    """The reference's tiling of the reason stream (:162-178), then the extension of reason_window_plan."""
+    return tile_codes(tile_codes(reason_codec, qplan["reference_tiled_len"]), qplan["tiled_len"])
 
 
 def tile_codes(rec_codec, tiled_len):
@@ -368,6 +397,126 @@ class ReasoningTokenizer:
                     latents[u].append(lat[k:k + 1])
                     segments[u].append(wav[k])
         return [crossfade_concat(seg, p["wav_window"], p["wav_ovlp"], p["target_len"]) for seg, p in zip(segments, plans)]
+
+    # Windows decoded by one SQCodec.decode call: an utterance's windows go through the decoder together (bit-identical to one
+    # window per call, tests/test_gpu_reason_decode.py), at most this many at a time to bound the decoder's activations.
+    decode_windows = 8
+
+    def _decode_join(self, latents, plan):
+        """latents: one (B, L, 136) tensor per window -> waves (B, target_len) float32 on the CPU.  The windows are decoded in
+        calls of up to `decode_windows` and joined by the float64 linear cross-fade + crop of :210-224 — on the device
+        (ua2_crossfade, one copy to the host at the end) when the decoder returns device tensors, by crossfade_concat on the
+        host for CPU stand-ins; the two are bit-identical."""
+        n, B = len(latents), latents[0].shape[0]
+        wavs = []
+        for c in range(0, n, self.decode_windows):
+            lat = torch.cat(latents[c:c + self.decode_windows], 0)                  # window-major: row k * B + b
+            wavs.append(self.SQCodec.decode(lat.transpose(1, 2).contiguous()))
+        wav = torch.cat(wavs, 0).view(n, B, -1)
+        if wav.is_cuda:
+            out = [ops.crossfade(wav[:, b].contiguous(), plan["wav_window"], plan["wav_ovlp"], plan["target_len"]) for b in range(B)]
+            return torch.stack(out).cpu()
+        return torch.cat([crossfade_concat([wav[k, b:b + 1] for k in range(n)], plan["wav_window"], plan["wav_ovlp"], plan["target_len"])
+                          for b in range(B)], 0)
+
+    def _require_dit(self, return_reasoning_text=False):
+        if return_reasoning_text:
+            raise NotImplementedError("return_reasoning_text=True needs the reasoning-text LLM of AudioThinking, which is not built")
+        if self.model is None or not hasattr(self.model, "cfm_wrapper"):
+            raise NotImplementedError("decoding needs the codec model with its flow-matching DiT (AudioDiffusion1D(unet_model_config_path=...))")
+
+    @torch.no_grad()
+    def token2audio(self, reason_codec, rec_codec, return_reasoning_text=False, duration=30, guidance_scale=1.5, num_steps=10,
+                    disable_progress=False):
+        """:132-226: reason_codec (B, 8, T_q) + rec_codec (B, 8, T) -> waves (B, int(T / 12.5 * 24000)) float32 on the CPU.
+        30-s windows: 375 rec codes (hop 279, overlap 96 -> 48 in-context latent frames, 750 latent frames) conditioned on 150
+        reason codes each (reason_window_plan: window 0 as the reference, window k >= 1 on reason codes [111 k, 111 k + 150) —
+        the reference never advances its reason window and fails from the second window on, see there).
+        Randomness as the reference: the first window's `true` latent (B, 750, 136) is drawn on the CPU generator before any
+        tiling (:140), every later window draws its (B, 702, 136) tail on the CPU (:200), inference_codes draws its start noise
+        on the device generator (AudioDiffusion1D.py:653-656).  `guidance_scale` is accepted and not used: the reference passes
+        the literal 1.5 (:193, :201).  The windows' latents are decoded together and joined on the device (_decode_join)."""
+        self._require_dit(return_reasoning_text)
+        rec_codec, reason_codec = rec_codec.to(self.device), reason_codec.to(self.device)
+        B = rec_codec.shape[0]
+        if reason_codec.shape[0] != B:
+            raise ValueError(f"token2audio: reason codes of batch {reason_codec.shape[0]}, rec codes of batch {B}")
+        L = int(duration * self.sq_codec_hz)
+        first = torch.randn(B, L, self.model.sq_codec_latent).to(self.device)          # :140, before any tiling
+        plan = window_plan(rec_codec.shape[-1], duration, self.rec_frame_rate, self.sample_rate, self.sq_codec_hz)
+        qplan = reason_window_plan(reason_codec.shape[-1], len(plan["starts"]), duration, self.reason_frame_rate)
+        rec_codec = tile_codes(rec_codec, plan["tiled_len"])
+        reason_codec = tile_reason_codes(reason_codec, qplan)
+        ov = plan["ovlp_frames"]
+        latents = []
+        for i, (s0, q0) in enumerate(zip(plan["starts"], qplan["starts"])):
+            codes_input = [reason_codec[:, :, q0:q0 + qplan["min_codes"]], rec_codec[:, :, s0:s0 + plan["min_codes"]]]
+            if i == 0:
+                true, n_inc = first, 0
+            else:                                                      # :196-202: the previous window's tail as in-context frames
+                tail = latents[-1][:, -ov:, :]
+                true, n_inc = torch.cat([tail, torch.randn(B, L - ov, tail.shape[-1]).to(self.device)], 1), ov
+            lat = self.model.inference_codes(codes_input, None, true, L, n_inc, additional_feats=[], guidance_scale=1.5, num_steps=num_steps,
+                                             disable_progress=disable_progress, scenario="other_seg")
+            latents.append(lat.float())
+        return self._decode_join(latents, plan)
+
+    def detokenize(self, reason_codec, rec_codec, return_reasoning_text=False, min_duration=30, steps=50, guidance_scale=1.5,
+                   disable_progress=False):
+        """reason_codec (8, T_q), rec_codec (8, T) -> wave (1, N) float32 on the CPU (:393-397)."""
+        return self.token2audio(reason_codec.unsqueeze(0), rec_codec.unsqueeze(0), return_reasoning_text, duration=min_duration,
+                                guidance_scale=guidance_scale, num_steps=steps, disable_progress=disable_progress)
+
+    @torch.no_grad()
+    def detokenize_batch(self, reason_codecs, rec_codecs, steps=50, guidance_scale=1.5, max_batch=8, duration=30):
+        """lists of reason_codec (8, T_q,u) and rec_codec (8, T_u) -> list of waves (1, N_u) float32 on the CPU: `detokenize` for
+        several utterances, window k of up to `max_batch` of them in ONE guided solve (the two-stream twin of
+        detokenize_no_reason_batch).  Every torch.randn of the one-by-one path — :140 / :200 on the CPU generator, the start
+        noise on the device generator — is drawn here in the order a loop over `detokenize` consumes them, so under the
+        row-invariant contract (Transformer1DModel.sum_order = 0) each wave is bit-identical to the loop's.  Each utterance's
+        windows are then decoded and joined as `detokenize` does (_decode_join)."""
+        if len(reason_codecs) != len(rec_codecs):
+            raise ValueError(f"detokenize_batch: {len(reason_codecs)} reason streams for {len(rec_codecs)} rec streams")
+        self._require_dit()
+        if not hasattr(self.model, "prepare_latents"):
+            return [self.detokenize(q, c, steps=steps, guidance_scale=guidance_scale, min_duration=duration) for q, c in zip(reason_codecs, rec_codecs)]
+        dev = self.device
+        L, Cl = int(duration * self.sq_codec_hz), self.model.sq_codec_latent
+        cpu_noise, dev_noise, plans, qplans, tiled, tiled_q = [], [], [], [], [], []
+        for q, c in zip(reason_codecs, rec_codecs):                    # the one-by-one consumption order of both generators
+            cn = [torch.randn(1, L, Cl)]                               # :140 first, before any tiling
+            p = window_plan(c.shape[-1], duration, self.rec_frame_rate, self.sample_rate, self.sq_codec_hz)
+            qp = reason_window_plan(q.shape[-1], len(p["starts"]), duration, self.reason_frame_rate)
+            dn = []
+            for i in range(len(p["starts"])):
+                if i > 0:
+                    cn.append(torch.randn(1, L - p["ovlp_frames"], Cl))   # :200
+                dn.append(self.model.prepare_latents(1, L, torch.float32, dev))
+            cpu_noise.append(cn); dev_noise.append(dn); plans.append(p); qplans.append(qp)
+            tiled.append(tile_codes(c.unsqueeze(0).to(dev), p["tiled_len"]))
+            tiled_q.append(tile_reason_codes(q.unsqueeze(0).to(dev), qp))
+        ov = plans[0]["ovlp_frames"] if plans else 0
+        nwin = [len(p["starts"]) for p in plans]
+        latents = [[] for _ in rec_codecs]
+        step = max(1, max_batch)
+        for i in range(max(nwin, default=0)):
+            active = [u for u, w in enumerate(nwin) if w > i]
+            for g0 in range(0, len(active), step):
+                grp = active[g0:g0 + step]
+                s0, q0 = plans[grp[0]]["starts"][i], qplans[grp[0]]["starts"][i]      # the same for every utterance
+                rec = torch.cat([tiled[u][:, :, s0:s0 + plans[u]["min_codes"]] for u in grp], 0)
+                reason = torch.cat([tiled_q[u][:, :, q0:q0 + qplans[u]["min_codes"]] for u in grp], 0)
+                noise = torch.cat([dev_noise[u][i] for u in grp], 0)
+                if i == 0:
+                    true, n_inc = torch.cat([cpu_noise[u][0] for u in grp], 0).to(dev), 0
+                else:
+                    true = torch.cat([torch.cat([latents[u][-1][:, -ov:, :], cpu_noise[u][i].to(dev)], 1) for u in grp], 0)
+                    n_inc = ov
+                lat = self.model.inference_codes([reason, rec], None, true, L, n_inc, additional_feats=[], guidance_scale=1.5,
+                                                 num_steps=steps, scenario="other_seg", noise=noise).float()
+                for k, u in enumerate(grp):
+                    latents[u].append(lat[k:k + 1])
+        return [self._decode_join(lat, p) for lat, p in zip(latents, plans)]
 
     def detokenize_no_reason(self, rec_codec, return_reasoning_text=False, min_duration=30, steps=50, guidance_scale=1.5,
                              disable_progress=False):
