@@ -346,6 +346,14 @@ int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_t ld, int32
                     int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
                     int32_t C, float* next_h, int32_t row_key_shift, void* stream);
 
+/* n-gram repeat filter of the text loop (evaluation/asr_task.py:329-432 generate_asr_with_ngram_sampling, :407-432).  Row r
+ * (r < R): candidate c = out[r * ld], generated ids H = hist[r * cap ...], L = hist_len[r] of them.  c is replaced by `fallback`
+ * when the n-gram (last n - 1 ids of H, c) already occurs in H; the final id is appended to H when L < cap and hist_len[r] becomes
+ * L + 1.  Nothing is written at or past cap; a row with L > cap passes c through unfiltered (its suffix is no longer stored).
+ * 2 <= n <= 16.  One 256-thread workgroup per row. */
+int ua2_ngram_filter(int32_t* out, int32_t ld, int32_t R, int32_t n, int32_t fallback,
+                     int32_t* hist, int32_t* hist_len, int32_t cap, void* stream);
+
 /* ---- codec: residual vector quantisation ------------------------------------------------ */
 
 /* Nearest-codeword search, level by level on the residual (core_vq.py:179-185, 365-376; the live codec's
@@ -598,6 +606,13 @@ int ua2_stage3_set_prefill_groups(ua2_stage3* h, const int32_t* group_rows, cons
  * batch (>= rows) then differs by fp32 summation noise in its K/V cache, i.e. by bf16-level noise in later logits — the same
  * class of difference the MFMA prefill attention already has against decode rows.  Below the threshold nothing changes. */
 int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows);
+/* n-gram repeat filter of the text-feedback frames: with n >= 2 every feedback of mode 1 (ua2_stage3_frame with or without
+ * UA2_FRAME_SKIP_AUDIO_EXPERTS, and the standalone feedback) first runs the n-gram filter above over the text ids of its R rows,
+ * so the frame log and the fed-back text id carry the filtered id.  hist [max_batch, cap] / hist_len [max_batch] int32 are
+ * device buffers owned by the caller, like the rest of the decode state.  n <= 1 turns the filter off.  The captured frame graphs
+ * are keyed on n (switching the filter off and on again re-uses them); a new fallback, new buffers or a new cap drop them.
+ * Modes 0 and 2 are never filtered. */
+int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, int32_t* hist, int32_t* hist_len, int32_t cap);
 /* cfg_scale > 1: frames of (conditional, unconditional) row pairs — rows 2p, 2p + 1; an even row count — sample from the guided
  * logits (ua2_cfg_mix); feedback mode 2 continues every row from its pair's conditional row. */
 int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale);

@@ -107,6 +107,7 @@ _EXPORTS = {
     "ua2_cfg_mix": (C.c_int, [vp, i32, i32, C.c_float, vp, vp, vp, i32, vp]),
     "ua2_stage3_set_cfg": (C.c_int, [vp, C.c_float]),
     "ua2_stage3_set_order_free_rows": (C.c_int, [vp, i32]),
+    "ua2_stage3_set_ngram": (C.c_int, [vp, i32, i32, vp, vp, i32]),
     "ua2_linear_workspace_bytes": (C.c_size_t, [C.c_int, i64, i64]),
     "ua2_linear_chain_timed": (C.c_int, [C.POINTER(LinearArgs), i32, i32, vp, C.POINTER(C.c_float)]),
     "ua2_attn": (C.c_int, [C.POINTER(AttnArgs), vp]),
@@ -130,6 +131,7 @@ _EXPORTS = {
     "ua2_layernorm_rows": (C.c_int, [vp, vp, vp, vp, i64, i32, f32, vp]),
     "ua2_reason_merge": (C.c_int, [vp, vp, vp, vp, i64, i32, vp]),
     "ua2_crossfade": (C.c_int, [vp, vp, i32, i64, i64, i64, i64, vp]),
+    "ua2_ngram_filter": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "ua2_qknorm_rope_kv": (C.c_int, [C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, C.POINTER(KvGeom), vp]),
     "ua2_stage3_scratch_floats": (C.c_size_t, [C.POINTER(Stage3Desc)]),
     "ua2_stage3_create": (C.c_int, [C.POINTER(Stage3Desc), C.POINTER(vp)]),

@@ -141,3 +141,44 @@ extern "C" int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_
   UA2_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- n-gram repeat filter of the text loop (evaluation/asr_task.py:329-432 generate_asr_with_ngram_sampling) ----------------
+// Row r holds the generated text ids H = hist[r*cap .. r*cap + L), L = hist_len[r], and the frame's candidate c = out[r*ld].
+// c is banned when (H[L-n+1 .. L) , c) already occurs as an n-gram of H (_should_reject_ngram :407-415 over the n-grams that
+// _update_ngrams_simple :424-432 collects); a banned c becomes `fallback` (_get_fallback_token :417-421).  The final id is
+// appended and hist_len becomes L + 1 (EOS included: the loops stop there and discard every later frame).  One workgroup per
+// row; its threads test the start positions i in [0, L - n] in parallel.  Nothing is written at or past cap: a row with
+// L >= cap keeps its stored history, and a row with L > cap (whose suffix is no longer stored) passes c through unfiltered —
+// the host refuses to run a frame whose result it keeps into that state (Model_stage3.generate_frames).
+__global__ __launch_bounds__(256) void ngram_filter_kernel(int32_t* __restrict__ out, int ld, int n, int fallback,
+                                                           int32_t* __restrict__ hist, int32_t* __restrict__ hist_len, int cap) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  int32_t* h = hist + (size_t)r * cap;
+  const int L = max(hist_len[r], 0);
+  const int32_t c = out[(size_t)r * ld];
+  int hit = 0;
+  if (L <= cap && L >= n) {                      // L == n - 1: no n-gram in H yet, nothing to match
+    const int32_t* suf = h + (L - n + 1);        // the last n - 1 ids
+    for (int i = tid; i <= L - n; i += blockDim.x) {
+      bool eq = h[i + n - 1] == c;
+      for (int j = 0; eq && j < n - 1; ++j) eq = h[i + j] == suf[j];
+      hit |= eq ? 1 : 0;
+    }
+  }
+  hit = __syncthreads_or(hit);                   // every thread has read c and H before thread 0 writes
+  if (tid == 0) {
+    const int32_t id = hit ? fallback : c;
+    out[(size_t)r * ld] = id;
+    if (L < cap) h[L] = id;
+    hist_len[r] = L + 1;
+  }
+}
+
+extern "C" int ua2_ngram_filter(int32_t* out, int32_t ld, int32_t R, int32_t n, int32_t fallback, int32_t* hist,
+                                int32_t* hist_len, int32_t cap, void* stream) {
+  UA2_CHECK(out && hist && hist_len && R > 0 && ld >= 1 && cap >= 1, "ua2_ngram_filter: bad arguments");
+  UA2_CHECK(n >= 2 && n <= 16, "ua2_ngram_filter: n must be in 2..16, got %d", n);
+  hipLaunchKernelGGL(ngram_filter_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, out, ld, n, fallback, hist, hist_len, cap);
+  UA2_LAUNCH_CHECK();
+  return 0;
+}

@@ -61,6 +61,9 @@ struct ua2_stage3 {
   // row groups of the next ua2_stage3_trunk call (prefill): the trunk's attention then runs the MFMA flash kernel
   const int32_t *group_rows = nullptr, *group_seq = nullptr, *group_nkeys = nullptr;
   int32_t n_groups = 0, group_q_tiles = 0;
+  // n-gram repeat filter of the text-feedback frames (ua2_stage3_set_ngram; ngram_n <= 1 = off): caller-owned device history
+  int32_t ngram_n = 0, ngram_fallback = 0, ngram_cap = 0;
+  int32_t *ngram_hist = nullptr, *ngram_hist_len = nullptr;
   std::map<std::tuple<int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
 };
 
@@ -509,6 +512,22 @@ extern "C" int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows) {
   return 0;
 }
 
+extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, int32_t* hist, int32_t* hist_len, int32_t cap) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_ngram: NULL handle");
+  if (n <= 1) {                    // off: the frame graphs key on n, so the filtered ones stay valid for the same buffers
+    h->ngram_n = 0;
+    return 0;
+  }
+  UA2_CHECK(n <= 16, "ua2_stage3_set_ngram: n must be <= 16, got %d", n);
+  UA2_CHECK(hist && hist_len && cap >= 1, "ua2_stage3_set_ngram: missing history buffers");
+  if (fallback != h->ngram_fallback || hist != h->ngram_hist || hist_len != h->ngram_hist_len || cap != h->ngram_cap) {
+    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);   // recorded text frames bake the filter's arguments: drop them
+    h->graphs.clear();
+  }
+  h->ngram_n = n; h->ngram_fallback = fallback; h->ngram_hist = hist; h->ngram_hist_len = hist_len; h->ngram_cap = cap;
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale) {
   UA2_CHECK(h != nullptr && cfg_scale >= 1.f, "ua2_stage3_set_cfg: NULL handle or cfg_scale < 1");
   h->cfg_scale = cfg_scale;
@@ -659,6 +678,11 @@ extern "C" int ua2_stage3_heads(ua2_stage3* h, int32_t R, void* stream) { return
 static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card, void* stream, int no_text) {
   UA2_CHECK(h && R > 0 && R <= h->d.max_rows && mode >= 0 && mode <= 2, "ua2_stage3_feedback: bad arguments");
   const ua2_stage3_desc& d = h->d;
+  if (mode == 1 && h->ngram_n > 1) {   // asr_task.py:371-375: the filtered id is what the log records and the next frame consumes
+    UA2_CHECK(R <= d.max_batch, "ua2_stage3_feedback: n-gram history holds %d rows, R=%d", d.max_batch, R);
+    if (int rc = ua2_ngram_filter(d.out_tokens, d.n_cb + 1, R, h->ngram_n, h->ngram_fallback, h->ngram_hist, h->ngram_hist_len,
+                                  h->ngram_cap, stream)) return rc;
+  }
   hipLaunchKernelGGL(feedback_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, R, d.n_cb, mode, reason_eos,
                      reason_card, d.log_frames, d.max_rows, d.tokens, d.mask, d.row_pos, d.forbid, d.out_tokens,
                      d.frame_log, d.counters, no_text);
@@ -690,7 +714,10 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   int tbits, cbits;
   memcpy(&tbits, &h->temperature, sizeof(int));
   memcpy(&cbits, &h->cfg_scale, sizeof(int));
-  const auto key = std::make_tuple((int)R, (int)mode | (skip_text ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0), (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);
+  // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram)
+  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;
+  const auto key = std::make_tuple((int)R, (int)mode | (skip_text ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram,
+                                   (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     hipGraph_t graph = nullptr;

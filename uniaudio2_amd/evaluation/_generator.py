@@ -274,10 +274,23 @@ class GeneratorBase:
         return out
 
     @torch.inference_mode()
-    def _generate_text(self, tokens, tokens_mask, topk=1, temperature=1.0, max_frames=500) -> str:
-        """The loop of generate_asr / generate_audio_caption / generate_answer (asr_task.py:658-688)."""
+    def _generate_text(self, tokens, tokens_mask, topk=1, temperature=1.0, max_frames=500, no_repeat_ngram_size=0,
+                       ngram_fallback=128000) -> str:
+        """The loop of generate_asr / generate_audio_caption / generate_answer (asr_task.py:658-688).
+        no_repeat_ngram_size >= 2: the loop of generate_asr_with_ngram_sampling (asr_task.py:359-400) — every frame's text id
+        that would repeat an n-gram of the ids generated so far becomes `ngram_fallback`, on the device (Model_stage3.set_ngram);
+        the filter is on for this loop only."""
         B, L = self._prefill([tokens], [tokens_mask])
         self._set_sampling(topk, temperature)
+        if no_repeat_ngram_size > 1:
+            self._model.set_ngram(no_repeat_ngram_size, ngram_fallback, capacity=max_frames)
+            try:
+                return self._text_loop(L, max_frames)
+            finally:
+                self._model.set_ngram(0)
+        return self._text_loop(L, max_frames)
+
+    def _text_loop(self, L, max_frames):
         text, frame, done = [], 0, False
         while not done and frame < max_frames:
             n = min(self.chunk_frames, max_frames - frame)

@@ -1,6 +1,6 @@
-"""Mirror of the reference's evaluation/asr_task.py `Generator` (greedy `generate_asr`).  Not mirrored: the beam
-search (:438-, calls a method Model_stage3 lacks — SURVEY Appendix A.9) and the n-gram variant (:329-405: it prefills
-with the training forward `self._model(...)`, :356, which never writes the KV cache, so it decodes without its prompt)."""
+"""Mirror of the reference's evaluation/asr_task.py `Generator`: greedy `generate_asr` and the n-gram-constrained
+`generate_asr_with_ngram_sampling` (:329-432).  Not mirrored: the beam search (:438-, calls a method Model_stage3 lacks —
+SURVEY Appendix A.9)."""
 import torch
 
 from ._generator import GeneratorBase
@@ -13,6 +13,23 @@ class Generator(GeneratorBase):
         """reason_token (T_r, 8), semantic_token (T_s, 8) long -> transcription text (asr_task.py:630-688)."""
         tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature)
+
+    @torch.inference_mode()
+    def generate_asr_with_ngram_sampling(self, task_prompt, task_name, text_token=None, semantic_token=None, reason_token=None,
+                                         temperature: float = 0.9, topk: int = 200, cfg_scale=1.0, no_repeat_ngram_size: int = 3,
+                                         repetition_penalty: float = 1.2, *, fallback_token: int = 128000) -> str:
+        """asr_task.py:329-405: the generate_asr loop where a text id that would repeat an n-gram of the ids generated so far
+        (`no_repeat_ngram_size`; the prompt is not part of the history) is replaced by the fixed id `fallback_token` (128000 in
+        the reference, _get_fallback_token :417-421), which is fed back and enters the history; the loop stops at EOS (128001),
+        which therefore is never banned.  The filter runs on the device between the text sample and the feedback
+        (Model_stage3.set_ngram).  `repetition_penalty` is unused, as in the reference.  no_repeat_ngram_size <= 1 bans nothing
+        (the reference's n == 1 never finds a banned id either) and runs the plain loop.
+        One departure: the reference prefills with the training forward `self._model(...)` (:356), which passes no positions to the
+        two experts and so never fills their KV caches — its first frame then attends to zeroed expert K/V.  Here the prefill is
+        generate_asr's (forward_prefix), so the n-gram loop decodes from the same state as the greedy one."""
+        tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
+        return self._generate_text(tokens, mask, topk=topk, temperature=temperature, no_repeat_ngram_size=no_repeat_ngram_size,
+                                   ngram_fallback=fallback_token)
 
     # audio_music_caption_task.py uses the same prompt layout and loop under another name
     generate_audio_caption = generate_asr

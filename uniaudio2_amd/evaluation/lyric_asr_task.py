@@ -18,3 +18,8 @@ class Generator(_AsrGenerator):
         """reason_token (T_r, 8), semantic_token (T_s, 8) long -> lyric text (lyric_asr_task.py:202-254)."""
         tokens, mask = self.prepare_lyric_asr_task(task_prompt, reason_token, semantic_token)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature)
+
+    def generate_asr_with_ngram_sampling(self, *args, **kwargs):
+        """The reference's lyric Generator has no n-gram variant (the CLI's `--decode_type ngram` fails there with AttributeError)."""
+        raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "
+                         "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")

@@ -136,6 +136,8 @@ class Model_stage3(nn.Module):
         self._cfg = 1.0
         self._pos_hi = 0
         self._text_fed_back = False    # the last frame run was a text-feedback frame (every row now holds masks audio 0 / text 1)
+        self._ngram = None             # (n, fallback, capacity) of the text frames' n-gram filter (set_ngram); None = off
+        self._ngram_hi = 0             # upper bound of every live row's n-gram history length (host side: no device sync)
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
             self.set_order_free_rows(self.order_free_rows)
 
@@ -192,6 +194,9 @@ class Model_stage3(nn.Module):
         st["mask"][:R].copy_(tokens_mask)
         st["row_pos"][:R].copy_(pos)
         st["row_seq"][:R].copy_(seq)
+        if "ngram_len" in st:                      # rows that start here start with an empty n-gram history
+            st["ngram_len"][:R].zero_()
+            self._ngram_hi = 0
         return R
 
     # ---- reference-compatible methods ---------------------------------------------------------
@@ -277,6 +282,35 @@ class Model_stage3(nn.Module):
             check(lib.ua2_stage3_set_cfg(self._h, cfg_scale), "ua2_stage3_set_cfg")
             self._cfg = cfg_scale
 
+    def set_ngram(self, n: int = 0, fallback: int = 128000, capacity: int = 512):
+        """n-gram repeat filter of the text-feedback frames (generate_frames mode 1; evaluation/asr_task.py:329-432
+        generate_asr_with_ngram_sampling): a text id that would repeat an n-gram of the ids the row's filtered text frames have
+        produced since its decode started becomes `fallback`, on the device between the text sample and the feedback
+        (include/ua2hip.h ua2_ngram_filter).  n <= 1 turns it off (the reference bans nothing with n == 1 either).  The history,
+        [max_batch, capacity] int32, is allocated on first use (and again for a new capacity) and kept in the decode state; the
+        rows that begin_decode / begin_ragged start begin with an empty one, and retire_rows carries it along.  generate_frames
+        refuses a call that would grow a history past `capacity`.  generate_frame (the reference-shaped single frame) is never
+        filtered."""
+        self._need()
+        st = self._st
+        n, fallback, capacity = int(n), int(fallback), int(capacity)
+        if n > 16:
+            raise ValueError(f"no_repeat_ngram_size must be <= 16, got {n}")
+        if n <= 1:
+            check(lib.ua2_stage3_set_ngram(self._h, 0, 0, None, None, 0), "ua2_stage3_set_ngram")
+            self._ngram = None
+            return
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        if "ngram_hist" not in st or st["ngram_hist"].shape[1] != capacity:
+            i32 = dict(dtype=torch.int32, device=st["device"])
+            st["ngram_hist"] = torch.zeros(st["B"], capacity, **i32)
+            st["ngram_len"] = torch.zeros(st["B"], **i32)          # a new history: every row starts empty
+            self._ngram_hi = 0
+        check(lib.ua2_stage3_set_ngram(self._h, n, fallback, st["ngram_hist"].data_ptr(), st["ngram_len"].data_ptr(), capacity),
+              "ua2_stage3_set_ngram")
+        self._ngram = (n, fallback, capacity)
+
     def set_order_free_rows(self, rows: int = 0):
         """bf16 plans: trunk launches of >= `rows` rows (batched prefill, decode frames of that many sequences) run on the
         order-free 256-row-tile GEMM (include/ua2hip.h ua2_stage3_set_order_free_rows; 0 = off, the default: every row keeps
@@ -296,7 +330,8 @@ class Model_stage3(nn.Module):
         (n_frames, batch, 9) int32 (device).
         skip_text_head (modes 0 and 2): lm_head and the text sample are skipped — the audio loops feed the text id back under
         a zero mask and never read it (tts_task.py:259,274-277), so the audio columns are bit-identical with and without it;
-        the text column of the log then holds -1.  The reference-shaped generate_frame always computes it."""
+        the text column of the log then holds -1.  The reference-shaped generate_frame always computes it.
+        Mode 1 under set_ngram(n >= 2): the log's text column and the fed-back text id are the n-gram-filtered ids."""
         if skip_text_head:
             if mode not in (0, 2):
                 raise ValueError("skip_text_head applies to the audio-feedback modes (0, 2)")
@@ -305,6 +340,10 @@ class Model_stage3(nn.Module):
             raise ValueError("skip_audio_experts applies to the text-feedback mode (1)")
         self._need()
         st = self._st
+        if mode == 1 and self._ngram is not None:
+            # every text frame appends one id to each row's n-gram history: never filter against a truncated one
+            if self._ngram_hi + n_frames > self._ngram[2]:
+                raise ValueError(f"n-gram history full: {self._ngram_hi} + {n_frames} frames > capacity {self._ngram[2]} (set_ngram)")
         start = int(st["counters"][0].item())
         if start + n_frames > st["log_frames"]:
             raise ValueError("frame log too small: raise log_frames in setup_caches")
@@ -316,6 +355,8 @@ class Model_stage3(nn.Module):
             self._pos_hi = int(st["row_pos"][:batch].max().item())
             self._check_positions(self._pos_hi + n_frames - 1)
         self._pos_hi += n_frames
+        if mode == 1 and self._ngram is not None:
+            self._ngram_hi += n_frames
         s = ops.stream()
         for i in range(n_frames):
             # skip_audio_experts (text-only continuations: asr_task.py:666-682 and twins): from the session's SECOND text-feedback frame on
@@ -367,8 +408,9 @@ class Model_stage3(nn.Module):
         assert len(set(keep)) == len(keep) and all(0 <= k < batch for k in keep)
         gone = [r for r in range(batch) if r not in set(keep)]
         perm = torch.tensor(keep + gone, dtype=torch.long, device=st["device"])
-        for k in ("tokens", "mask", "row_pos", "forbid", "out_tokens"):
-            st[k][:batch] = st[k][:batch][perm]
+        for k in ("tokens", "mask", "row_pos", "forbid", "out_tokens", "ngram_hist", "ngram_len"):
+            if k in st:
+                st[k][:batch] = st[k][:batch][perm]
         for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert):
             pt = g.kv_cache.page_table
             pt[:batch] = pt[:batch][perm]

@@ -13,8 +13,13 @@ Differences, all explicit:
   * Under `torchrun` (WORLD_SIZE > 1) the texts of --text_file are sharded over the ranks, one utterance
     per GPU at a time, and gathered with one RCCL all-gather (uniaudio2_amd/parallel.py); rank 0 writes.
   * --topk > 1 samples on the device with a counter-based generator seeded by --seed: reproducible, same
-    distribution as the reference's sample_topk, but not torch's random stream.  --decode_type
-    ngram/beamsearch raise NotImplementedError (the reference's beam search is dead code).
+    distribution as the reference's sample_topk, but not torch's random stream.
+  * --decode_type ngram (ASR / Yue_ASR: generate_asr_with_ngram_sampling, greedy, n = 3, as the reference's :310-322) runs the
+    n-gram filter on the device; its prefill is generate_asr's (the reference's trains-mode prefill leaves the experts' caches
+    empty, evaluation/asr_task.py).  lyric_recognition + ngram raises ValueError (the reference's lyric Generator has no such
+    method: AttributeError); the caption / understanding / s2t tasks ignore the flag, as the reference does.  --decode_type
+    beamsearch raises NotImplementedError (the reference's beam search is dead code); so does any non-greedy
+    --decode_type for the generation tasks.
   * Encoding raw audio (--audio / --audio_dir) needs the codec's frozen SSL encoders (Whisper, WavLM, BEST-RQ), which are
     out of scope: it raises with that message; pre-tokenised `--reason_pt/--semantic_pt/--token_dir`
     inputs work.  Stage 2 (tokens -> wav: RVQ look-ups, flow-matching DiT, SQ-Codec) runs on the device; wav files are
@@ -158,9 +163,19 @@ def _check_decode(args):
         raise NotImplementedError("--decode_type ngram/beamsearch are not on the device path (greedy only this round)")
 
 
+def _check_understanding_decode(args, task):
+    """multi_task_inference.py:310-322 of the reference: ngram reaches generate_asr_with_ngram_sampling for the ASR tasks and is
+    ignored by the others; its lyric Generator lacks the method.  Beam search is dead code there."""
+    if args.decode_type == "beamsearch":
+        raise NotImplementedError("--decode_type beamsearch is not on the device path (the reference's beam search is dead code)")
+    if args.decode_type == "ngram" and task == "lyric_recognition":
+        raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "
+                         "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")
+
+
 def run_understanding(args):
     task = args.task.strip().lower()
-    _check_decode(args)
+    _check_understanding_decode(args, task)
     if (args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)):
         raise NotImplementedError("encoding raw audio needs the codec's frozen SSL encoders (out of scope, SURVEY.md §8f); "
                                   "pass --reason_pt + --semantic_pt or --token_dir")
@@ -209,6 +224,10 @@ def run_understanding(args):
             elif task in ("audio_caption", "music_caption"):                                       # :329-342
                 text_out = generator.generate_audio_caption(task_prompt, task_name=task, reason_token=reason, semantic_token=semantic,
                                                             temperature=args.temperature, topk=1, cfg_scale=args.cfg_scale)
+            elif args.decode_type == "ngram":                                                       # :316-321: asr, yue_asr
+                text_out = generator.generate_asr_with_ngram_sampling(task_prompt, task_name=task, reason_token=reason,
+                                                                      semantic_token=semantic, temperature=args.temperature, topk=1,
+                                                                      cfg_scale=args.cfg_scale)
             else:   # asr, yue_asr, lyric_recognition (:310-327: the reference calls generate_asr on all three; its lyric module only
                     # defines generate_lyric_asr, so the call fails there — here the lyric Generator has both names)
                 text_out = generator.generate_asr(task_prompt, task_name=task, reason_token=reason, semantic_token=semantic,
