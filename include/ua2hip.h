@@ -317,6 +317,13 @@ int ua2_rmsnorm_blend(int32_t M, int32_t C, const float* x, const float* w, floa
                       const float* other, const uint8_t* mask, int32_t mask_ld, int32_t col_a, int32_t col_b,
                       float* out1, float* out2, const ua2_handover* ho /* optional: hand-over of out1 */, void* stream);
 
+/* The all-NaN rule of the sampling tails (ua2_argmax_embed, ua2_sample_topk, and the executor's internal arg-max + table gather):
+ * a NaN score never wins a comparison, so a row whose partial maxima (arg-max) or race scores (top-k: a NaN row, or a row of -inf)
+ * are all NaN has no winner.  Such a row takes its LOWEST CANDIDATE id — the lowest part_idx entry of the row for the arg-max
+ * forms, the first admitted column (forbid[m], or 0) for ua2_sample_topk — and every tail clamps the id it chose into [0, limit)
+ * before it is written to out_tokens and before any gather: limit = V for ua2_sample_topk, the vocabulary for the executor's
+ * launches, 16 * n_part (the most ids the partials can describe) for the exported ua2_argmax_embed.  A NaN partial next to
+ * finite ones simply loses.  The token written and the row gathered are always the same in-range value. */
 /* Greedy sampling tail (model_new.py:146-187 with topk=1; lowest index wins ties) fused with
  * the next-step embedding gather (model_new.py:640,662-663):
  *   tok = argmax over the per-tile partials; out_tokens[m*out_ld + out_col] = tok;

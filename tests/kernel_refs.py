@@ -1,0 +1,223 @@
+"""Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py and tests/test_gpu_rowwise.py.
+
+Every helper takes `dt`: torch.float64 is the reference a kernel is compared with; torch.float32 evaluates the SAME formula in
+plain fp32 on the host, whose error against the float64 result (`E_ref`) sizes the bar of a tolerance test:
+bar = max(4 * E_ref, 8 * 2^-24 * scale) (two legal fp32 summation orders differ by about twice the single-order error, and the
+kernels' exp / tanh / rsqrt are good to 1-2 ulp; the floor because E_ref can be exactly 0 on short rows).
+tests/test_kernel_refs.py pins each helper to the torch library function it restates (CPU, float64, rtol 1e-12).
+All helpers are vectorised over rows and heads."""
+import math
+
+import numpy as np
+import torch
+
+PAGE = 64
+F64 = torch.float64
+
+
+def bar(e_ref, scale=1.0):
+    return max(4.0 * float(e_ref), 8.0 * 2.0 ** -24 * float(scale))
+
+
+# ---- paged caches -----------------------------------------------------------------------------------------------------------
+
+def page_slot(p, ring_pages):
+    lp = p // PAGE
+    return lp % ring_pages if ring_pages > 0 else lp
+
+
+class PagedCache:
+    """Paged K / V cache on the host: pools [pages, n_kv, 64, hs] of `dtype`, a scattered page table [B, max_pages].
+    ring_pages > 0 (a power of two): position p lives in table column (p // 64) % ring_pages, and only the positions a sequence
+    of length L still holds (those whose page was not overwritten by a later one) are materialised.  K[b], V[b]: the values of
+    every position as drawn (fp32); stored(b, p) returns what the pool holds at the slot of position p, widened to float64."""
+
+    def __init__(self, lens, n_kv, hs, dtype, seed=0, ring_pages=0, K=None, V=None, fill=0.0, extra_pages=0):
+        g = torch.Generator().manual_seed(seed)
+        self.lens, self.n_kv, self.hs, self.dtype, self.ring_pages = list(lens), n_kv, hs, dtype, ring_pages
+        B = len(lens)
+        self.max_pages = ring_pages if ring_pages > 0 else (max(lens) + PAGE - 1) // PAGE
+        n_pages = B * self.max_pages + extra_pages
+        self.table = torch.randperm(n_pages, generator=g)[:B * self.max_pages].to(torch.int32).view(B, self.max_pages)
+        self.k = torch.full((n_pages, n_kv, PAGE, hs), fill, dtype=dtype)
+        self.v = torch.full((n_pages, n_kv, PAGE, hs), fill, dtype=dtype)
+        self.K = K if K is not None else [torch.randn(L, n_kv, hs, generator=g) for L in lens]
+        self.V = V if V is not None else [torch.randn(L, n_kv, hs, generator=g) for L in lens]
+        for b, L in enumerate(lens):
+            ps = self.held(b)
+            pg = self.table[b, page_slot(ps, ring_pages)].long()
+            self.k[pg, :, ps % PAGE] = self.K[b][ps].to(dtype)
+            self.v[pg, :, ps % PAGE] = self.V[b][ps].to(dtype)
+        assert int(self.table.min()) >= 0 and int(self.table.max()) < n_pages
+
+    def held(self, b):
+        """Positions of sequence b the pool holds."""
+        L = self.lens[b]
+        first = 0 if self.ring_pages == 0 else max(0, ((L - 1) // PAGE - self.ring_pages + 1) * PAGE)
+        return torch.arange(first, L)
+
+    def stored(self, b, ps):
+        ps = torch.as_tensor(ps)
+        pg = self.table[b, page_slot(ps, self.ring_pages)].long()
+        return self.k[pg, :, ps % PAGE].to(F64), self.v[pg, :, ps % PAGE].to(F64)
+
+    def stored_seq(self, b):
+        """(K, V) [L, n_kv, hs] float64 as stored; positions the ring no longer holds are NaN (a reference must not touch them)."""
+        L = self.lens[b]
+        K = torch.full((L, self.n_kv, self.hs), float("nan"), dtype=F64)
+        V = K.clone()
+        ps = self.held(b)
+        K[ps], V[ps] = self.stored(b, ps)
+        return K, V
+
+
+def attn_ref(q, K, V, pos, seq, n_head, n_kv, window=0, dt=F64):
+    """softmax(q k^T / sqrt(hs)) v over keys max(0, pos + 1 - window) .. pos of the row's sequence.  q [R, n_head * hs];
+    K, V: per sequence [L, n_kv, hs], the values actually stored (already rounded to the cache dtype); pos, seq [R] ints."""
+    q = torch.as_tensor(q).to(dt)
+    pos, seq = np.asarray(pos, dtype=np.int64), np.asarray(seq, dtype=np.int64)
+    R, G = q.shape[0], n_head // n_kv
+    hs = q.shape[1] // n_head
+    out = torch.zeros(R, n_head * hs, dtype=dt)
+    for b in np.unique(seq):
+        rows = np.nonzero(seq == b)[0]
+        p = torch.from_numpy(pos[rows])
+        n = int(p.max()) + 1
+        lo = torch.clamp(p + 1 - window, min=0) if window > 0 else torch.zeros_like(p)
+        first = int(lo.min())
+        Kb, Vb = K[b][first:n].to(dt), V[b][first:n].to(dt)                        # [n', n_kv, hs]
+        qb = q[rows].view(len(rows), n_kv, G, hs)
+        s = torch.einsum("rkgd,lkd->rkgl", qb, Kb) / math.sqrt(hs)
+        key = torch.arange(first, n)
+        vis = (key[None, :] <= p[:, None]) & (key[None, :] >= lo[:, None])         # [r, n']
+        s = s.masked_fill(~vis[:, None, None, :], float("-inf"))
+        w = torch.softmax(s, dim=-1)
+        Vz = torch.where(torch.isnan(Vb), torch.zeros_like(Vb), Vb)                # slots no row may see carry weight 0
+        assert not bool(torch.isnan(torch.where(vis[:, None, None, :], s, torch.zeros_like(s))).any()), "a visible key is not stored"
+        out[rows] = torch.einsum("rkgl,lkd->rkgd", w, Vz).reshape(len(rows), n_head * hs)
+    return out
+
+
+# ---- glue kernels -----------------------------------------------------------------------------------------------------------
+
+def rmsnorm_blend_ref(x, w, eps, other=None, mask=None, col_a=-1, col_b=-1, dt=F64):
+    """n = x * rsqrt(mean(x^2) + eps) * w; out1 = n * fa + other * fb (fa = mask[:, col_a] or 1; fb = mask[:, col_b] with `other`)."""
+    x, w = x.to(dt), w.to(dt)
+    n = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps) * w
+    out1 = n * mask[:, col_a:col_a + 1].to(dt) if col_a >= 0 else n.clone()
+    if other is not None:
+        out1 = out1 + other.to(dt) * mask[:, col_b:col_b + 1].to(dt)
+    return out1, n
+
+
+def layernorm_ref(x, w=None, b=None, eps=1e-5, dt=F64):
+    x = x.to(dt)
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    y = d * torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    if w is not None:
+        y = y * w.to(dt)
+    if b is not None:
+        y = y + b.to(dt)
+    return y
+
+
+def embed_frame_ref(tokens, mask, audio_emb, wte, va, dt=F64):
+    """audio_sum = sum_i mask[:, i] * audio_emb[tok[:, i] + i * va] added in the order i = 0 .. n_cb - 1; text = wte[tok[:, n_cb]]."""
+    tokens = tokens.long()
+    ncb = tokens.shape[1] - 1
+    s = torch.zeros(tokens.shape[0], audio_emb.shape[1], dtype=dt)
+    for i in range(ncb):
+        e = audio_emb[tokens[:, i] + i * va].to(dt)
+        s = s + torch.where(mask[:, i:i + 1] != 0, e, torch.zeros_like(e))
+    return s, wte[tokens[:, ncb]].to(dt)
+
+
+def cfg_mix_ref(l0, l1, scale, dt=F64):
+    """guided = l1 + (l0 - l1) * scale, every operation rounded once in `dt`."""
+    l0, l1 = l0.to(dt), l1.to(dt)
+    return l1 + (l0 - l1) * torch.tensor(scale, dtype=torch.float32).to(dt)
+
+
+def argmax_partials(row, forbid=0):
+    """Per-16-column (max, arg-max) of a 1-D fp32 row: lowest index on ties, columns < forbid excluded, a group without an
+    admitted column = (-inf, its first column)."""
+    row = np.asarray(row, dtype=np.float32)
+    V = row.shape[0]
+    nb = (V + 15) // 16
+    pad = np.full(nb * 16, -np.inf, dtype=np.float32)
+    pad[:V] = row
+    pad[:min(forbid, V)] = -np.inf
+    g = pad.reshape(nb, 16)
+    idx = g.argmax(1)                                   # numpy: first occurrence
+    return g.max(1), (idx + 16 * np.arange(nb)).astype(np.int32)
+
+
+def time_film_ref(params, x, batch_mask, rows_per_batch, gamma_scale, dt=F64):
+    C = x.shape[1]
+    p, x = params.to(dt), x.to(dt)
+    gamma = 1.0 + gamma_scale * torch.tanh(p[:, :C])
+    beta = p[:, C:]
+    out = gamma * x + beta
+    if batch_mask is not None:
+        masked = batch_mask.bool()[torch.arange(x.shape[0]) // rows_per_batch]
+        out = torch.where(masked[:, None], x, out)
+    return out
+
+
+def ew_act_ref(x, act, dt=F64):
+    x = x.to(dt)
+    return {1: lambda v: v / (1.0 + torch.exp(-v)), 2: lambda v: 1.0 / (1.0 + torch.exp(-v)), 3: torch.tanh}[act](x)
+
+
+def rotate_half(x):
+    x1, x2 = x[..., :x.shape[-1] // 2], x[..., x.shape[-1] // 2:]
+    return torch.cat((-x2, x1), dim=-1)
+
+
+def qknorm_rope_ref(qkv, pos, n_head, hs, qw=None, qb=None, kw=None, kb=None, eps=1e-5, cos=None, sin=None, rot_dim=0, dt=F64):
+    """qkv [R, 3 * n_head * hs] = (q | k | v): LayerNorm over the head dim with affine on q and k (when weights are given), then
+    rotate-half rotary on the first rot_dim dims with freqs = cat(f, f) (cos / sin [max_pos, rot_dim / 2]) -> q, k, v [R, n_head, hs]."""
+    R = qkv.shape[0]
+    q, k, v = (t.reshape(R, n_head, hs) for t in qkv.to(dt).chunk(3, dim=-1))
+    if qw is not None:
+        q = layernorm_ref(q, qw, qb, eps, dt)
+        k = layernorm_ref(k, kw, kb, eps, dt)
+    if rot_dim > 0:
+        p = torch.as_tensor(pos).long()
+        c = torch.cat((cos[p], cos[p]), -1).to(dt)[:, None, :]
+        s = torch.cat((sin[p], sin[p]), -1).to(dt)[:, None, :]
+
+        def rot(t):
+            a, rest = t[..., :rot_dim], t[..., rot_dim:]
+            return torch.cat((a * c + rotate_half(a) * s, rest), -1)
+        q, k = rot(q), rot(k)
+    return q, k, v
+
+
+def dwconv_ref(x, w, bias=None, *, stride=1, dilation=1, pad_left=0, Tout=None, transposed=False, dt=F64):
+    """Depthwise conv: y[b,c,t] = bias[c] + sum_j w[c,j] x[b,c, t*stride + j*dilation - pad_left] (zero outside);
+    transposed: y[b,c,t] = bias[c] + sum_{ti*stride + j == t + pad_left} w[c,j] x[b,c,ti].  Written index by index over the taps
+    (not through F.conv1d, which tests/test_kernel_refs.py compares it with)."""
+    x, w = x.to(dt), w.to(dt)
+    B, C, Tin = x.shape
+    K = w.shape[1]
+    y = torch.zeros(B, C, Tout, dtype=dt)
+    t = torch.arange(Tout)
+    for j in range(K):
+        if not transposed:
+            ti = t * stride + j * dilation - pad_left
+            ok = (ti >= 0) & (ti < Tin)
+        else:
+            r = t + pad_left - j
+            ok = (r >= 0) & (r % stride == 0) & (r // stride < Tin)
+            ti = r // stride
+        y[:, :, t[ok]] += w[None, :, j:j + 1] * x[:, :, ti[ok]]
+    if bias is not None:
+        y = y + bias.to(dt)[None, :, None]
+    return y
+
+
+def bf16_round(x):
+    """RNE to bf16 of an fp32 tensor, as fp32."""
+    return x.float().to(torch.bfloat16).float()

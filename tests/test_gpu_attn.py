@@ -1,6 +1,7 @@
 """GPU parity of the MFMA flash form of ua2_attn (prefill, dense encoders / DiT): against a torch fp32 softmax(q k^T) v on
 the bf16 cache contents, against the row-by-row kernel (same arithmetic contract), and bit-for-bit invariance of a row's
-result under re-grouping of the query rows."""
+result under re-grouping of the query rows.
+The row-by-row (decode) form on its own — fp32 caches, windows, ring caches, every group size — is in tests/test_gpu_attn_decode.py."""
 import numpy as np
 import pytest
 import torch

@@ -141,6 +141,41 @@ __device__ __forceinline__ int ua2_page_slot(const ua2_kv_geom& kv, int pos) {
   return kv.ring_pages > 0 ? (lp & (kv.ring_pages - 1)) : lp;   // ring_pages is a power of two (checked by the launchers): no integer division per key
 }
 
+// ---- final token of a sampling tail (include/ua2hip.h, "all-NaN rule"; DESIGN.md, sampling tail) -------------------------------
+// The three tails (argmax_embed_kernel, argmax_gather_kernel, sample_topk_kernel) pick the row's token under "larger score, then
+// lower id".  A thread enters with its own best (bv, bi), bi = UA2_TOK_NONE while nothing has won: a NaN score never wins a
+// comparison, so a row whose scores are all NaN ends the reduction without a winner.  Such a row takes its LOWEST CANDIDATE id
+// (lowest(): the lowest id this thread was offered, UA2_TOK_NONE for none; evaluated only on that path), and whatever was
+// chosen is clamped into [0, limit) — limit = vocabulary / table rows as the launcher knows them — so that the id written to
+// out_tokens and the row every gather reads are the same in-range value.  Order of the reduction: 64-lane xor butterflies, then
+// the wave results in wave order (red_v / red_i: one slot per wave).  Every thread of the workgroup must call; all return the token.
+#define UA2_TOK_NONE 0x7fffffff
+template <class Lowest>
+__device__ __forceinline__ int ua2_row_token(float bv, int bi, int limit, float* red_v, int* red_i, int* tok_s, Lowest lowest) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = bv; red_i[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
+      if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
+    *tok_s = bi;
+  }
+  __syncthreads();
+  int t = *tok_s;
+  if (t == UA2_TOK_NONE) {            // nobody won (the same value in every thread): lowest candidate id of the row
+    __syncthreads();                  // every thread has read tok_s before it changes
+    atomicMin(tok_s, lowest());
+    __syncthreads();
+    t = *tok_s;
+  }
+  return min(max(t, 0), limit - 1);
+}
+
 static inline int ua2_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Kernels that use more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised.  The
@@ -201,9 +236,13 @@ struct ua2_qkv_gather {
   int32_t qn, esz, pos;    // esz: bytes per cache element; pos: position of the step the rows are written for
   ua2_kv_geom kv;          // destination caches (row m = sequence m)
 };
-int ua2_argmax_gather(int32_t M, int32_t n_part, const float* part_max, const int32_t* part_idx, int32_t* out_tokens, int32_t out_ld,
+// `limit`: ids the table holds per row_off block (the vocabulary of the head); the token is clamped into [0, limit) (ua2_row_token)
+int ua2_argmax_gather(int32_t M, int32_t n_part, int32_t limit, const float* part_max, const int32_t* part_idx, int32_t* out_tokens, int32_t out_ld,
                       int32_t out_col, const float* tab_y, const void* tab_h, const float* tab_ssq, int64_t row_off, int32_t Cd, float* next_x,
                       const ua2_handover* ho, const ua2_qkv_gather* qg, hipStream_t s);
+// ua2_argmax_embed with the vocabulary known (the exported form only knows limit <= 16 * n_part)
+int ua2_argmax_embed_launch(int dtype, int32_t M, int32_t n_part, int32_t limit, const float* part_max, const int32_t* part_idx, int32_t* out_tokens,
+                            int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, hipStream_t s);
 int ua2_kv_rows_extract(const void* k_pool, const void* v_pool, const int32_t* pos, int n, int n_kv, int hs, int esz, void* out_k, void* out_v, hipStream_t s);
 // decode-regime specialisation; returns 1 when the problem is outside its regime
 int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s);

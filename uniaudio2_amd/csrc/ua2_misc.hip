@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void rmsnorm_blend_kernel(int C, const float* 
 
 // model_new.py:146-187 at topk=1 (masked arg-max; lowest index on ties) + :640,662-663 (_embed_audio)
 template <int DT>
-__global__ void argmax_embed_kernel(int n_part, const float* __restrict__ pmax, const int32_t* __restrict__ pidx,
+__global__ void argmax_embed_kernel(int n_part, int limit, const float* __restrict__ pmax, const int32_t* __restrict__ pidx,
                                     int32_t* __restrict__ out_tokens, int out_ld, int out_col,
                                     const void* __restrict__ emb, int emb_off, int C, float* __restrict__ next_h) {
   __shared__ float sv[4];
@@ -220,29 +220,20 @@ __global__ void argmax_embed_kernel(int n_part, const float* __restrict__ pmax, 
   __shared__ int tok_s;
   const int m = blockIdx.x;
   float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = UA2_TOK_NONE;
   for (int p = threadIdx.x; p < n_part; p += blockDim.x) {
     const float v = pmax[(size_t)m * n_part + p];
     const int i = pidx[(size_t)m * n_part + p];
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-    tok_s = bi;
-    out_tokens[(size_t)m * out_ld + out_col] = bi;
-  }
-  __syncthreads();
+  const int tok = ua2_row_token(bv, bi, limit, sv, si, &tok_s, [&] {
+    int lo = UA2_TOK_NONE;
+    for (int p = threadIdx.x; p < n_part; p += blockDim.x) lo = min(lo, pidx[(size_t)m * n_part + p]);
+    return lo;
+  });
+  if (threadIdx.x == 0) out_tokens[(size_t)m * out_ld + out_col] = tok;
   if (emb) {
-    const size_t row = (size_t)tok_s + (size_t)emb_off;
+    const size_t row = (size_t)tok + (size_t)emb_off;
     for (int c = threadIdx.x; c < C; c += blockDim.x) next_h[(size_t)m * C + c] = load_elem<DT>(emb, row * C + c);
   }
 }
@@ -254,7 +245,7 @@ __global__ void argmax_embed_kernel(int n_part, const float* __restrict__ pmax, 
 // sums of squares), are functions of the sampled id alone.  The executor builds them once per plan WITH THE SAME LAUNCHES the frame
 // would run (a row's bits do not depend on the rows beside it: the row-invariance contract), and the frame gathers: y -> next_x [M, Cd];
 // hand-over rows -> ho.h (row-major) or ho.packed (fragment order), ho.ssq.  Seven 5.9-us GEMVs per B = 1 frame disappear.
-__global__ __launch_bounds__(256) void argmax_gather_kernel(int n_part, const float* __restrict__ pmax, const int32_t* __restrict__ pidx,
+__global__ __launch_bounds__(256) void argmax_gather_kernel(int n_part, int limit, const float* __restrict__ pmax, const int32_t* __restrict__ pidx,
                                                             int32_t* __restrict__ out_tokens, int out_ld, int out_col,
                                                             const float* __restrict__ tab_y, const unsigned short* __restrict__ tab_h,
                                                             const float* __restrict__ tab_ssq, long long row_off, int Cd,
@@ -264,28 +255,19 @@ __global__ __launch_bounds__(256) void argmax_gather_kernel(int n_part, const fl
   __shared__ int tok_s;
   const int m = blockIdx.x;
   float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = UA2_TOK_NONE;
   for (int p = threadIdx.x; p < n_part; p += blockDim.x) {
     const float v = pmax[(size_t)m * n_part + p];
     const int i = pidx[(size_t)m * n_part + p];
     if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-    tok_s = bi;
-    out_tokens[(size_t)m * out_ld + out_col] = bi;
-  }
-  __syncthreads();
-  const size_t row = (size_t)((long long)tok_s + row_off);
+  const int tok = ua2_row_token(bv, bi, limit, sv, si, &tok_s, [&] {
+    int lo = UA2_TOK_NONE;
+    for (int p = threadIdx.x; p < n_part; p += blockDim.x) lo = min(lo, pidx[(size_t)m * n_part + p]);
+    return lo;
+  });
+  if (threadIdx.x == 0) out_tokens[(size_t)m * out_ld + out_col] = tok;
+  const size_t row = (size_t)((long long)tok + row_off);
   const float4* y4 = reinterpret_cast<const float4*>(tab_y + row * Cd);
   float4* x4 = reinterpret_cast<float4*>(next_x + (size_t)m * Cd);
   for (int c = threadIdx.x; c < Cd / 4; c += blockDim.x) x4[c] = y4[c];
@@ -327,6 +309,9 @@ __global__ __launch_bounds__(256) void argmax_gather_kernel(int n_part, const fl
 __global__ __launch_bounds__(256) void cfg_mix_kernel(float* __restrict__ logits, int ld, int V, float scale,
                                                       const int32_t* __restrict__ forbid, float* __restrict__ pmax,
                                                       int32_t* __restrict__ pidx) {
+  // hipcc contracts multiply-adds by default and __fmul_rn / __fadd_rn do not prevent it (ua2_codec_join.hip): the mix came out as
+  // fma(l0 - l1, scale, l1), 1 ulp off what torch evaluates.  Plain operators under this pragma give the three roundings.
+#pragma clang fp contract(off)
   const int n = blockIdx.x * 256 + threadIdx.x;
   const int nb = (V + 15) / 16;
   const int pair = blockIdx.y;                             // rows 2 pair, 2 pair + 1
@@ -337,7 +322,7 @@ __global__ __launch_bounds__(256) void cfg_mix_kernel(float* __restrict__ logits
   float g = -INFINITY;
   if (n < V) {
     const float l0 = logits[n], l1 = logits[ld + n];
-    g = __fadd_rn(l1, __fmul_rn(__fsub_rn(l0, l1), scale));
+    g = l1 + (l0 - l1) * scale;
     logits[n] = g;
     logits[ld + n] = g;
   }
@@ -403,22 +388,29 @@ extern "C" int ua2_rmsnorm_blend(int32_t M, int32_t C, const float* x, const flo
   return 0;
 }
 
-extern "C" int ua2_argmax_embed(int dtype, int32_t M, int32_t n_part, const float* part_max, const int32_t* part_idx,
-                                int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb,
-                                int32_t emb_row_offset, int32_t C, float* next_h, void* stream) {
-  UA2_CHECK(M > 0 && n_part > 0 && part_max && part_idx && out_tokens, "ua2_argmax_embed: bad arguments");
+int ua2_argmax_embed_launch(int dtype, int32_t M, int32_t n_part, int32_t limit, const float* part_max, const int32_t* part_idx, int32_t* out_tokens,
+                            int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, hipStream_t s) {
+  UA2_CHECK(M > 0 && n_part > 0 && limit > 0 && part_max && part_idx && out_tokens, "ua2_argmax_embed: bad arguments");
   UA2_CHECK(!emb || next_h, "ua2_argmax_embed: next_h is NULL");
-  hipStream_t s = (hipStream_t)stream;
   if (dtype == UA2_BF16)
-    hipLaunchKernelGGL((argmax_embed_kernel<UA2_BF16>), dim3(M), dim3(256), 0, s, n_part, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
+    hipLaunchKernelGGL((argmax_embed_kernel<UA2_BF16>), dim3(M), dim3(256), 0, s, n_part, limit, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
   else if (dtype == UA2_F32)
-    hipLaunchKernelGGL((argmax_embed_kernel<UA2_F32>), dim3(M), dim3(256), 0, s, n_part, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
+    hipLaunchKernelGGL((argmax_embed_kernel<UA2_F32>), dim3(M), dim3(256), 0, s, n_part, limit, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
   else {
     ua2_set_error("ua2_argmax_embed: bad dtype %d", dtype);
     return -1;
   }
   UA2_LAUNCH_CHECK();
   return 0;
+}
+
+// the exported form does not carry the vocabulary: the partials are per 16 columns, so ids lie below 16 * n_part
+extern "C" int ua2_argmax_embed(int dtype, int32_t M, int32_t n_part, const float* part_max, const int32_t* part_idx,
+                                int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb,
+                                int32_t emb_row_offset, int32_t C, float* next_h, void* stream) {
+  UA2_CHECK(n_part > 0 && n_part <= (0x7fffffff >> 4), "ua2_argmax_embed: bad arguments");
+  return ua2_argmax_embed_launch(dtype, M, n_part, 16 * n_part, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h,
+                                 (hipStream_t)stream);
 }
 
 // rows of a scratch cache (row r = page r, written at position pos[r] by a q|k|v launch) -> compact table rows [n][n_kv * head_size]
@@ -438,10 +430,10 @@ int ua2_kv_rows_extract(const void* k_pool, const void* v_pool, const int32_t* p
   return 0;
 }
 
-int ua2_argmax_gather(int32_t M, int32_t n_part, const float* part_max, const int32_t* part_idx, int32_t* out_tokens, int32_t out_ld,
+int ua2_argmax_gather(int32_t M, int32_t n_part, int32_t limit, const float* part_max, const int32_t* part_idx, int32_t* out_tokens, int32_t out_ld,
                       int32_t out_col, const float* tab_y, const void* tab_h, const float* tab_ssq, int64_t row_off, int32_t Cd, float* next_x,
                       const ua2_handover* ho, const ua2_qkv_gather* qg, hipStream_t s) {
-  UA2_CHECK(M > 0 && n_part > 0 && part_max && part_idx && out_tokens && tab_y && next_x && Cd % 32 == 0, "ua2_argmax_gather: bad arguments");
+  UA2_CHECK(M > 0 && n_part > 0 && limit > 0 && part_max && part_idx && out_tokens && tab_y && next_x && Cd % 32 == 0, "ua2_argmax_gather: bad arguments");
   ua2_qkv_gather q{};
   if (qg) {
     UA2_CHECK(qg->tab_q && qg->tab_k && qg->tab_v && qg->q_out && qg->qn % 4 == 0 && (qg->esz == 2 || qg->esz == 4) && qg->kv.k_pool && qg->kv.v_pool &&
@@ -454,7 +446,7 @@ int ua2_argmax_gather(int32_t M, int32_t n_part, const float* part_max, const in
     UA2_CHECK(tab_h && tab_ssq && ho->ssq && (ho->h || ho->packed) && (!ho->h || ho->ldh % 4 == 0), "ua2_argmax_gather: hand-over tables / outputs missing");
     h = *ho;
   }
-  hipLaunchKernelGGL(argmax_gather_kernel, dim3(M), dim3(256), 0, s, n_part, part_max, part_idx, out_tokens, out_ld, out_col, tab_y,
+  hipLaunchKernelGGL(argmax_gather_kernel, dim3(M), dim3(256), 0, s, n_part, limit, part_max, part_idx, out_tokens, out_ld, out_col, tab_y,
                      reinterpret_cast<const unsigned short*>(tab_h), tab_ssq, (long long)row_off, Cd, next_x, h, q);
   UA2_LAUNCH_CHECK();
   return 0;

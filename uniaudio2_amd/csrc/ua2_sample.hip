@@ -14,8 +14,9 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned key_of(float f) {   // monotone: larger float -> larger key
-  const unsigned u = __float_as_uint(f);
+__device__ __forceinline__ unsigned key_of(float f) {   // monotone: larger float -> larger key; -0.0 and +0.0 share one key
+  unsigned u = __float_as_uint(f);                       // (`logits < topk_value` keeps -0.0 at a +0.0 threshold: they compare equal)
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restri
   __shared__ int tok_s;
   const int m = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const float* row = logits + (size_t)m * ld;
-  const int fb = forbid ? forbid[m] : 0;
+  const int fb = forbid ? max(forbid[m], 0) : 0;
   // ---- exact k-th largest key among columns [fb, V) -------------------------------------------
   if (tid == 0) { sel_prefix = 0u; sel_remaining = (unsigned)topk; }
   for (int pass = 3; pass >= 0; --pass) {
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restri
   // device-resident part of the key (ua2_stage3_set_sampling writes it): added to the by-value seed
   seed += (unsigned long long)(unsigned)counter[1] | ((unsigned long long)(unsigned)counter[2] << 32);
   float bv = -INFINITY;
-  int bi = 0x7fffffff;
+  int bi = UA2_TOK_NONE;
   for (int c = fb + tid; c < V; c += nt) {
     const float l = row[c] / temperature;
     if (key_of(l) < kth) continue;               // removed: strictly below the k-th value
@@ -96,23 +97,11 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restri
     const float score = expf(l - mx) / q;                                    // probs / q up to the softmax constant
     if (score > bv || (score == bv && c < bi)) { bv = score; bi = c; }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if ((tid & 63) == 0) { red_v[tid >> 6] = bv; red_i[tid >> 6] = bi; }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < (nt >> 6); ++w)
-      if (red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi)) { bv = red_v[w]; bi = red_i[w]; }
-    tok_s = bi;
-    out_tokens[(size_t)m * out_ld + out_col] = bi;
-  }
-  __syncthreads();
+  // every kept column scored NaN (a NaN or all -inf row): the lowest column the row may sample (ua2_row_token)
+  const int tok = ua2_row_token(bv, bi, V, red_v, red_i, &tok_s, [&] { return (tid == 0 && fb < V) ? fb : UA2_TOK_NONE; });
+  if (tid == 0) out_tokens[(size_t)m * out_ld + out_col] = tok;
   if (emb) {
-    const size_t er = (size_t)tok_s + (size_t)emb_off;
+    const size_t er = (size_t)tok + (size_t)emb_off;
     for (int c = tid; c < C; c += nt) next_h[(size_t)m * C + c] = load_elem<DT>(emb, er * C + c);
   }
 }

@@ -605,7 +605,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     if (cfg)
       if (int rc = ua2_cfg_mix(h->text_logits, d.vt, d.vt, h->cfg_scale, nullptr, h->pmax_t, h->pidx_t, R / 2, s)) return rc;
     if (h->topk == 1)
-      return ua2_argmax_embed(d.dtype, R, h->npart_t, h->pmax_t, h->pidx_t, d.out_tokens, w, 0, nullptr, 0, C, nullptr, s);
+      return ua2_argmax_embed_launch(d.dtype, R, h->npart_t, d.vt, h->pmax_t, h->pidx_t, d.out_tokens, w, 0, nullptr, 0, C, nullptr, s);
     // model_new.py:623 sample_topk(text_logits, topk, temperature)
     return ua2_sample_topk(d.dtype, R, h->text_logits, d.vt, d.vt, std::min(h->topk, d.vt), h->temperature, nullptr, 0, d.counters + 1, 0,
                            d.out_tokens, w, 0, nullptr, 0, C, nullptr, key_shift, s);
@@ -650,10 +650,10 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
         qg.kv.n_kv = gd.n_kv; qg.kv.n_head = gd.n_head; qg.kv.head_size = gd.head_size;
       }
       // with layer 0's q | k | v in hand nothing reads the hand-over of the projected row (its only consumer was that launch)
-      if (int rc = ua2_argmax_gather(R, h->npart_a, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, h->ptab_y, h->ptab_h, h->ptab_ssq,
+      if (int rc = ua2_argmax_gather(R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, h->ptab_y, h->ptab_h, h->ptab_ssq,
                                      (int64_t)i * d.va, Cd, h->xd, (scaled && !h->ptab_q) ? &g : nullptr, h->ptab_q ? &qg : nullptr, s)) return rc;
     } else if (h->topk == 1) {
-      if (int rc = ua2_argmax_embed(d.dtype, R, h->npart_a, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, d.audio_emb,
+      if (int rc = ua2_argmax_embed_launch(d.dtype, R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, d.audio_emb,
                                     i * d.va, C, h->curr_h, s)) return rc;
     } else {   // model_new.py:639 audio_sample_topk(ci_logits, topk, temperature, forbid_prefix)
       if (int rc = ua2_sample_topk(d.dtype, R, h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->topk, h->temperature,
