@@ -106,6 +106,26 @@ size_t ua2_packed_elems(int dtype, int64_t N, int64_t K);
 int ua2_pack_linear(const void* src, int src_dtype, int transposed, int64_t N, int64_t K,
                     void* out, int dtype, int rope_head_size, void* stream);
 
+/* ---- fp8 weight-only twins (OCP e4m3fn, never the fnuz encoding) of the decode kernel's weights; UA2_BF16 launches only ----------
+ * Contract, per OUTPUT ROW n of W [N, K]: e[n] = ceil(log2(amax_n / 448)) (an all-zero row takes 0; clamped to [-117, 120] so that 2^e
+ * and every nonzero |W'| are normal numbers), q[n, k] = RNE_e4m3fn(W[n, k] * 2^-e[n]) (|W 2^-e| <= 448: nothing saturates), and the
+ * weight the model computes with is W' = q * 2^e — exactly representable in bf16.  A launch on the fp8 image gives, bit for bit, what
+ * the bf16 launch gives on the packed bf16 form of W' (a power-of-two scale commutes with every fp32 rounding of the sums), so the fp8
+ * image is a second, half-sized copy of a weight that the few-row decode kernel streams, and every many-row kernel keeps reading W'.
+ *
+ * ua2_pack_linear_w8: out_q = the fp8 image [N/16][K/64][64 lanes][16 B] — a lane's 16 bytes are its 8 B-fragment elements of chunk 2j
+ * followed by its 8 of chunk 2j + 1 (a chunk = 32 of K; the lane <-> (column, k) map inside a chunk and the rope_head_size row
+ * permutation are those of the bf16 form above), ua2_packed_bytes_w8 bytes; out_exp = int8 [N padded to 16] exponents in PACKED column
+ * order, padding columns 0; out_bf16 (may be NULL) = the bf16 form above of W', written from the same q and e.  K % 64 != 0 is refused
+ * (the caller then keeps that weight in bf16 alone); ua2_packed_bytes_w8 returns 0 for it. */
+typedef struct {
+  const void* q;         /* fp8 image */
+  const int8_t* exp;     /* exponents, packed column order */
+} ua2_w8_ref;
+size_t ua2_packed_bytes_w8(int64_t N, int64_t K);
+int ua2_pack_linear_w8(const void* src, int src_dtype, int transposed, int64_t N, int64_t K, void* out_q, int8_t* out_exp,
+                       void* out_bf16, int rope_head_size, void* stream);
+
 /* Geometry of the paged KV cache shared by the QKV epilogue and the attention kernel.
  * Pool layout (per layer): [n_pages][n_kv][UA2_PAGE][head_size] of `dtype`, K and V separate.
  * page_table[seq*max_pages + p] = page id holding positions [p*UA2_PAGE, (p+1)*UA2_PAGE). */
@@ -224,6 +244,12 @@ typedef struct ua2_linear_args {
 } ua2_linear_args;
 
 int ua2_linear(const ua2_linear_args* a, void* stream);
+/* The same launch with the weight(s) streamed from their fp8 twins (w1: the second matrix of a SWIGLU launch, else NULL); a->w0 / a->w1
+ * still carry the bf16 forms of W'.  Served: UA2_BF16, K % 64 == 0, no more rows than the launchers give the decode kernel (5 by default; UA2_GEMV_MAX_ROWS), no x_packed,
+ * the (prologue, epilogue) pairs of the decode frame — NORM or SCALED with QKV_ROPE / SWIGLU / STORE, CAST with RESIDUAL / STORE,
+ * LOCAL_ATTN with RESIDUAL.  Anything else is an error (never a silent launch on the bf16 form).  Same grid, waves, chunk ranges and
+ * summation order as the bf16 launch of that (N, K): bit-identical outputs.  Counted as "gemv_w8" by ua2_debug_kernel_launches. */
+int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream);
 /* [v9] 1 when a launch with these arguments (sum_order = UA2_SUM_ORDER_FREE) will run on the order-free kernel (csrc/ua2_gemm2.hip) as it
  * stands — shape, alignment, the tile-count rule, scratch for K slabs; 0 when ua2_linear would take the row-invariant kernels instead.
  * Nothing is launched. */
@@ -240,7 +266,7 @@ size_t ua2_linear_workspace_bytes(int dtype, int64_t M, int64_t K);
 int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
- * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "gemv", "rsplit" ([v10] the range split
+ * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
  * of ua2_skinny.hip: main + combine count once); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
@@ -613,6 +639,20 @@ int ua2_stage3_set_prefill_groups(ua2_stage3* h, const int32_t* group_rows, cons
  * batch (>= rows) then differs by fp32 summation noise in its K/V cache, i.e. by bf16-level noise in later logits — the same
  * class of difference the MFMA prefill attention already has against decode rows.  Below the threshold nothing changes. */
 int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows);
+/* fp8 weights for the plan's few-row launches (UA2_BF16 plans).  table[i] = {w: a packed weight pointer exactly as the desc gave it (a
+ * layer's qkv / proj / fc1 / fc2 / mlp_proj, projection, lm_head, audio_head[i]) — it must hold the bf16 form of W' —, q / exp: its fp8
+ * twin from ua2_pack_linear_w8}.  Launches of the frame that go to the decode kernel — exactly those that would go to it in the plain bf16 plan: by default up to 5 rows
+ * (UA2_GEMV_MAX_ROWS), and a weight whose (N, K) geometry has no fp8 form stays on its bf16 form — then stream the fp8 image of every
+ * weight that has an entry (a SWIGLU launch: of both); prefill chunks, larger batches and the plan's tables keep reading W' — the same
+ * function, the same bits.  lm_head then runs as a launch of its own (the rider kernel has no fp8 form).  The table is copied; the
+ * images stay owned by the caller and alive as long as the plan uses them.  n = 0 clears.  Every call drops the captured frame graphs.
+ * An entry whose pointer is not a weight of the plan, or a plan of another dtype, is an error. */
+typedef struct {
+  const void* w;
+  const void* q;
+  const int8_t* exp;
+} ua2_w8_entry;
+int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32_t n);
 /* n-gram repeat filter of the text-feedback frames: with n >= 2 every feedback of mode 1 (ua2_stage3_frame with or without
  * UA2_FRAME_SKIP_AUDIO_EXPERTS, and the standalone feedback) first runs the n-gram filter above over the text ids of its R rows,
  * so the frame log and the fed-back text id carry the filtered id.  hist [max_batch, cap] / hist_len [max_batch] int32 are

@@ -70,6 +70,16 @@ class ConvTcArgs(C.Structure):
                 ("y_hi", vp), ("y_lo", vp), ("y_f32", vp)]
 
 
+class W8Ref(C.Structure):
+    """ua2_w8_ref: fp8 (e4m3fn) image + per-column exponents of one packed weight (ua2_pack_linear_w8)."""
+    _fields_ = [("q", vp), ("exp", vp)]
+
+
+class W8Entry(C.Structure):
+    """ua2_w8_entry: (packed bf16 pointer of a plan weight, its fp8 image, its exponents) for ua2_stage3_set_w8."""
+    _fields_ = [("w", vp), ("q", vp), ("exp", vp)]
+
+
 ACT_NONE, ACT_PRELU, ACT_ELU, ACT_TANH, ACT_ROUND9 = 0, 1, 2, 3, 4
 EW_IDENTITY, EW_SILU, EW_SIGMOID, EW_TANH = 0, 1, 2, 3
 
@@ -98,6 +108,10 @@ _EXPORTS = {
     "ua2_packed_elems": (C.c_size_t, [C.c_int, i64, i64]),
     "ua2_pack_linear": (C.c_int, [vp, C.c_int, C.c_int, i64, i64, vp, C.c_int, C.c_int, vp]),
     "ua2_linear": (C.c_int, [C.POINTER(LinearArgs), vp]),
+    "ua2_packed_bytes_w8": (C.c_size_t, [i64, i64]),
+    "ua2_pack_linear_w8": (C.c_int, [vp, C.c_int, C.c_int, i64, i64, vp, vp, vp, C.c_int, vp]),
+    "ua2_linear_w8": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), vp]),
+    "ua2_stage3_set_w8": (C.c_int, [vp, C.POINTER(W8Entry), i32]),
     "ua2_linear_order_free_accepts": (C.c_int, [C.POINTER(LinearArgs)]),
     "ua2_debug_force_general_linear": (C.c_int, [C.c_int]),
     "ua2_debug_kernel_launches": (i64, [C.c_char_p]),

@@ -193,7 +193,7 @@ inline void ua2_allow_big_lds() {
 }
 
 // ---- test hooks (ua2hip.h ABI v9): launch counters per kernel family, and UA2_* environment variables read once -------------
-enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_N = 5 };
+enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_N = 6 };
 extern std::atomic<int64_t> g_ua2_launches[UA2_CNT_N];
 extern std::atomic<int> g_ua2_env_gen;              // bumped by ua2_debug_refresh_env
 inline void ua2_count_launch(int family) { g_ua2_launches[family].fetch_add(1, std::memory_order_relaxed); }
@@ -214,8 +214,16 @@ struct Ua2EnvInt {
   bool set() { load(); return present; }
 };
 
+// fp8 (OCP e4m3fn) weight-only twins of a launch's w0 / w1 (include/ua2hip.h ua2_pack_linear_w8): image + per-column exponents.
+// strict: the caller asked for the fp8 kernel by name (ua2_linear_w8) — a launch it does not serve is an error, never the bf16 twin.
+struct Ua2W8 {
+  const void *q0 = nullptr, *q1 = nullptr;
+  const int8_t *e0 = nullptr, *e1 = nullptr;
+  bool strict = false;
+};
 // internal launchers used by both the op-level ABI and the frame executor
-int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s);
+// w8 != NULL: launches that the decode kernel serves stream the fp8 image instead of a.w0 / a.w1 (the same bits: a.w0 / a.w1 hold W')
+int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
 int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_attn_local_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_gemv_rows_per_tile(int dtype, int K);   // rows one decode-kernel workgroup holds in LDS (ua2_gemv.hip)
@@ -245,7 +253,9 @@ int ua2_argmax_embed_launch(int dtype, int32_t M, int32_t n_part, int32_t limit,
                             int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, hipStream_t s);
 int ua2_kv_rows_extract(const void* k_pool, const void* v_pool, const int32_t* pos, int n, int n_kv, int hs, int esz, void* out_k, void* out_v, hipStream_t s);
 // decode-regime specialisation; returns 1 when the problem is outside its regime
-int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s);
+int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
+// does the decode kernel have an fp8-weight form for this launch (bf16, K % 64 == 0, a (prologue, epilogue) pair of the decode frame, a geometry it tiles)?
+bool ua2_gemv_w8_ok(const ua2_linear_args& a);
 // riders (ua2_gemv.hip gemv_rider_kernel): column tiles [tile0, tile1) of the one-row-tile GEMV `r` on the idle CUs of host launch `a`
 bool ua2_gemv_rider_ok(const ua2_linear_args& a, const ua2_linear_args& r);
 int ua2_gemv_launch_with_rider(const ua2_linear_args& a, const ua2_linear_args& r, int tile0, int tile1, hipStream_t s);

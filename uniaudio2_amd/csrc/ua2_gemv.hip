@@ -49,13 +49,38 @@ __device__ __forceinline__ void local_attn_prologue(const ua2_linear_args& a, ch
   if (!streamed) burst();
 }
 
+// fp8 weights (W8 != 0; include/ua2hip.h ua2_pack_linear_w8).  One 16-byte lane load of the fp8 image carries the lane's B fragments of
+// TWO chunks (2j: bytes 0-7, 2j + 1: bytes 8-15), so a wave streams half the bytes of the bf16 launch in half as many 1 KiB bursts.
+// Eight OCP e4m3fn codes -> the bf16 B fragment of one chunk, exactly (an e4m3 value has 4 significant bits and sits inside the bf16
+// exponent range, subnormals included): v_cvt_pk_f32_fp8 x 4, v_cvt_pk_bf16_f32 x 4.  The row's power-of-two scale is NOT applied here
+// but once on the reduced tile (a power of two commutes with every fp32 rounding of the chain and of the cross-wave sum).
+__device__ __forceinline__ u32x4 dequant_e4m3x8(unsigned d0, unsigned d1) {
+  const f32x2_hw f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
+  const f32x2_hw f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
+  return u32x4{pack_bf16x2(f0[0], f0[1]), pack_bf16x2(f1[0], f1[1]), pack_bf16x2(f2[0], f2[1]), pack_bf16x2(f3[0], f3[1])};
+}
+
+// 1 KiB burst of the weight image that load `u` of the round starting at chunk `cb` fetches (`last` = the wave's last chunk: clamped, never predicated)
+template <int W8>
+__device__ __forceinline__ int burst_index(int cb, int u, int last) {
+  if constexpr (W8 == 1) return min((cb >> 1) + u, last >> 1);
+  else if constexpr (W8 == 2) return min(cb + u, last) >> 1;
+  else return min(cb + u, last);
+}
+
 // MR = multi-round: <= 8 waves per workgroup, several rounds of CPW chunks per wave, next round's
 // weights prefetched (double buffer); !MR = single burst: up to 16 waves, everything up front.
-template <int DT, int PRO, int EPI, int CPW, bool MR>
+// W8: 0 = the weights of a.w0 / a.w1 in the launch dtype; 1 = fp8 image, the wave's chunk range is a whole number of rounds of CPW
+// chunks (every shape of the released model): CPW / 2 loads per round; 2 = fp8 image, any range of up to CPW chunks (odd starts,
+// single-chunk ranges: small K): one load per chunk, the half picked by the chunk's parity.  The geometry, the chunk order inside a
+// wave's chain and the order of the cross-wave sum are those of W8 = 0, whatever the form.
+template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0>
 __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, const int a_stride, const int red_off, const int rt,
-                                          const int bx, const int by) {
+                                          const int bx, const int by, const Ua2W8* w8 = nullptr) {
   constexpr int KC = Elem<DT>::KC, EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
   constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
+  static_assert(W8 == 0 || DT == UA2_BF16, "fp8 weights are a bf16-plan option");
+  constexpr int NL = (W8 == 1) ? CPW / 2 : CPW;               // weight loads per matrix per round
   char* a_lds = smem;                                        // [rows][a_stride] of T
   float* red = reinterpret_cast<float*>(smem + red_off);     // [nw][NT][256]
   float* ssq = red + kMaxWaves * NT * 256;                   // [nw][16]
@@ -72,7 +97,11 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   const int nchunks = (a.K + KC - 1) / KC;
   int tile[NT];
   const u32x4* wp[NT];
-  if constexpr (EPI == UA2_EPI_SWIGLU) {
+  if constexpr (W8 != 0) {                                     // [N/16][K/64][64 lanes][16 B]: nchunks / 2 bursts per tile (K % 64 == 0)
+    tile[0] = bx;
+    wp[0] = reinterpret_cast<const u32x4*>(w8->q0) + (size_t)bx * (nchunks >> 1) * 64 + lane;
+    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(w8->q1) + (size_t)bx * (nchunks >> 1) * 64 + lane; }
+  } else if constexpr (EPI == UA2_EPI_SWIGLU) {
     tile[0] = tile[1] = bx;
     wp[0] = reinterpret_cast<const u32x4*>(a.w0) + (size_t)tile[0] * nchunks * 64 + lane;
     wp[1] = reinterpret_cast<const u32x4*>(a.w1) + (size_t)tile[0] * nchunks * 64 + lane;
@@ -120,13 +149,22 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   if constexpr (PRO == UA2_PRO_SCALED) {
     if (tid < 256) scaled_ssq_request(a, m0 + min(tid >> 4, rows - 1), tid & 15, ssqv);
   }
+  // fp8 weights: exponent of this thread's epilogue column (16 bytes per tile, padded to 16 columns: in bounds for every thread).  Every
+  // thread loads it, not just the 256 epilogue threads: a load under a lane predicate ends in a wait in front of the weight burst
+  int wexp[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) wexp[t] = 0;
+  if constexpr (W8 != 0) {
+    wexp[0] = w8->e0[bx * 16 + (tid & 15)];
+    if constexpr (NT == 2) wexp[1] = w8->e1[bx * 16 + (tid & 15)];
+  }
 
-  u32x4 wf[NT][CPW];
+  u32x4 wf[NT][NL];
   auto burst = [&]() {
 #pragma unroll
-    for (int u = 0; u < CPW; ++u)
+    for (int u = 0; u < NL; ++u)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)min(c0 + u, last) * 64);
+      for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(c0, u, last) * 64);
   };
   if constexpr (PRO == UA2_PRO_LOCAL_ATTN) {
     switch (a.kv.head_size) {
@@ -254,13 +292,13 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   const char* abase = a_lds + ((size_t)i * a_stride + g * EPL) * BYTES;
   for (int cb = c0; cb < c1; cb += CPW) {
     // multi-round geometries: the next round's weights go out before this round's MFMAs
-    u32x4 wn[NT][MR ? CPW : 1];
+    u32x4 wn[NT][MR ? NL : 1];
     const bool more = MR && (cb + CPW < c1);
     if constexpr (MR) if (more) {
 #pragma unroll
-      for (int u = 0; u < CPW; ++u)
+      for (int u = 0; u < NL; ++u)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) wn[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)min(cb + CPW + u, last) * 64);
+        for (int t = 0; t < NT; ++t) wn[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(cb + CPW, u, last) * 64);
     }
 #pragma unroll
     for (int u = 0; u < CPW; ++u) {
@@ -270,20 +308,31 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       if (arow && c < c1) raw = *reinterpret_cast<const u32x4*>(abase + (size_t)c * KC * BYTES);
       af.v = __builtin_bit_cast(decltype(af.v), raw);
 #pragma unroll
-      for (int t = 0; t < NT; ++t) af.mma(wf[t][u], acc[t]);
+      for (int t = 0; t < NT; ++t) {
+        if constexpr (W8 == 1) {                           // chunk cb + u: half (u & 1) of load u / 2 (cb is even)
+          const u32x4 w = wf[t][u >> 1];
+          af.mma(dequant_e4m3x8(w[(u & 1) * 2], w[(u & 1) * 2 + 1]), acc[t]);
+        } else if constexpr (W8 == 2) {                    // chunk c: half (c & 1) of its own load (a clamped chunk meets a zero A fragment)
+          const u32x4 w = wf[t][u];
+          const bool odd = (min(c, last) & 1) != 0;
+          af.mma(dequant_e4m3x8(odd ? w[2] : w[0], odd ? w[3] : w[1]), acc[t]);
+        } else {
+          af.mma(wf[t][u], acc[t]);
+        }
+      }
     }
     if constexpr (MR) {
       if (more) {
 #pragma unroll
-        for (int u = 0; u < CPW; ++u)
+        for (int u = 0; u < NL; ++u)
 #pragma unroll
           for (int t = 0; t < NT; ++t) wf[t][u] = wn[t][u];
       }
     } else if (cb + CPW < c1) {  // rare: single-burst geometry that does not tile K exactly
 #pragma unroll
-      for (int u = 0; u < CPW; ++u)
+      for (int u = 0; u < NL; ++u)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)min(cb + CPW + u, last) * 64);
+        for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(cb + CPW, u, last) * 64);
     }
   }
 
@@ -300,6 +349,8 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     float s = 0.f;
     for (int w = 0; w < nw; ++w) s += red[(w * NT + t) * 256 + src];
     v[t] = s;
+    // fp8 weights: the column's scale 2^e, once, on the reduced sum (exact: e in [-117, 120] keeps 2^e a normal float)
+    if constexpr (W8 != 0) v[t] = __fmul_rn(s, __uint_as_float((unsigned)(wexp[t] + 127) << 23));
   }
   linear_epilogue<DT, EPI, NT>(a, v, tile, row, col, pre, m0, rows);
 }
@@ -309,6 +360,14 @@ __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_kernel(const u
                                                               const int red_off, const int rt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<DT, PRO, EPI, CPW, MR>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y);
+}
+
+// the same launch on the fp8 image of its weight(s): bf16 activations in LDS, bf16 MFMA, half the weight bytes
+template <int PRO, int EPI, int CPW, bool MR, int W8>
+__global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_w8_kernel(const ua2_linear_args a, const int a_stride,
+                                                                 const int red_off, const int rt, const Ua2W8 w8) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
 }
 
 // ---- riders: a second, independent one-row-tile GEMV carried by the idle CUs of a launch that cannot fill the device -----------
@@ -462,8 +521,26 @@ void launch_one(const ua2_linear_args& a, dim3 grid, int waves, int a_stride, in
   ua2_count_launch(UA2_CNT_GEMV);
 }
 
+template <int PRO, int EPI, int CPW, bool MR, int W8>
+void launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
+  constexpr auto kern = gemv_w8_kernel<PRO, EPI, CPW, MR, W8>;
+  ua2_allow_big_lds<kern>();
+  hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt, w8);
+  ua2_count_launch(UA2_CNT_GEMV_W8);
+}
+
+// Which fp8 form serves a geometry: 1 = every wave's range is whole rounds of cpw chunks; 2 = ranges of up to 4 chunks in one
+// single-burst round of 4 (the small-K fall-back geometries); 0 = none (the launch stays on the bf16 twin).
+int w8_form(int nchunks, const Geometry& geo) {
+  if (nchunks % 2) return 0;
+  if (nchunks % geo.waves == 0 && (nchunks / geo.waves) % geo.cpw == 0) return 1;
+  const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
+  if (!mr && geo.cpw == 4 && ua2_ceil_div(nchunks, geo.waves) <= 4) return 2;
+  return 0;
+}
+
 template <int DT, int PRO, int EPI>
-int launch_cpw(const ua2_linear_args& a, hipStream_t s) {
+int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr) {
   constexpr int KC = Elem<DT>::KC, BYTES = Elem<DT>::BYTES;
   constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
   const int nchunks = ua2_ceil_div(a.K, KC);
@@ -482,6 +559,28 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s) {
   const size_t smem = (size_t)red_off + (size_t)(kMaxWaves * NT * 256 + 2 * kMaxWaves * 16 + 32) * sizeof(float);
   const dim3 grid(gx, mtiles);
   const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
+  if constexpr (DT == UA2_BF16 && (EPI == UA2_EPI_QKV_ROPE || EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_STORE || EPI == UA2_EPI_RESIDUAL) &&
+                !(PRO == UA2_PRO_CAST && (EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_QKV_ROPE))) {
+    if (w8) {     // the same grid, waves, LDS carve and chunk ranges: only the weight stream differs
+      const int form = w8_form(nchunks, geo);
+      if (form == 2) {
+        launch_one_w8<PRO, EPI, 4, false, 2>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else if (form == 1 && mr) {
+        if (geo.cpw == 4) launch_one_w8<PRO, EPI, 4, true, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one_w8<PRO, EPI, 8, true, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else if (form == 1) {
+        if (geo.cpw == 4) launch_one_w8<PRO, EPI, 4, false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else if (geo.cpw == 8 || NT == 2) launch_one_w8<PRO, EPI, 8, false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one_w8<PRO, EPI, (NT == 1 ? 16 : 8), false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else {
+        return 1;
+      }
+      UA2_LAUNCH_CHECK();
+      return 0;
+    }
+  } else {
+    if (w8) return 1;
+  }
   if (mr) {
     if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
     else launch_one<DT, PRO, EPI, 8, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
@@ -498,8 +597,36 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s) {
   return 0;
 }
 
+// the (prologue, epilogue) pairs of the bf16 decode frame: the ones with an fp8-weight instantiation
+bool w8_pair(int pro, int epi) {
+  switch (pro) {
+    case UA2_PRO_NORM: case UA2_PRO_SCALED: return epi == UA2_EPI_QKV_ROPE || epi == UA2_EPI_SWIGLU || epi == UA2_EPI_STORE;
+    case UA2_PRO_CAST: return epi == UA2_EPI_RESIDUAL || epi == UA2_EPI_STORE;
+    case UA2_PRO_LOCAL_ATTN: return epi == UA2_EPI_RESIDUAL;
+    default: return false;
+  }
+}
+
 template <int DT>
-int launch_dt(const ua2_linear_args& a, hipStream_t s) {
+int launch_dt(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr) {
+  if (w8) {       // fp8 weights: only the pairs above (each instantiation below is compiled for exactly those)
+    if (DT != UA2_BF16 || !w8_pair(a.prologue, a.epilogue)) return 1;
+    if (a.prologue == UA2_PRO_NORM) {
+      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s, w8);
+      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s, w8);
+      return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_STORE>(a, s, w8);
+    } else if (a.prologue == UA2_PRO_CAST) {
+      if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_RESIDUAL>(a, s, w8);
+      return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_STORE>(a, s, w8);
+    } else if (a.prologue == UA2_PRO_LOCAL_ATTN) {
+      return launch_cpw<DT, UA2_PRO_LOCAL_ATTN, UA2_EPI_RESIDUAL>(a, s, w8);
+    } else if constexpr (DT == UA2_BF16) {
+      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_QKV_ROPE>(a, s, w8);
+      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_SWIGLU>(a, s, w8);
+      return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_STORE>(a, s, w8);
+    }
+    return 1;
+  }
   if (a.prologue == UA2_PRO_NORM) {
     if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s);
     if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s);
@@ -588,8 +715,16 @@ ua2_gemv_geometry ua2_pick_gemv_geometry(int dtype, int N, int K, int nt) {
 
 // Returns 0 if launched, 1 if this problem is outside the decode regime (caller uses the general
 // kernel), negative on error.
-int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s) {
+bool ua2_gemv_w8_ok(const ua2_linear_args& a) {
+  if (a.dtype != UA2_BF16 || a.K % 64 || a.N <= 0 || !w8_pair(a.prologue, a.epilogue) || rows_per_tile(a.dtype, a.K) < 1) return false;
+  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
+  return w8_form(a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
+}
+
+int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
   if (rows_per_tile(a.dtype, a.K) < 1) return 1;   // a single row does not fit the LDS budget
+  if (w8 && w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && ua2_gemv_w8_ok(a)) return launch_dt<UA2_BF16>(a, s, w8);
+  if (w8 && w8->strict) return 1;                  // asked for by name: never the bf16 twin in its place
   if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s);
   if (a.dtype == UA2_F32) return launch_dt<UA2_F32>(a, s);
   return 1;

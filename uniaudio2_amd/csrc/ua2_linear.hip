@@ -9,6 +9,8 @@
 //     contiguous 1 KiB burst (64 lanes x 16 B);
 //   * M rows ride in the 16-row A operand of mfma_f32_16x16x32_bf16 (bf16 operands, fp32 accumulate) or
 //     mfma_f32_16x16x4_f32 (exact fp32).
+#include <algorithm>
+
 #include "ua2_common.h"
 #include "ua2_linear_common.h"
 
@@ -40,11 +42,86 @@ __global__ void pack_kernel(const void* __restrict__ src, void* __restrict__ out
   }
 }
 
+// ---- fp8 (OCP e4m3fn) weight-only packing: include/ua2hip.h ua2_pack_linear_w8 -----------------------------------------------
+// packed column -> source row (the bf16 pack's map: rope_hs > 0 permutes the rows of every head)
+__device__ __forceinline__ int64_t w8_src_row(int64_t n, int rope_hs) {
+  if (rope_hs <= 0) return n;
+  const int64_t h = n / rope_hs, within = n - h * rope_hs;
+  const int64_t r = within / 16, c = within % 16;
+  return h * rope_hs + (c < 8 ? r * 8 + c : rope_hs / 2 + r * 8 + (c - 8));
+}
+
+// e = ceil(log2(amax / 448)) without a logarithm: amax = m 2^x with m in [0.5, 1) and 448 = 0.875 2^9, so amax 2^-e <= 448 first holds
+// at e = x - 9 (m <= 0.875) or x - 8.  Zero rows take 0; clamped to [-117, 120] so that both 2^e and the smallest nonzero |W'| = 2^(e - 9)
+// are normal numbers of fp32 and bf16.
+__device__ __forceinline__ int w8_exponent(float amax) {
+  if (!(amax > 0.f)) return 0;
+  int x;
+  const float m = frexpf(amax, &x);
+  const int e = (m <= 0.875f) ? x - 9 : x - 8;
+  return min(max(e, -117), 120);
+}
+
+// RNE of a finite |v| <= 448 to OCP e4m3fn (bias 7, subnormals m / 8 2^-6, no infinities): the code byte, sign included
+__device__ __forceinline__ unsigned f2e4m3(float v) {
+  const unsigned sign = (__float_as_uint(v) >> 24) & 0x80u;
+  const float x = fminf(fabsf(v), 448.f);
+  if (x < 0.015625f) return sign | (unsigned)rintf(x * 512.f);       // below 2^-6: multiples of 2^-9 (8 = the smallest normal)
+  unsigned u = __float_as_uint(x);
+  u += 0x7ffffu + ((u >> 20) & 1u);                                    // round the 23-bit fraction to 3 bits, ties to even
+  return sign | ((((u >> 23) - 120u) << 3) | ((u >> 20) & 7u));
+}
+__device__ __forceinline__ float e4m32f(unsigned b) {
+  const unsigned E = (b >> 3) & 15u, m = b & 7u;
+  const float mag = E ? __uint_as_float(((E + 120u) << 23) | (m << 20)) : (float)m * 0.001953125f;
+  return (b & 0x80u) ? -mag : mag;
+}
+
+// one wave per packed column: amax over the source row -> exponent (columns past N: 0)
+template <int SRC>
+__global__ void w8_exp_kernel(const void* __restrict__ src, int8_t* __restrict__ out_exp, int transposed, int64_t N, int64_t K, int64_t n16, int rope_hs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t np = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (np >= n16) return;
+  const int64_t n = w8_src_row(np, rope_hs);
+  float amax = 0.f;
+  if (n < N)
+    for (int64_t k = lane; k < K; k += 64) amax = fmaxf(amax, fabsf(load_elem<SRC>(src, transposed ? (size_t)(k * N + n) : (size_t)(n * K + k))));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+  if (lane == 0) out_exp[np] = (int8_t)w8_exponent(amax);
+}
+
+// one thread per fp8 byte of the image [N/16][K/64][64 lanes][16 B]; the bf16 twin W' = q 2^e goes out from the same q and e
+template <int SRC>
+__global__ void w8_pack_kernel(const void* __restrict__ src, const int8_t* __restrict__ exps, uint8_t* __restrict__ out_q,
+                               unsigned short* __restrict__ out_bf16, int transposed, int64_t N, int64_t K, int64_t total, int rope_hs) {
+  const int64_t nbursts = K / 64;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int e = (int)(idx & 7), half = (int)((idx >> 3) & 1), lane = (int)((idx >> 4) & 63);
+    const int64_t burst = (idx >> 10) % nbursts, tile = (idx >> 10) / nbursts;
+    const int64_t chunk = 2 * burst + half;
+    const int64_t np = tile * 16 + (lane & 15), n = w8_src_row(np, rope_hs);
+    const int64_t k = chunk * 32 + (lane >> 4) * 8 + e;
+    const int ex = exps[np];
+    float v = 0.f;
+    if (n < N) v = load_elem<SRC>(src, transposed ? (size_t)(k * N + n) : (size_t)(n * K + k));
+    const unsigned q = f2e4m3(__fmul_rn(v, __uint_as_float((unsigned)(127 - ex) << 23)));
+    out_q[idx] = (uint8_t)q;
+    if (out_bf16) out_bf16[((tile * (2 * nbursts) + chunk) * 64 + lane) * 8 + e] = f2bf(__fmul_rn(e4m32f(q), __uint_as_float((unsigned)(127 + ex) << 23)));
+  }
+}
+
 }  // namespace
 
 static int g_force_general = 0;
 
-int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s) {
+int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
+  const bool w8_strict = w8 && w8->strict;
+  if (w8_strict)
+    UA2_CHECK(a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_w8_ok(a),
+              "ua2_linear_w8: not a launch the fp8 decode kernel serves (UA2_BF16, K %% 64 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed)",
+              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
   UA2_CHECK(a.M > 0 && a.N > 0 && a.K > 0, "ua2_linear: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   UA2_CHECK(a.w0 != nullptr, "ua2_linear: w0 is NULL");
   const int epl = a.dtype == UA2_BF16 ? 8 : 4;
@@ -57,7 +134,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s) {
                   a.kv.n_head % (128 / a.kv.head_size) == 0 && a.K == a.kv.n_head * a.kv.head_size && a.K % kc == 0,
               "ua2_linear: bad LOCAL_ATTN arguments");
     UA2_CHECK(a.resid != nullptr && a.y != nullptr, "ua2_linear: RESIDUAL needs resid, y");
-    const int rc = ua2_gemv_try_launch(a, s);
+    const int rc = ua2_gemv_try_launch(a, s, w8);
     UA2_CHECK(rc <= 0, "ua2_linear: LOCAL_ATTN problem outside the decode kernel's range");
     return rc;
   }
@@ -88,7 +165,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s) {
   }
   if (a.prologue == UA2_PRO_SCALED) {   // row-major hand-over: one row tile, the decode kernel
     UA2_CHECK(a.M <= ua2_gemv_rows_per_tile(a.dtype, a.K), "ua2_linear: x_h serves launches of one row tile (M=%d): hand over x_packed", a.M);
-    const int rc = ua2_gemv_try_launch(a, s);
+    const int rc = ua2_gemv_try_launch(a, s, w8);
     UA2_CHECK(rc <= 0, "ua2_linear: UA2_PRO_SCALED launch outside the decode kernel's range");
     return rc;
   }
@@ -125,11 +202,11 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s) {
     ua2_set_error("ua2_linear: bad dtype %d", a.dtype);
     return -1;
   }
-  if (g_force_general != 2) {
+  if (g_force_general != 2 && !w8_strict) {
     const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0);  // many rows: packed operand, 128-row tiles
     if (rc <= 0) return rc;
   }
-  const int rc = ua2_gemv_try_launch(a, s);  // decode regime: LDS-staged activations, all loads up front
+  const int rc = ua2_gemv_try_launch(a, s, w8);  // decode regime: LDS-staged activations, all loads up front
   UA2_CHECK(rc <= 0, "ua2_linear: prologue %d / epilogue %d / K=%d is outside the built kernels (a row must fit the LDS operand tile)",
             a.prologue, a.epilogue, a.K);
   return rc;
@@ -193,4 +270,41 @@ extern "C" int ua2_pack_linear(const void* src, int src_dtype, int transposed, i
   }
   UA2_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" size_t ua2_packed_bytes_w8(int64_t N, int64_t K) {
+  if (N <= 0 || K <= 0 || K % 64) return 0;
+  return (size_t)((N + 15) / 16) * 16 * (size_t)K;
+}
+
+extern "C" int ua2_pack_linear_w8(const void* src, int src_dtype, int transposed, int64_t N, int64_t K, void* out_q, int8_t* out_exp,
+                                  void* out_bf16, int rope_head_size, void* stream) {
+  UA2_CHECK(src && out_q && out_exp && N > 0 && K > 0, "ua2_pack_linear_w8: bad arguments");
+  UA2_CHECK(K % 64 == 0, "ua2_pack_linear_w8: K=%lld must be a multiple of 64 (two 32-wide chunks per fp8 burst)", (long long)K);
+  UA2_CHECK(rope_head_size == 0 || (rope_head_size % 32 == 0 && N % rope_head_size == 0),
+            "ua2_pack_linear_w8: rope_head_size=%d must divide N and be a multiple of 32", rope_head_size);
+  UA2_CHECK(src_dtype == UA2_F32 || src_dtype == UA2_BF16, "ua2_pack_linear_w8: bad source dtype %d", src_dtype);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n16 = (N + 15) / 16 * 16, total = n16 * K;
+  const int eblocks = (int)((n16 + 3) / 4);
+  const int blocks = (int)std::min<int64_t>((total + 255) / 256, 65535 * 16);
+  if (src_dtype == UA2_F32) {
+    hipLaunchKernelGGL(w8_exp_kernel<UA2_F32>, dim3(eblocks), dim3(256), 0, s, src, out_exp, transposed, N, K, n16, rope_head_size);
+    hipLaunchKernelGGL(w8_pack_kernel<UA2_F32>, dim3(blocks), dim3(256), 0, s, src, out_exp, (uint8_t*)out_q, (unsigned short*)out_bf16, transposed, N, K, total, rope_head_size);
+  } else {
+    hipLaunchKernelGGL(w8_exp_kernel<UA2_BF16>, dim3(eblocks), dim3(256), 0, s, src, out_exp, transposed, N, K, n16, rope_head_size);
+    hipLaunchKernelGGL(w8_pack_kernel<UA2_BF16>, dim3(blocks), dim3(256), 0, s, src, out_exp, (uint8_t*)out_q, (unsigned short*)out_bf16, transposed, N, K, total, rope_head_size);
+  }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream) {
+  UA2_CHECK(a != nullptr && w0 != nullptr && w0->q && w0->exp, "ua2_linear_w8: NULL args or fp8 twin of w0");
+  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->q && w1->exp), "ua2_linear_w8: SWIGLU needs the fp8 twin of w1");
+  Ua2W8 w8;
+  w8.q0 = w0->q; w8.e0 = w0->exp;
+  if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
+  w8.strict = true;
+  return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
 }

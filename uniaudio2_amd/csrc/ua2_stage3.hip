@@ -64,6 +64,9 @@ struct ua2_stage3 {
   // n-gram repeat filter of the text-feedback frames (ua2_stage3_set_ngram; ngram_n <= 1 = off): caller-owned device history
   int32_t ngram_n = 0, ngram_fallback = 0, ngram_cap = 0;
   int32_t *ngram_hist = nullptr, *ngram_hist_len = nullptr;
+  // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
+  struct W8Twin { const void* q; const int8_t* exp; };
+  std::map<const void*, W8Twin> w8;
   std::map<std::tuple<int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
 };
 
@@ -132,6 +135,22 @@ void fresh_args(const ua2_stage3* h, ua2_linear_args& a) {
   memset(&a, 0, sizeof(a));
   a.workspace = h->gemm_ws;
   a.workspace_bytes = h->gemm_ws_bytes;
+}
+
+// Every Linear of the frame goes through here: with fp8 twins attached, a launch whose weight(s) all have one hands them to the launcher,
+// which streams them where the decode kernel serves the launch (few rows) and reads a.w0 / a.w1 — the bf16 forms of W' — everywhere else.
+int lin(const ua2_stage3* h, const ua2_linear_args& a, hipStream_t s) {
+  if (h->w8.empty()) return ua2_linear_launch(a, s);
+  const auto t0 = h->w8.find(a.w0);
+  if (t0 == h->w8.end()) return ua2_linear_launch(a, s);
+  Ua2W8 w;
+  w.q0 = t0->second.q; w.e0 = t0->second.exp;
+  if (a.epilogue == UA2_EPI_SWIGLU) {
+    const auto t1 = h->w8.find(a.w1);
+    if (t1 == h->w8.end()) return ua2_linear_launch(a, s);
+    w.q1 = t1->second.q; w.e1 = t1->second.exp;
+  }
+  return ua2_linear_launch(a, s, &w);
 }
 
 // local = the depth decoder: positions < kLocalCtx, short-context attention (fused into the O-projection when R == 1)
@@ -205,7 +224,7 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
       UA2_CHECK(rc <= 0, "ua2_stage3: launch kind %d cannot carry its rider (plan / launch mismatch)", kind);
       return rc;
     }
-    return ua2_linear_launch(a, s);
+    return lin(h, a, s);
   };
   const int dt = h->d.dtype;
   const int C = g.n_embd, qn = g.n_head * g.head_size, nqkv = (g.n_head + 2 * g.n_kv) * g.head_size;
@@ -267,7 +286,7 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     if (pack_act) a.y_packed = h->act_ws; else a.y = h->act;
     if (scaled) ho.consume(a);
     a.sum_order = order;
-    if (int rc = ua2_linear_launch(a, s)) return rc;
+    if (int rc = lin(h, a, s)) return rc;
 
     fresh_args(h, a);
     a.dtype = dt; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_RESIDUAL;
@@ -512,6 +531,27 @@ extern "C" int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows) {
   return 0;
 }
 
+extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32_t n) {
+  UA2_CHECK(h != nullptr && n >= 0 && (n == 0 || table), "ua2_stage3_set_w8: NULL handle / table or n < 0");
+  UA2_CHECK(n == 0 || h->d.dtype == UA2_BF16, "ua2_stage3_set_w8: fp8 weights are an option of UA2_BF16 plans");
+  std::map<const void*, ua2_stage3::W8Twin> m;
+  for (int i = 0; i < n; ++i) {
+    const ua2_w8_entry& e = table[i];
+    UA2_CHECK(e.w && e.q && e.exp, "ua2_stage3_set_w8: entry %d has a NULL pointer", i);
+    bool mine = e.w == h->d.lm_head || e.w == h->d.projection;
+    for (const void* p : h->audio_head) mine = mine || p == e.w;
+    for (int gi = 0; gi < 4 && !mine; ++gi)
+      for (int k = 0; k < 5 && !mine; ++k)
+        for (const void* p : h->ptrs[gi][k]) mine = mine || p == e.w;
+    UA2_CHECK(mine, "ua2_stage3_set_w8: entry %d is not a weight of this plan", i);
+    m[e.w] = ua2_stage3::W8Twin{e.q, e.exp};
+  }
+  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);     // recorded frames bake the kernels and the weight pointers: drop them
+  h->graphs.clear();
+  h->w8.swap(m);
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, int32_t* hist, int32_t* hist_len, int32_t cap) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_ngram: NULL handle");
   if (n <= 1) {                    // off: the frame graphs key on n, so the filtered ones stay valid for the same buffers
@@ -573,7 +613,8 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   const ua2_linear_args lm = a;
   RiderPlan rp;
   bool ride = false;
-  if (!skip_text && !text_only && d.n_cb > 0 && d.decoder.n_layer > 0) {
+  // fp8 twins attached: the rider kernel has no fp8 form, so lm_head runs as a launch of its own (on its fp8 image when it has one)
+  if (!skip_text && !text_only && d.n_cb > 0 && d.decoder.n_layer > 0 && h->w8.empty()) {
     const ua2_gpt_desc& g = d.decoder;
     const int qn = g.n_head * g.head_size, nqkv = (g.n_head + 2 * g.n_kv) * g.head_size;
     ua2_linear_args hs[3];
@@ -595,7 +636,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     }
   }
   if (!skip_text && !ride)
-    if (int rc = ua2_linear_launch(lm, s)) return rc;
+    if (int rc = lin(h, lm, s)) return rc;
   // model_new.py:618-622: with guidance the sampler sees l[1] + (l[0] - l[1]) * cfg_scale and both rows take its sample
   const bool cfg = h->cfg_scale > 1.f && R > 1;
   UA2_CHECK(!cfg || R % 2 == 0, "ua2_stage3_heads: classifier-free guidance needs (conditional, unconditional) row pairs, R=%d", R);
@@ -624,7 +665,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
       a.M = R; a.N = Cd; a.K = C; a.x = curr; a.ldx = C; a.w0 = d.projection; a.y = h->xd; a.ldy = Cd;
       if (scaled) hod.produce(a, h->norms[3][0][0]);
       a.sum_order = order;
-      if (int rc = ua2_linear_launch(a, s)) return rc;
+      if (int rc = lin(h, a, s)) return rc;
     }
     if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, d.n_cb <= 8, false,
                          scaled ? d.decoder.ln_f : nullptr, scaled, ride ? &rp : nullptr, tab && i > 0 && h->ptab_q)) return rc;
@@ -635,7 +676,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     a.part_max = h->pmax_a; a.part_idx = h->pidx_a; a.forbid = d.forbid;
     if (scaled) hod.consume(a);
     a.sum_order = order;
-    if (int rc = ua2_linear_launch(a, s)) return rc;
+    if (int rc = lin(h, a, s)) return rc;
     if (cfg)   // model_new.py:634-637
       if (int rc = ua2_cfg_mix(h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->cfg_scale, d.forbid, h->pmax_a,
                                h->pidx_a, R / 2, s)) return rc;

@@ -122,8 +122,10 @@ class GPT(nn.Module):
 
     # ---- device plan -----------------------------------------------------------------------
     def set_kv_cache(self, batch_size: int, max_seq_length: Optional[int] = None, rope_cache_length=None,
-                     device=None, dtype=None):
-        """lit_model.py:224-254.  Also (re)packs the weights for `dtype` (torch.float32 or bfloat16)."""
+                     device=None, dtype=None, weight_dtype=None):
+        """lit_model.py:224-254.  Also (re)packs the weights for `dtype` (torch.float32 or bfloat16).
+        weight_dtype=torch.float8_e4m3fn (bf16 plans): every Linear is replaced by its fp8 weight-only form W' (ops.dequant_w8):
+        the packed bf16 weights ARE W', and plan["w8"] lists (bf16 twin, fp8 image, exponents) for the frame executor."""
         cfg = self.config
         p0 = self.transformer.h[0].attn.qkv.weight
         device = device or p0.device
@@ -133,10 +135,19 @@ class GPT(nn.Module):
         max_seq_length = max_seq_length or self.max_seq_length
         self.kv_cache = KVCache(cfg, cfg.n_layer, batch_size, max_seq_length, dtype, device)
         f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
-        pk = lambda lin: ops.pack_linear(lin.weight.detach().to(device), dtype)
-        plan = dict(dtype=dtype, device=device, batch=batch_size, max_seq=max_seq_length)
-        plan["qkv"] = [ops.pack_linear(b.attn.qkv.weight.detach().to(device), dtype, rope_head_size=cfg.head_size)
-                       for b in self.transformer.h]
+        if weight_dtype is not None and (weight_dtype != torch.float8_e4m3fn or dtype != torch.bfloat16):
+            raise ValueError("weight_dtype must be None or torch.float8_e4m3fn, and fp8 weights need dtype=torch.bfloat16")
+        plan = dict(dtype=dtype, device=device, batch=batch_size, max_seq=max_seq_length, w8=[])
+
+        def pack(w, rope_head_size=0):
+            if weight_dtype is None:
+                return ops.pack_linear(w.detach().to(device), dtype, rope_head_size=rope_head_size)
+            q, e, twin = ops.pack_linear_w8(w.detach().to(device), rope_head_size=rope_head_size)
+            plan["w8"].append((twin, q, e))
+            return twin
+
+        pk = lambda lin: pack(lin.weight)
+        plan["qkv"] = [pack(b.attn.qkv.weight, rope_head_size=cfg.head_size) for b in self.transformer.h]
         plan["proj"] = [pk(b.attn.proj) for b in self.transformer.h]
         plan["fc1"] = [pk(b.mlp.fc_1) for b in self.transformer.h]
         plan["fc2"] = [pk(b.mlp.fc_2) for b in self.transformer.h]

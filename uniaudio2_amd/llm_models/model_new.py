@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import Stage3Desc, check, lib, vp
+from .._lib import Stage3Desc, W8Entry, check, lib, vp
 from .config import Config as gpt_config
 from .lit_model import GPT
 
@@ -35,6 +35,9 @@ class ModelArgs:
     audio_semantic_vocab_size: int
     audio_reason_vocab_size: int
     audio_num_codebooks: int
+
+
+_UNSET = object()      # "argument left out" where None is a meaningful value
 
 
 def ragged_schedule(n_frames):
@@ -72,16 +75,28 @@ class Model_stage3(nn.Module):
         self._h = None
         self._st = None
         self.sampling_seed = None      # set by callers that key the sampler themselves (CLI: per-utterance keys)
+        self.weight_dtype = None       # torch.float8_e4m3fn: every bf16 plan setup_caches builds computes with the fp8 weight-only forms W' and streams fp8 images in its few-row launches (CLI --weight_dtype)
         self.order_free_rows = 0       # > 0: every plan setup_caches builds opts its many-row launches into the order-free GEMM (CLI --order_free_rows)
 
     # ---- caches / device plan ----------------------------------------------------------------
     def setup_caches(self, max_batch_size: int, dtype: Optional[torch.dtype] = None, max_seq_length: int = 2048,
-                     max_rows: Optional[int] = None, log_frames: int = 512):
+                     max_rows: Optional[int] = None, log_frames: int = 512, weight_dtype=_UNSET):
         """model_new.py:554-565: 2048-slot caches for the three 3072-d GPTs, `audio_num_codebooks`
         slots for the local decoder.  `dtype` selects the kernel precision (default: the
-        parameters' dtype, as in the reference where `.to(dtype)` decides)."""
+        parameters' dtype, as in the reference where `.to(dtype)` decides).
+        weight_dtype: None | torch.float8_e4m3fn (left out: self.weight_dtype).  fp8 (bf16 plans only; LOSSY: relative rms error of a
+        weight 2.7e-2 against bf16's 1.6e-3): every Linear of the four GPTs, projection, audio_head[i] and lm_head is replaced by
+        W' = RNE_e4m3fn(W 2^-e) 2^e with a power-of-two scale per output row (ops.dequant_w8) — embeddings, norms, RoPE tables and
+        the K/V caches are not touched.  The packed bf16 weights then hold W' and the launches that go to the few-row decode kernel (frames of up to 5 rows by default) stream the fp8 images
+        (half the bytes); the plan is bit-identical to a bf16 plan loaded with W'.  Costs 1.5 x the bf16 weight memory."""
         p0 = self.projection.weight
         device, dtype = p0.device, (dtype or p0.dtype)
+        if weight_dtype is _UNSET:
+            weight_dtype = getattr(self, "weight_dtype", None)
+        if weight_dtype is not None and weight_dtype != torch.float8_e4m3fn:
+            raise ValueError(f"weight_dtype must be None or torch.float8_e4m3fn, got {weight_dtype}")
+        if weight_dtype is not None and dtype != torch.bfloat16:
+            raise ValueError("weight_dtype=torch.float8_e4m3fn needs a bf16 plan (dtype=torch.bfloat16); the fp32 plan is the exact contract")
         if device.type != "cuda":
             raise RuntimeError("uniaudio2_amd runs on a ROCm device only (no CPU fallback); call model.to('cuda')")
         cfg = self.config
@@ -90,15 +105,24 @@ class Model_stage3(nn.Module):
         max_rows = max(max_rows or 64, B)
         self._destroy()
         for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert):
-            g.set_kv_cache(B, max_seq_length=max_seq_length, device=device, dtype=dtype)
-        self.decoder.set_kv_cache(B, max_seq_length=ncb, device=device, dtype=dtype)
-        st = dict(dtype=dtype, device=device, B=B, max_rows=max_rows, log_frames=log_frames, ncb=ncb, va=va)
+            g.set_kv_cache(B, max_seq_length=max_seq_length, device=device, dtype=dtype, weight_dtype=weight_dtype)
+        self.decoder.set_kv_cache(B, max_seq_length=ncb, device=device, dtype=dtype, weight_dtype=weight_dtype)
+        st = dict(dtype=dtype, device=device, B=B, max_rows=max_rows, log_frames=log_frames, ncb=ncb, va=va, weight_dtype=weight_dtype)
+        w8 = []                        # (bf16 twin, fp8 image, exponents) of the heads' weights
+
+        def pack(w, transposed=False):
+            if weight_dtype is None:
+                return ops.pack_linear(w.detach(), dtype, transposed=transposed)
+            q, e, twin = ops.pack_linear_w8(w.detach(), transposed=transposed)
+            w8.append((twin, q, e))
+            return twin
+
         cast = lambda t: t.detach().to(device=device, dtype=dtype).contiguous()
         st["wte"] = cast(self.backbone.transformer.wte.weight)
         st["audio_emb"] = cast(self.audio_embeddings.weight)
-        st["lm_head"] = ops.pack_linear(self.backbone.lm_head.weight.detach(), dtype)
-        st["projection"] = ops.pack_linear(self.projection.weight.detach(), dtype)
-        st["audio_head"] = [ops.pack_linear(self.audio_head[i].detach(), dtype, transposed=True) for i in range(ncb)]
+        st["lm_head"] = pack(self.backbone.lm_head.weight)
+        st["projection"] = pack(self.projection.weight)
+        st["audio_head"] = [pack(self.audio_head[i], transposed=True) for i in range(ncb)]
         i32 = dict(dtype=torch.int32, device=device)
         st["tokens"] = torch.zeros(max_rows, ncb + 1, **i32)
         st["mask"] = torch.zeros(max_rows, ncb + 1, dtype=torch.uint8, device=device)
@@ -140,6 +164,25 @@ class Model_stage3(nn.Module):
         self._ngram_hi = 0             # upper bound of every live row's n-gram history length (host side: no device sync)
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
             self.set_order_free_rows(self.order_free_rows)
+        if weight_dtype is not None:
+            for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert, self.decoder):
+                w8 += g.plan["w8"]
+            st["w8"] = w8              # keeps the fp8 images alive while the executor points at them
+            self.set_w8(True)
+
+    def set_w8(self, on: bool = True):
+        """Attach (or, on=False, clear) the fp8 images of a plan built with weight_dtype=torch.float8_e4m3fn.  Cleared, every launch
+        reads the bf16 forms of W' — the same ids and logits bit for bit, at the bf16 plan's speed.  Either way the captured frame
+        graphs are dropped (include/ua2hip.h ua2_stage3_set_w8)."""
+        self._need()
+        w8 = self._st.get("w8")
+        if w8 is None:
+            raise ValueError("this plan was built without fp8 weights (setup_caches(..., weight_dtype=torch.float8_e4m3fn))")
+        if not on:
+            check(lib.ua2_stage3_set_w8(self._h, None, 0), "ua2_stage3_set_w8")
+            return
+        tab = (W8Entry * len(w8))(*[W8Entry(t.data_ptr(), q.data_ptr(), e.data_ptr()) for t, q, e in w8])
+        check(lib.ua2_stage3_set_w8(self._h, tab, len(w8)), "ua2_stage3_set_w8")
 
     def _destroy(self):
         if self._h is not None:

@@ -114,6 +114,7 @@ def _load_config_and_llm(args):
     resume_for_inference(args.resume, args.exp_dir, model, device)
     model.to(device=device, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     model.order_free_rows = max(0, int(getattr(args, "order_free_rows", 0) or 0))     # applied by setup_caches (bf16 plans)
+    model.weight_dtype = torch.float8_e4m3fn if getattr(args, "weight_dtype", "none") == "fp8_e4m3" else None   # likewise
     return train_args, model, device
 
 
@@ -421,8 +422,18 @@ def decode_token_dir(codec, args, device):
     return wav_dir
 
 
+class _Parser(argparse.ArgumentParser):
+    """Checks the options that only make sense together at parse time (a usage error, not a failure after the checkpoint loaded)."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.weight_dtype != "none" and ns.dtype != "bf16":
+            self.error("--weight_dtype fp8_e4m3 needs --dtype bf16 (the fp32 plan is the exact contract)")
+        return ns
+
+
 def get_parser():
-    p = argparse.ArgumentParser(description="Multi-task inference: understanding (audio->text) or generation (text->wav)")
+    p = _Parser(description="Multi-task inference: understanding (audio->text) or generation (text->wav)")
     p.add_argument("--task", type=str, required=True)
     p.add_argument("--stage", type=str, default="all", choices=["1", "2", "all"])
     for name in ("audio", "audio_dir", "reason_pt", "semantic_pt", "question", "question_file", "text_file", "results", "token_dir",
@@ -441,6 +452,11 @@ def get_parser():
     p.add_argument("--seed", type=int, default=888)
     p.add_argument("--rank", type=int, default=0)
     p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="kernel precision (extension; the reference runs fp32)")
+    p.add_argument("--weight_dtype", type=str, default="none", choices=["none", "fp8_e4m3"],
+                   help="stage 1, --dtype bf16 only (extension): fp8_e4m3 replaces every Linear weight of the LM by its weight-only 8-bit form "
+                        "(OCP e4m3fn, one power-of-two scale per output row; embeddings, norms and the K/V cache stay as they are) and decode "
+                        "frames of up to 5 sequences stream the fp8 copies.  LOSSY: a weight's relative rms error is 2.7e-2 (bf16: 1.6e-3), ids "
+                        "can differ from the bf16 run.  Costs 1.5 x the bf16 weight memory.  Default none")
     p.add_argument("--save_safetensors", action="store_true",
                    help="also write {name}_tokens.safetensors next to the reference's two .pt files (extension)")
     p.add_argument("--codec_batch", type=int, default=1,

@@ -50,6 +50,56 @@ def pack_linear(weight, dtype, transposed=False, rope_head_size=0):
     return out
 
 
+def w8_exponents(weight):
+    """Per-row exponents of the fp8 weight-only contract (include/ua2hip.h): e = ceil(log2(amax / 448)) per output row of `weight`
+    [N, K], 0 for an all-zero row, clamped to [-117, 120].  Computed without a logarithm: amax = m 2^x with m in [0.5, 1) and
+    448 = 0.875 2^9.  Plain torch, any device."""
+    amax = weight.detach().float().abs().amax(dim=1)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    return e.clamp(-117, 120).to(torch.int32)
+
+
+def quant_w8(weight):
+    """(q, e): q [N, K] torch.float8_e4m3fn = RNE(weight * 2^-e), e [N] int32 — the quantiser of the fp8 contract in plain torch."""
+    e = w8_exponents(weight)
+    scaled = torch.ldexp(weight.detach().float(), -e.unsqueeze(1))
+    return scaled.to(torch.float8_e4m3fn), e
+
+
+def dequant_w8(weight):
+    """W' = q * 2^e [N, K] fp32: the weight a plan with weight_dtype=torch.float8_e4m3fn computes with in place of `weight`
+    (exactly representable in bf16).  Plain torch, any device: for tests and for looking at what the option costs."""
+    q, e = quant_w8(weight)
+    return torch.ldexp(q.float(), e.unsqueeze(1))
+
+
+def pack_linear_w8(weight, transposed=False, rope_head_size=0):
+    """nn.Linear.weight [N, K] (or [K, N] with transposed=True; K % 64 == 0) -> (q, exp, bf16_twin): the fp8 image in the decode
+    kernel's burst order (uint8), the int8 exponents in packed column order (N padded to 16) and pack_linear(W', bfloat16)
+    (ua2_pack_linear_w8)."""
+    assert weight.dim() == 2 and weight.is_cuda
+    w = weight.contiguous()
+    if w.dtype not in _CODES:
+        w = w.float()
+    N, K = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
+    n16 = (N + 15) // 16 * 16
+    q = torch.empty(max(lib.ua2_packed_bytes_w8(N, K), 1), dtype=torch.uint8, device=w.device)
+    exp = torch.empty(n16, dtype=torch.int8, device=w.device)
+    twin = torch.empty(packed_elems(torch.bfloat16, N, K), dtype=torch.bfloat16, device=w.device)
+    check(lib.ua2_pack_linear_w8(ptr(w), dtype_code(w.dtype), int(transposed), N, K, ptr(q), ptr(exp), ptr(twin), rope_head_size,
+                                 stream()), "ua2_pack_linear_w8")
+    return q, exp, twin
+
+
+def linear_w8(args, w0, w1=None):
+    """ua2_linear_w8: the launch `args` (ops.linear(..., launch=False); w0 / w1 = the bf16 twins) on the fp8 twins w0, w1 = (q, exp)."""
+    r0 = _lib.W8Ref(ptr(w0[0]), ptr(w0[1]))
+    r1 = _lib.W8Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
+    check(lib.ua2_linear_w8(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8")
+
+
 def kv_geom(k_pool, v_pool, page_table, n_head, n_kv, head_size, ring_pages=0):
     g = KvGeom()
     g.ring_pages = ring_pages
