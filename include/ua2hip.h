@@ -551,6 +551,17 @@ int ua2_reason_merge(float* out, const float* rec, const float* reason, const in
  * requires 0 < ovlp <= win - ovlp and seg_stride >= win. */
 int ua2_crossfade(float* out, const float* seg, int32_t n_seg, int64_t seg_stride, int64_t win, int64_t ovlp, int64_t target_len,
                   void* stream);
+/* Whisper log-mel front end (reason_tokenizer.py:67-72: WhisperFeatureExtractor(feature_size=80), numpy path).  wav [B, n_samples]
+ * fp32 at 16 kHz -> out [B, 80, 3000] fp32.  Per clip: truncate / zero-pad to 480 000 samples, reflect-pad 200 on both sides,
+ * frames of 400 at hop 160, periodic Hann window, power of the 201 real-DFT bins, 80 x 201 Slaney mel filter bank,
+ * log10(max(., 1e-10)), the last of the 3001 frames dropped, max(x, max over the clip - 8), (x + 4) / 4.
+ * basis [400, 402] fp32: row n = (hann[n] cos(2 pi n k / 400), k < 201 | hann[n] sin(2 pi n k / 400), k < 201); mel_fb [201, 80] fp32;
+ * both built once on the host in float64 (the kernel carries no tables).  fp32 accumulation throughout; the clip maximum is a
+ * second launch over per-workgroup maxima (no atomics): a clip's bits depend neither on scheduling nor on the batch it is in.
+ * ws: scratch of the size the _workspace_bytes function below reports for B. */
+size_t ua2_logmel_workspace_bytes(int32_t B);
+int ua2_logmel(float* out, const float* wav, int32_t B, int64_t n_samples, const float* basis, const float* mel_fb, float* ws,
+               size_t ws_bytes, void* stream);
 /* q/k LayerNorm over the head dim + partial rotary embedding + K/V append to the paged cache for the x-transformers
  * style attention of the AudioThinking encoder (modules/transformer.py:447-485, 146-170).  qkv [R, 3*n_head*hs] =
  * (q | k | v); q_out [R, n_head*hs] fp32; cos_t / sin_t [max_pos, rot_dim/2]; norm weights NULL = no q/k norm;

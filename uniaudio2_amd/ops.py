@@ -507,3 +507,47 @@ def qknorm_rope_kv(dtype, qkv, row_pos, row_seq, kv, q_out, qw=None, qb=None, kw
     check(lib.ua2_qknorm_rope_kv(dtype_code(dtype), ptr(qkv), qkv.shape[0], ptr(row_pos), ptr(row_seq), ptr(qw), ptr(qb), ptr(kw),
                                  ptr(kb), float(eps), ptr(cos), ptr(sin), rot_dim, ptr(q_out), C.byref(kv), stream()),
           "ua2_qknorm_rope_kv")
+
+
+# ---- Whisper log-mel front end -------------------------------------------------------------------
+
+LOGMEL_SAMPLES, LOGMEL_FFT, LOGMEL_HOP, LOGMEL_BINS, LOGMEL_MELS, LOGMEL_FRAMES = 480000, 400, 160, 201, 80, 3000
+_LOGMEL_TABLES = {}
+
+
+def logmel_tables_host():
+    """(basis [400, 402], mel_fb [201, 80]) float64 on the host: the windowed DFT basis and the filter bank WhisperFeatureExtractor
+    builds (periodic Hann window; mel_filter_bank(201, 80, 0, 8000, 16000, norm='slaney', mel_scale='slaney')), restated."""
+    n = torch.arange(LOGMEL_FFT, dtype=torch.float64)
+    hann = 0.5 - 0.5 * torch.cos(2 * torch.pi * n / LOGMEL_FFT)
+    k = torch.arange(LOGMEL_BINS, dtype=torch.float64)
+    ang = 2 * torch.pi * ((n[:, None] * k[None, :]) % LOGMEL_FFT) / LOGMEL_FFT      # exact integer reduction of n k mod 400
+    basis = torch.cat([hann[:, None] * torch.cos(ang), hann[:, None] * torch.sin(ang)], 1)
+    # Slaney scale: linear (200/3 Hz per mel) below 1 kHz, logarithmic (27 mels per factor 6.4) above
+    logstep = torch.log(torch.tensor(6.4, dtype=torch.float64)) / 27.0
+    to_mel = lambda f: torch.where(f >= 1000.0, 15.0 + torch.log(f.clamp(min=1e-300) / 1000.0) / logstep, 3.0 * f / 200.0)
+    to_hz = lambda m: torch.where(m >= 15.0, 1000.0 * torch.exp(logstep * (m - 15.0)), 200.0 * m / 3.0)
+    lo, hi = to_mel(torch.tensor([0.0, 8000.0], dtype=torch.float64))
+    edges = to_hz(torch.linspace(float(lo), float(hi), LOGMEL_MELS + 2, dtype=torch.float64))
+    freqs = torch.linspace(0.0, 8000.0, LOGMEL_BINS, dtype=torch.float64)
+    diff = edges[1:] - edges[:-1]
+    slopes = edges[None, :] - freqs[:, None]
+    fb = torch.minimum(-slopes[:, :-2] / diff[:-1], slopes[:, 2:] / diff[1:]).clamp(min=0.0)
+    fb = fb * (2.0 / (edges[2:] - edges[:-2]))[None, :]                                # norm='slaney'
+    return basis, fb
+
+
+def logmel(wav):
+    """wav [B, N] fp32 at 16 kHz on the device -> log-mel [B, 80, 3000] fp32 (ua2_logmel: WhisperFeatureExtractor's numpy path)."""
+    assert wav.dim() == 2 and wav.dtype == torch.float32
+    wav = wav.contiguous()
+    tabs = _LOGMEL_TABLES.get(wav.device)
+    if tabs is None:
+        basis, fb = logmel_tables_host()
+        tabs = _LOGMEL_TABLES[wav.device] = (basis.float().contiguous().to(wav.device), fb.float().contiguous().to(wav.device))
+    assert tuple(tabs[0].shape) == (LOGMEL_FFT, 2 * LOGMEL_BINS) and tuple(tabs[1].shape) == (LOGMEL_BINS, LOGMEL_MELS)
+    B, N = wav.shape
+    out = torch.empty(B, LOGMEL_MELS, LOGMEL_FRAMES, dtype=torch.float32, device=wav.device)
+    ws = torch.empty(max(lib.ua2_logmel_workspace_bytes(B) // 4, 1), dtype=torch.float32, device=wav.device)
+    check(lib.ua2_logmel(ptr(out), ptr(wav), B, N, ptr(tabs[0]), ptr(tabs[1]), ptr(ws), ws.numel() * 4, stream()), "ua2_logmel")
+    return out

@@ -11,6 +11,8 @@ Out of scope: the three frozen SSL encoders (Whisper-medium, W
 un-vendored packages).  `fetch_codes_batch` therefore takes them as an injected callable `ssl_features(input_audios,
 spectrograms) -> dict(whisper (B, Cw, T50), wavlm (B, Cl, T50), bestrq_acoustic / bestrq_semantic (B, 1024, T25))`;
 `fetch_codes_from_features` is everything after them.  The reasoning-text LLM of AudioThinking is likewise not built.
+Whisper is the exception: with a `whisper_encoder` (models/modeling_whisper.py) set, `fetch_codes_batch` computes the
+"whisper" entry itself from `spectrograms` (`get_whisper_feature` :334-343) and the callable supplies WavLM / BEST-RQ only.
 
 Randomness is explicit: the reference draws `torch.rand(B,1,1) < 0.2` inside time_film at inference time (:435)
 and `randn` latents inside inference_codes (:655); here both are arguments (defaults draw from torch's generator exactly
@@ -162,8 +164,11 @@ class AudioThinking(nn.Module):
 
 class AudioDiffusion1D(nn.Module):
     def __init__(self, num_channels=None, unet_model_config_path=None, whisper_fea_dim=1024, wavlm_fea_dim=768, codec_dim=768,
-                 encoder_depth=5, use_detokenizer=True, ssl_features: Optional[Callable] = None, device=None, **unused):
+                 encoder_depth=5, use_detokenizer=True, ssl_features: Optional[Callable] = None, device=None, whisper_encoder=None,
+                 **unused):
         super().__init__()
+        # frozen, loaded from its own checkpoint and prepared by its owner: kept out of this module's parameters / state dict
+        object.__setattr__(self, "whisper_encoder", whisper_encoder)
         self.max_t_len, self.sample_rate, self.sq_codec_latent = 30 * 50, 24000, 136
         self.whisper_fea_dim, self.wavlm_fea_dim, self.codec_dim = whisper_fea_dim, wavlm_fea_dim, codec_dim
         self.ssl_features = ssl_features
@@ -310,6 +315,16 @@ class AudioDiffusion1D(nn.Module):
         return [reason_codes], [codes], [merge]
 
     @torch.inference_mode()
+    def get_whisper_feature(self, mels, n_len, len_semantic):
+        """:334-343: mels (B, 80, 3000) -> (B, Cw, n) Whisper features, n = max(int(n_len / 24000 * 50), 2 * len_semantic) frames at
+        most (n_len: samples of the 24-kHz segment; len_semantic: frames of the BEST-RQ semantic stream)."""
+        if self.whisper_encoder is None:
+            raise NotImplementedError("get_whisper_feature needs a WhisperEncoder (AudioDiffusion1D(whisper_encoder=...))")
+        n_len = int((n_len / 24000) * 50)
+        n_len = max(n_len, len_semantic * 2)
+        return self.whisper_encoder(mels)[:, :n_len, :].transpose(1, 2)
+
+    @torch.inference_mode()
     def fetch_codes_batch(self, input_audios, spectrograms, additional_feats=None, return_reasoning_text=False, film_masks=None):
         """:493-551.  The frozen SSL encoders are the injected `ssl_features` callable (see the module docstring).  film_masks
         (3, B) bool: the three FiLM draws of this call made by the caller (ReasoningTokenizer.audio2token draws them for the
@@ -317,10 +332,18 @@ class AudioDiffusion1D(nn.Module):
         if return_reasoning_text:
             raise NotImplementedError("the reasoning-text LLM of AudioThinking is not part of the token path and is not built")
         if self.ssl_features is None:
+            if self.whisper_encoder is not None:
+                raise NotImplementedError("tokenising audio needs the frozen WavLM / BEST-RQ encoders (out of scope, SURVEY.md §2.1); "
+                                          "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
+                                          "fetch_codes_from_features")
             raise NotImplementedError("tokenising audio needs the frozen Whisper / WavLM / BEST-RQ encoders (out of scope, SURVEY.md §2.1); "
                                       "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
                                       "fetch_codes_from_features")
-        f = self.ssl_features(input_audios, spectrograms)
+        f = dict(self.ssl_features(input_audios, spectrograms))
+        if "whisper" not in f and self.whisper_encoder is not None:
+            if spectrograms is None:
+                raise ValueError("fetch_codes_batch: the Whisper encoder needs the log-mel `spectrograms` (B, 80, 3000)")
+            f["whisper"] = self.get_whisper_feature(spectrograms, input_audios.shape[-1], f["bestrq_semantic"].shape[2])
         return self.fetch_codes_from_features(f["whisper"], f["wavlm"], f["bestrq_acoustic"], f["bestrq_semantic"], film_masks=film_masks)
 
     # ---- decode side -----------------------------------------------------------------------------------------------

@@ -16,11 +16,13 @@ Mirror of the reference's tools/tokenizer/ReasoningCodec_film/reason_tokenizer.p
   * `tokenize(wav path) -> (reason (8, T_r), rec (8, T_s))` (:377-387): load, down-mix, resample to 24 kHz
     (torchaudio's windowed-sinc algorithm restated as one MFMA GEMM, `resample`), then `audio2token`
     (:86-129): tile the clip to 30-s segments (+240 samples), `model.fetch_codes_batch` per batch of 6
-    segments, crop to int(dur * 12.5) + 1 / int(dur * 5) + 1 tokens.  The frozen SSL encoders inside
-    fetch_codes_batch are an injected callable (models/AudioDiffusion1D.py); `tokenize(tensor)` passes
-    tensors through (:387-388).
+    segments, crop to int(dur * 12.5) + 1 / int(dur * 5) + 1 tokens.  The frozen WavLM / BEST-RQ encoders inside
+    fetch_codes_batch are an injected callable (models/AudioDiffusion1D.py); the Whisper branch runs on the device
+    when the model carries a `whisper_encoder`: `get_whisper_features` (:67-72) = 24 -> 16 kHz `resample` + the
+    log-mel kernel (ua2_logmel).  `tokenize(tensor)` passes tensors through (:387-388).
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -184,7 +186,10 @@ class ReasoningTokenizer:
         self.sample_rate = 24000
         self.rec_frame_rate, self.reason_frame_rate, self.sq_codec_hz = 12.5, 5, 25        # :31-33
         self.SQCodec, self.latent_fn, self.model = sq_codec, latent_fn, model
-        self.feature_extractor = feature_extractor          # Whisper log-mel front end (:67-72), out of scope: injected or None
+        # Whisper log-mel front end (:67-72): an injected callable wins; without one, a model that carries a Whisper encoder gets
+        # the device log-mel (get_whisper_features); otherwise None is handed on (the ssl_features callable's business)
+        self.feature_extractor = feature_extractor
+        self.whisper_dtype = torch.bfloat16                 # _load_released: the reference runs the encoder under bf16 autocast (:117)
         self.skip_discarded_segments = True                 # audio2token: do not encode segments whose tokens the reference slices away
         self.vq = (vq_phone, vq_semantic, vq_acoustic)
         if model is not None:
@@ -195,8 +200,9 @@ class ReasoningTokenizer:
     def _load_released(self, train_config, model_path):
         """The reference's constructor (:22-66): yaml -> SQ-Codec (sq_config yaml `generator.config`, sq_resume['codec_model'],
         scalar24k.py:423-437) + AudioDiffusion1D (transformer_diffusion_config json; model_path['model'], 'module.' prefixes
-        stripped, strict=False).  The frozen SSL encoders / Whisper front end named in the yaml are not loaded (out of scope):
-        decoding works, `tokenize(path)` needs `model.ssl_features`.  Widths of the encode side are read off the checkpoint."""
+        stripped, strict=False).  Of the frozen SSL encoders named in the yaml only Whisper is loaded, when `whisper_path` names an
+        existing directory (models/modeling_whisper.py); WavLM / BEST-RQ are not (out of scope): decoding works, `tokenize(path)`
+        needs `model.ssl_features`.  Widths of the encode side are read off the checkpoint."""
         import yaml
         from .models.AudioDiffusion1D import AudioDiffusion1D
         from .models.scalar24k import ScalarModel
@@ -228,6 +234,10 @@ class ReasoningTokenizer:
         self.model.sq_codec_latent = sq_cfg["latent_hidden_dim"]
         self.model.prepare()
         self.model.init_device_dtype(self.device, torch.float32)
+        wp = ta.get("whisper_path")
+        if wp and os.path.isdir(wp):
+            from .models.modeling_whisper import WhisperEncoder
+            object.__setattr__(self.model, "whisper_encoder", WhisperEncoder.from_pretrained(wp).to(self.device).prepare(self.whisper_dtype))
         self.vq = (model.vq_pronunciation_semantic, model.vq_structure_semantic, model.vq_acoustic)
 
     @property
@@ -235,6 +245,12 @@ class ReasoningTokenizer:
         return True
 
     # ---- audio -> tokens ---------------------------------------------------------------------------------------------
+    def get_whisper_features(self, audio, sr):
+        """:67-72: audio (B, N) fp32 on the device -> log-mel (B, 80, 3000) as WhisperFeatureExtractor computes it, on the device."""
+        if sr != 16000:
+            audio = resample(audio, sr, 16000)
+        return ops.logmel(audio.float().contiguous())
+
     @torch.no_grad()
     def audio2token(self, orig_samples, sr, return_reasoning_text=False, task_name="speech_reasoning", min_duration=30, batch_size=6):
         """:86-129.  orig_samples (1, N) at 24 kHz -> (reason (1, 8, T_r), rec (1, 8, T_s)) int64."""
@@ -274,7 +290,12 @@ class ReasoningTokenizer:
                     k = max(-(-(need_rec - have_rec) // per_rec), -(-(need_reason - have_reason) // per_reason), 1)
                 k = min(k, Bc - r)
                 rows = chunk[r:r + k]
-                mels = self.feature_extractor(rows[:, 0, :]) if self.feature_extractor is not None else None
+                if self.feature_extractor is not None:
+                    mels = self.feature_extractor(rows[:, 0, :])
+                elif getattr(self.model, "whisper_encoder", None) is not None:
+                    mels = self.get_whisper_features(rows[:, 0, :], self.sample_rate)
+                else:
+                    mels = None
                 reasoning_codes, rec_codes, _ = self.model.fetch_codes_batch(rows, mels, additional_feats=[], return_reasoning_text=return_reasoning_text,
                                                                             film_masks=[m[r:r + k] for m in masks])
                 rc, mc = torch.cat(reasoning_codes, 1), torch.cat(rec_codes, 1)
