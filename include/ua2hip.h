@@ -562,6 +562,32 @@ int ua2_crossfade(float* out, const float* seg, int32_t n_seg, int64_t seg_strid
 size_t ua2_logmel_workspace_bytes(int32_t B);
 int ua2_logmel(float* out, const float* wav, int32_t B, int64_t n_samples, const float* basis, const float* mel_fb, float* ws,
                size_t ws_bytes, void* stream);
+/* ---- BEST-RQ (MusicFM 25 Hz) encoder: modules/our_MERT_BESTRQ/mert_fairseq/models/musicfm/ (entry points added under ABI v10) ----
+ * ua2_conv2d: nn.Conv2d(kernel 3 x 3, padding 1, stride (stride_f, stride_t), each 1 or 2) of the stem's Res2dModule (modules/conv.py:
+ * 20-42), exact fp32 on the f32 matrix pipe (the arithmetic class of ua2_conv1d precision 0), with the epilogue
+ *     y = act( conv(x) + bias (+ residual) ),   act 0 = none, 1 = ReLU.
+ * x [B, Cin, F, T] fp32, y and residual [B, Cout, Fo, To] fp32 with Fo = (F - 1) / stride_f + 1, To = (T - 1) / stride_t + 1.
+ * Eval-mode BatchNorm2d is folded by the caller: w' = w g / sqrt(var + eps), b' = (b - mean) g / sqrt(var + eps) + beta.
+ * w: for Cin > 4 the filter as ua2_pack_linear(fp32) of the [Cout, G * 9 * 16] matrix whose reduction index is (group of 16 input
+ * channels, tap kf * 3 + kt, channel in the group), Cin zero-padded to 16 G (host helper ops.pack_conv2d_weight); for Cin <= 4 (the
+ * first layer, Cin = 1) the plain [Cout, Cin, 3, 3] fp32 filter, summed as one fma chain.  Any F, T, Cin, Cout (partial tiles are
+ * masked, never mis-tiled); every load index is clamped into the buffer and the zero padding is a select on the loaded value.  A clip's
+ * output does not depend on the batch it is in. */
+int ua2_conv2d(const float* x, const void* w, const float* bias, const float* residual, float* y, int32_t B, int32_t Cin, int32_t Cout,
+               int32_t F, int32_t T, int32_t stride_f, int32_t stride_t, int32_t act, void* stream);
+/* LayerNorm + the conformer's rotary step (transformers Wav2Vec2ConformerSelfAttention._apply_rotary_embedding: the LayerNorm-ed
+ * hidden states are rotated BEFORE linear_q / linear_k, linear_v reads them un-rotated).  out [R, 2 C]: columns [0, C) =
+ * n cos + rotate_half(n) sin per head of head_size (rotate_half = (-second half, first half)), columns [C, 2 C) = n, with
+ * n = F.layer_norm(x[r]) * w + b (the sums of ua2_layernorm_rows).  cos_t / sin_t [n_pos, head_size] fp32 = cos / sin of
+ * cat(freqs, freqs), built on the host; row r uses table row row_pos[r] (clamped to n_pos - 1).  C % head_size == 0, C <= 8192. */
+int ua2_layernorm_rope_rows(float* out, const float* x, const float* w, const float* b, const float* cos_t, const float* sin_t,
+                            const int32_t* row_pos, int32_t n_pos, int64_t R, int32_t C, int32_t head_size, float eps, void* stream);
+/* Tail of the MusicFM mel front end (modules/features.py MelSTFT(is_db=True), musicfm_25hz.py:199-233): spec [B * T, ld] fp32 holds per
+ * frame the real parts of the n_bins DFT bins in columns [0, n_bins) and the imaginary parts in [n_bins, 2 n_bins) (a ua2_linear
+ * product of the frames with the windowed basis); out[b][m][t] = (10 log10(max(sum_k (re^2 + im^2) mel_fb[k][m], 1e-10)) - mean) / std.
+ * mel_fb [n_bins, n_mels] fp32 (torchaudio melscale_fbanks, htk, norm None), built on the host.  fp32 throughout. */
+int ua2_melspec_db(float* out, const float* spec, const float* mel_fb, int32_t B, int32_t T, int32_t n_bins, int32_t n_mels, int32_t ld,
+                   float mean, float stdv, void* stream);
 /* q/k LayerNorm over the head dim + partial rotary embedding + K/V append to the paged cache for the x-transformers
  * style attention of the AudioThinking encoder (modules/transformer.py:447-485, 146-170).  qkv [R, 3*n_head*hs] =
  * (q | k | v); q_out [R, n_head*hs] fp32; cos_t / sin_t [max_pos, rot_dim/2]; norm weights NULL = no q/k norm;

@@ -551,3 +551,107 @@ def logmel(wav):
     ws = torch.empty(max(lib.ua2_logmel_workspace_bytes(B) // 4, 1), dtype=torch.float32, device=wav.device)
     check(lib.ua2_logmel(ptr(out), ptr(wav), B, N, ptr(tabs[0]), ptr(tabs[1]), ptr(ws), ws.numel() * 4, stream()), "ua2_logmel")
     return out
+
+
+# ---- BEST-RQ (MusicFM 25 Hz) encoder: 2-D convolution stem, LayerNorm + rotary rows, mel front end -------------------
+
+CONV2D_SMALL_CIN = 4          # ua2_conv2d: up to this many input channels the filter stays plain and one thread forms an output
+
+
+def pack_conv2d_weight(w):
+    """nn.Conv2d weight [Cout, Cin, 3, 3] fp32 -> the buffer ua2_conv2d takes: for Cin > 4 ua2_pack_linear(fp32) of the
+    [Cout, G * 9 * 16] matrix with reduction index (group of 16 channels, tap, channel in group), Cin zero-padded to 16 G; for
+    Cin <= 4 the plain filter."""
+    Cout, Cin, kf, kt = w.shape
+    assert (kf, kt) == (3, 3) and w.is_cuda
+    w = w.detach().float().contiguous()
+    if Cin <= CONV2D_SMALL_CIN:
+        return w
+    G = (Cin + 15) // 16
+    wp = torch.zeros(Cout, G * 16, 9, dtype=torch.float32, device=w.device)
+    wp[:, :Cin] = w.view(Cout, Cin, 9)
+    wk = wp.view(Cout, G, 16, 9).permute(0, 1, 3, 2).reshape(Cout, G * 9 * 16).contiguous()
+    return pack_linear(wk, torch.float32)
+
+
+def conv2d(x, w_packed, Cout, *, stride=(1, 1), bias=None, residual=None, relu=False):
+    """x [B, Cin, F, T] fp32 -> relu?(conv3x3(x, padding 1, stride) + bias (+ residual)) [B, Cout, Fo, To] (ua2_conv2d, exact fp32);
+    w_packed = pack_conv2d_weight(filter)."""
+    B, Cin, F, T = x.shape
+    Fo, To = (F - 1) // stride[0] + 1, (T - 1) // stride[1] + 1
+    y = torch.empty(B, Cout, Fo, To, dtype=torch.float32, device=x.device)
+    if residual is not None:
+        assert tuple(residual.shape) == (B, Cout, Fo, To)
+    check(lib.ua2_conv2d(ptr(x), ptr(w_packed), ptr(bias), ptr(residual), ptr(y), B, Cin, Cout, F, T, int(stride[0]), int(stride[1]),
+                         int(bool(relu)), stream()), "ua2_conv2d")
+    return y
+
+
+def layernorm_rope_rows(x, w, b, eps, cos, sin, row_pos, head_size):
+    """x [R, C] -> [R, 2 C] = [rotate(LN(x)) | LN(x)] (ua2_layernorm_rope_rows); cos / sin [n_pos, head_size], row_pos [R] int32."""
+    R, Cc = x.shape
+    assert cos.shape == sin.shape and cos.shape[1] == head_size and row_pos.numel() == R and row_pos.dtype == torch.int32
+    out = torch.empty(R, 2 * Cc, dtype=torch.float32, device=x.device)
+    check(lib.ua2_layernorm_rope_rows(ptr(out), ptr(x), ptr(w), ptr(b), ptr(cos), ptr(sin), ptr(row_pos), cos.shape[0], R, Cc, head_size,
+                                      float(eps), stream()), "ua2_layernorm_rope_rows")
+    return out
+
+
+MEL_SR, MEL_FFT, MEL_HOP, MEL_BINS, MEL_MELS, MEL_CUT = 24000, 2048, 240, 1025, 128, 960
+MEL_MEAN, MEL_STD = 6.768444971712967, 18.417922652295623       # melspec_2048 statistics of musicfm_25hz.py:80
+_MEL_TABLES = {}
+
+
+def melspec_tables_host(n_mels=MEL_MELS):
+    """(basis [2048, 2050], mel_fb [1025, n_mels]) float64 on the host: the periodic-Hann-windowed cos | sin basis of the 2048-point
+    DFT and torchaudio's melscale_fbanks(1025, 0, 12000, n_mels, 24000, norm=None, mel_scale='htk'), restated."""
+    n = torch.arange(MEL_FFT, dtype=torch.float64)
+    hann = 0.5 - 0.5 * torch.cos(2 * torch.pi * n / MEL_FFT)
+    k = torch.arange(MEL_BINS, dtype=torch.float64)
+    ang = 2 * torch.pi * ((n[:, None] * k[None, :]) % MEL_FFT) / MEL_FFT              # exact integer reduction of n k mod 2048
+    basis = torch.cat([hann[:, None] * torch.cos(ang), hann[:, None] * torch.sin(ang)], 1)
+    freqs = torch.linspace(0.0, MEL_SR // 2, MEL_BINS, dtype=torch.float64)
+    m_max = 2595.0 * torch.log10(torch.tensor(1.0 + (MEL_SR / 2) / 700.0, dtype=torch.float64))
+    m_pts = torch.linspace(0.0, float(m_max), n_mels + 2, dtype=torch.float64)
+    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - freqs[:, None]
+    fb = torch.minimum(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]).clamp(min=0.0)
+    return basis, fb
+
+
+def mel_frames(wav):
+    """wav [B, N] -> ([B * T, 2048] frames, T): cut to a multiple of 960 samples (musicfm_model.py:78), reflect-pad 1024 on both
+    sides (center=True), frames of 2048 at hop 240, the last of the T + 1 dropped ([..., :-1]).  Data movement only."""
+    B, N = wav.shape
+    n = N // MEL_CUT * MEL_CUT
+    if n <= MEL_FFT // 2:
+        raise ValueError(f"melspec: {N} samples; the reflection of center=True needs more than {MEL_FFT // 2} after the cut to a multiple of {MEL_CUT}")
+    x = wav[:, :n]
+    h = MEL_FFT // 2
+    x = torch.cat([x[:, 1:h + 1].flip(1), x, x[:, -h - 1:-1].flip(1)], 1)
+    T = n // MEL_HOP
+    return x.unfold(1, MEL_FFT, MEL_HOP)[:, :T].reshape(B * T, MEL_FFT).contiguous(), T
+
+
+def melspec(wav, n_mels=MEL_MELS):
+    """wav [B, N] fp32 at 24 kHz on the device -> normalised dB mel spectrogram [B, n_mels, T] fp32, T = (N // 960) * 4: MusicFM's
+    MelSTFT(n_fft 2048, hop 240, is_db) + [..., :-1] + (x - mean) / std, as an exact-fp32 ua2_linear against the windowed DFT basis
+    followed by ua2_melspec_db."""
+    assert wav.dim() == 2 and wav.dtype == torch.float32 and wav.is_cuda
+    tabs = _MEL_TABLES.get((wav.device, n_mels))
+    if tabs is None:
+        basis, fb = melspec_tables_host(n_mels)
+        n_pad = (2 * MEL_BINS + 15) // 16 * 16
+        wmat = torch.zeros(n_pad, MEL_FFT, dtype=torch.float32)
+        wmat[:2 * MEL_BINS] = basis.t().float()
+        tabs = _MEL_TABLES[(wav.device, n_mels)] = (pack_linear(wmat.to(wav.device), torch.float32), fb.float().contiguous().to(wav.device), n_pad)
+    wpk, fb, n_pad = tabs
+    frames, T = mel_frames(wav.contiguous())
+    B, M = wav.shape[0], frames.shape[0]
+    spec = torch.empty(M, n_pad, dtype=torch.float32, device=wav.device)
+    ws = linear_workspace(torch.float32, M, MEL_FFT, wav.device) if M > 16 else None
+    linear(dtype=torch.float32, M=M, N=n_pad, K=MEL_FFT, w0=wpk, x=frames, ldx=MEL_FFT, y=spec, ldy=n_pad, workspace=ws)
+    out = torch.empty(B, n_mels, T, dtype=torch.float32, device=wav.device)
+    check(lib.ua2_melspec_db(ptr(out), ptr(spec), ptr(fb), B, T, MEL_BINS, n_mels, n_pad, MEL_MEAN, MEL_STD, stream()), "ua2_melspec_db")
+    return out

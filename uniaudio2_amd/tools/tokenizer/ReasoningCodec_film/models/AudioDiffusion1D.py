@@ -13,6 +13,8 @@ spectrograms) -> dict(whisper (B, Cw, T50), wavlm (B, Cl, T50), bestrq_acoustic 
 `fetch_codes_from_features` is everything after them.  The reasoning-text LLM of AudioThinking is likewise not built.
 Whisper is the exception: with a `whisper_encoder` (models/modeling_whisper.py) set, `fetch_codes_batch` computes the
 "whisper" entry itself from `spectrograms` (`get_whisper_feature` :334-343) and the callable supplies WavLM / BEST-RQ only.
+BEST-RQ likewise: with a `bestrq_encoder` (models/PretrainedModel.py `BESTRQ_Model`) set, `bestrq_acoustic` / `bestrq_semantic` come
+from `extract_continous_embeds_multiple(input_audios)` (:503) unless the callable supplies them; WavLM is then the one encoder injected.
 
 Randomness is explicit: the reference draws `torch.rand(B,1,1) < 0.2` inside time_film at inference time (:435)
 and `randn` latents inside inference_codes (:655); here both are arguments (defaults draw from torch's generator exactly
@@ -165,10 +167,11 @@ class AudioThinking(nn.Module):
 class AudioDiffusion1D(nn.Module):
     def __init__(self, num_channels=None, unet_model_config_path=None, whisper_fea_dim=1024, wavlm_fea_dim=768, codec_dim=768,
                  encoder_depth=5, use_detokenizer=True, ssl_features: Optional[Callable] = None, device=None, whisper_encoder=None,
-                 **unused):
+                 bestrq_encoder=None, **unused):
         super().__init__()
         # frozen, loaded from its own checkpoint and prepared by its owner: kept out of this module's parameters / state dict
         object.__setattr__(self, "whisper_encoder", whisper_encoder)
+        object.__setattr__(self, "bestrq_encoder", bestrq_encoder)
         self.max_t_len, self.sample_rate, self.sq_codec_latent = 30 * 50, 24000, 136
         self.whisper_fea_dim, self.wavlm_fea_dim, self.codec_dim = whisper_fea_dim, wavlm_fea_dim, codec_dim
         self.ssl_features = ssl_features
@@ -332,6 +335,11 @@ class AudioDiffusion1D(nn.Module):
         if return_reasoning_text:
             raise NotImplementedError("the reasoning-text LLM of AudioThinking is not part of the token path and is not built")
         if self.ssl_features is None:
+            if self.bestrq_encoder is not None:
+                missing = "WavLM encoder" if self.whisper_encoder is not None else "Whisper / WavLM encoders"
+                raise NotImplementedError(f"tokenising audio needs the frozen {missing} (out of scope, SURVEY.md §2.1); "
+                                          "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
+                                          "fetch_codes_from_features")
             if self.whisper_encoder is not None:
                 raise NotImplementedError("tokenising audio needs the frozen WavLM / BEST-RQ encoders (out of scope, SURVEY.md §2.1); "
                                           "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
@@ -340,6 +348,8 @@ class AudioDiffusion1D(nn.Module):
                                       "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
                                       "fetch_codes_from_features")
         f = dict(self.ssl_features(input_audios, spectrograms))
+        if self.bestrq_encoder is not None and ("bestrq_acoustic" not in f or "bestrq_semantic" not in f):
+            f["bestrq_acoustic"], f["bestrq_semantic"] = self.bestrq_encoder.extract_continous_embeds_multiple(input_audios)      # :503
         if "whisper" not in f and self.whisper_encoder is not None:
             if spectrograms is None:
                 raise ValueError("fetch_codes_batch: the Whisper encoder needs the log-mel `spectrograms` (B, 80, 3000)")

@@ -190,6 +190,7 @@ class ReasoningTokenizer:
         # the device log-mel (get_whisper_features); otherwise None is handed on (the ssl_features callable's business)
         self.feature_extractor = feature_extractor
         self.whisper_dtype = torch.bfloat16                 # _load_released: the reference runs the encoder under bf16 autocast (:117)
+        self.bestrq_dtype = torch.float32                   # the reference runs BEST-RQ with autocast disabled (AudioDiffusion1D.py:502); bfloat16 = opt-in speed plan
         self.skip_discarded_segments = True                 # audio2token: do not encode segments whose tokens the reference slices away
         self.vq = (vq_phone, vq_semantic, vq_acoustic)
         if model is not None:
@@ -200,9 +201,10 @@ class ReasoningTokenizer:
     def _load_released(self, train_config, model_path):
         """The reference's constructor (:22-66): yaml -> SQ-Codec (sq_config yaml `generator.config`, sq_resume['codec_model'],
         scalar24k.py:423-437) + AudioDiffusion1D (transformer_diffusion_config json; model_path['model'], 'module.' prefixes
-        stripped, strict=False).  Of the frozen SSL encoders named in the yaml only Whisper is loaded, when `whisper_path` names an
-        existing directory (models/modeling_whisper.py); WavLM / BEST-RQ are not (out of scope): decoding works, `tokenize(path)`
-        needs `model.ssl_features`.  Widths of the encode side are read off the checkpoint."""
+        stripped, strict=False).  Of the frozen SSL encoders named in the yaml Whisper is loaded when `whisper_path` names an
+        existing directory (models/modeling_whisper.py) and BEST-RQ when its entry names an existing checkpoint file
+        (`bestrq_checkpoint`; models/PretrainedModel.py); WavLM is not (out of scope): decoding works, `tokenize(path)`
+        needs `model.ssl_features` for the WavLM features.  Widths of the encode side are read off the checkpoint."""
         import yaml
         from .models.AudioDiffusion1D import AudioDiffusion1D
         from .models.scalar24k import ScalarModel
@@ -238,7 +240,23 @@ class ReasoningTokenizer:
         if wp and os.path.isdir(wp):
             from .models.modeling_whisper import WhisperEncoder
             object.__setattr__(self.model, "whisper_encoder", WhisperEncoder.from_pretrained(wp).to(self.device).prepare(self.whisper_dtype))
+        self._load_bestrq(ta)
         self.vq = (model.vq_pronunciation_semantic, model.vq_structure_semantic, model.vq_acoustic)
+
+    def _load_bestrq(self, ta):
+        """AudioDiffusion1D.py:237-238: BESTRQ_Model(checkpoint_dir=best_rq_ckpt, layers = [4, 11]) — hidden_states[4] is the acoustic
+        stream, [11] the semantic one — set on the model when the yaml names an existing checkpoint file."""
+        bp = self.bestrq_checkpoint(ta)
+        if bp:
+            from .models import PretrainedModel
+            object.__setattr__(self.model, "bestrq_encoder",
+                               PretrainedModel.BESTRQ_Model(checkpoint_dir=bp, layers=(4, 11), device=self.device, dtype=self.bestrq_dtype))
+
+    @staticmethod
+    def bestrq_checkpoint(ta):
+        """The BEST-RQ checkpoint the yaml names (`best_rq_ckpt`, :47 -> BESTRQ_Model(checkpoint_dir=...)) when it is an existing file, else None."""
+        p = ta.get("best_rq_ckpt")
+        return p if p and os.path.isfile(p) else None
 
     @property
     def is_discrete(self):
