@@ -588,6 +588,47 @@ int ua2_layernorm_rope_rows(float* out, const float* x, const float* w, const fl
  * mel_fb [n_bins, n_mels] fp32 (torchaudio melscale_fbanks, htk, norm None), built on the host.  fp32 throughout. */
 int ua2_melspec_db(float* out, const float* spec, const float* mel_fb, int32_t B, int32_t T, int32_t n_bins, int32_t n_mels, int32_t ld,
                    float mean, float stdv, void* stream);
+/* ---- WavLM encoder: transformers WavLMModel, base architecture (feat_extract_norm "group", post-norm layers, gated relative-position
+ * bias), as AudioDiffusion1D.py:355-366 calls it (entry points added under ABI v10) ----
+ * First feature-extractor layer: Conv1d(1 -> C, kernel K, stride, no bias) + GroupNorm(num_groups = C) + exact-erf GELU.
+ * x [B, N] fp32, w [C, K] fp32, y [B, T0, C] fp32 TIME-MAJOR with T0 = (N - K) / stride + 1:
+ *     y[b][t][c] = gelu((conv[b][t][c] - mean[b][c]) * rsqrt(var[b][c] + eps) * gn_w[c] + gn_b[c]),
+ * conv = one fp32 fma chain over the taps in ascending order, mean / var (biased) over the T0 frames of clip b.  The statistics are
+ * sums and sums of squares in double over fixed chunks of 256 frames (a constant of the kernel: independent of B and of the grid),
+ * the chunks added in chunk order in double; a single frame has variance exactly 0.  Three launches; 16-byte stores along C.
+ * C % 4 == 0, K <= 16, stride <= 32.  ws: 8-byte aligned scratch of the size the _workspace_bytes function reports. */
+size_t ua2_wavlm_conv0_workspace_bytes(int32_t B, int64_t N, int32_t C, int32_t K, int32_t stride);
+int ua2_wavlm_conv0(float* y, const float* x, const float* w, const float* gn_w, const float* gn_b, int32_t B, int64_t N, int32_t C,
+                    int32_t K, int32_t stride, float eps, void* ws, size_t ws_bytes, void* stream);
+/* Grouped 1-D convolution over time-major rows (WavLMPositionalConvEmbedding: k 128, 16 groups, padding 64, the last step of an
+ * even kernel dropped by WavLMSamePadLayer):
+ *     y[b][t][co] = resid[b][t][co] + act( bias[co] + sum_{k, ci} W[co][ci][k] * x[b][t + k - K / 2][group(co) * C / groups + ci] ),
+ * x beyond both ends = 0, T outputs for T inputs (odd and even K), act 0 = none, 1 = exact-erf GELU, bias and resid optional.
+ * x, y, resid [B * T, C] fp32.  Exact fp32 on the f32 matrix pipe (the arithmetic class of ua2_conv1d precision 0).
+ * w: ua2_pack_linear(fp32) of the [C, K * C / groups] matrix whose reduction index is (tap, channel in the group) (host helper
+ * ops.pack_conv1d_grouped_weight); weight norm is folded by the caller.  The reduction runs in ascending index order: the order of
+ * summation is a function of (C, groups, K) only.  (C / groups) % 16 == 0 is required (an error otherwise); any T, also T < K / 2.
+ * Every load index is clamped into the buffer and the zero padding is a select on the loaded value. */
+int ua2_conv1d_grouped(float* y, const float* x, const void* w, const float* bias, const float* resid, int32_t B, int32_t T, int32_t C,
+                       int32_t groups, int32_t K, int32_t act, void* stream);
+/* Gate of WavLM's gated relative-position bias (WavLMAttention: gru_rel_pos_linear Linear(head_size, 8), gru_rel_pos_const).
+ * h [R, n_head * head_size] fp32 = the layer's input rows, w [8, head_size], b [8], c [n_head]; g [R, n_head] fp32:
+ *     p = w h[r, head] + b;  a = sigmoid(p0 + p1 + p2 + p3);  bb = sigmoid(p4 + p5 + p6 + p7);  g = a (bb c[head] - 1) + 2.
+ * One fma chain per projection, dims ascending; head_size % 4 == 0, <= 128. */
+int ua2_relpos_gate(float* g, const float* h, const float* w, const float* b, const float* c, int64_t R, int32_t n_head, int32_t head_size,
+                    void* stream);
+/* Dense attention with the gated relative-position bias over the paged K/V of `a` (n_head == n_kv, head size 64 or 128): row r attends
+ * keys 0 .. a->row_pos[r] with
+ *     score = q . k + gate[r][h] * rel_tab[h][clamp(kpos - q_pos[r] + tab_half, 0, 2 tab_half)]
+ * (q arrives scaled by head_size^-0.5, as WavLM scales it), online softmax, normalised fp32 output to a->y and / or a->y_packed.
+ * rel_tab [n_head, 2 tab_half + 1] fp32: entry d + tab_half holds the bias of relative position d = key - query (built on the host from
+ * rel_attn_embed by the transformers bucket rule); gate [R, n_head] from the gate entry point above; q_pos [R] int32.
+ * dtype UA2_BF16 needs the row groups of ua2_attn_args and runs the MFMA flash form (bf16 K/V, fp32-grade q and softmax, LDS-staged
+ * 64-key pages combined in page order, the head's table row staged in LDS once per workgroup, the bias added to the fp32 score tile
+ * before the running maximum; group_q_tiles 4 or 8 at head size 64, 4 at 128); a row's result does not depend on the grouping.
+ * dtype UA2_F32 is the parity form: row by row, the arithmetic of ua2_attn's fp32 kernel plus the bias term (with an all-zero table:
+ * its bits). */
+int ua2_attn_relbias(const ua2_attn_args* a, const int32_t* q_pos, const float* gate, const float* rel_tab, int32_t tab_half, void* stream);
 /* q/k LayerNorm over the head dim + partial rotary embedding + K/V append to the paged cache for the x-transformers
  * style attention of the AudioThinking encoder (modules/transformer.py:447-485, 146-170).  qkv [R, 3*n_head*hs] =
  * (q | k | v); q_out [R, n_head*hs] fp32; cos_t / sin_t [max_pos, rot_dim/2]; norm weights NULL = no q/k norm;

@@ -150,6 +150,11 @@ _EXPORTS = {
     "ua2_conv2d": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "ua2_layernorm_rope_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i32, i64, i32, i32, f32, vp]),
     "ua2_melspec_db": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
+    "ua2_wavlm_conv0_workspace_bytes": (C.c_size_t, [i32, i64, i32, i32, i32]),
+    "ua2_wavlm_conv0": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, f32, vp, C.c_size_t, vp]),
+    "ua2_conv1d_grouped": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "ua2_relpos_gate": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "ua2_attn_relbias": (C.c_int, [C.POINTER(AttnArgs), vp, vp, vp, i32, vp]),
     "ua2_ngram_filter": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "ua2_qknorm_rope_kv": (C.c_int, [C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, C.POINTER(KvGeom), vp]),
     "ua2_stage3_scratch_floats": (C.c_size_t, [C.POINTER(Stage3Desc)]),

@@ -20,10 +20,14 @@ Differences, all explicit:
     method: AttributeError); the caption / understanding / s2t tasks ignore the flag, as the reference does.  --decode_type
     beamsearch raises NotImplementedError (the reference's beam search is dead code); so does any non-greedy
     --decode_type for the generation tasks.
-  * Encoding raw audio (--audio / --audio_dir) needs the codec's frozen SSL encoders (Whisper, WavLM, BEST-RQ), which are
-    out of scope: it raises with that message; pre-tokenised `--reason_pt/--semantic_pt/--token_dir`
-    inputs work.  Stage 2 (tokens -> wav: RVQ look-ups, flow-matching DiT, SQ-Codec) runs on the device; wav files are
-    written with scipy (16-bit PCM) because torchaudio is not a dependency.
+  * Encoding raw audio (--audio / --audio_dir; the understanding tasks and the speech_s2s source) runs the codec's three frozen
+    SSL encoders (Whisper, WavLM, BEST-RQ) on the device when the codec yaml (--codec_config) names all three checkpoints
+    (`whisper_path`, `wav_lm_path`, `best_rq_ckpt`): `tokenize(path)`, the `{name}_reason.pt` / `{name}_semantic.pt` pair written to
+    --output_dir as the reference's _encode_audio_to_tokens does (:124-150, without its discarded 10-step decode), then as for
+    --token_dir.  With an encoder missing it raises NotImplementedError naming it; pre-tokenised
+    `--reason_pt/--semantic_pt/--token_dir` inputs always work.  The codec is loaded after the LLM and stays loaded (the reference
+    loads it first and unloads it).  Stage 2 (tokens -> wav: RVQ look-ups, flow-matching DiT, SQ-Codec) runs on the device; wav
+    files are written with scipy (16-bit PCM) because torchaudio is not a dependency.
 """
 import argparse
 import glob
@@ -174,13 +178,50 @@ def _check_understanding_decode(args, task):
                          "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")
 
 
+def _has_raw_audio(args):
+    return bool((args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)))
+
+
+SSL_ENCODERS = (("Whisper", "whisper_encoder", "whisper_path"), ("WavLM", "wavlm_encoder", "wav_lm_path"), ("BEST-RQ", "bestrq_encoder", "best_rq_ckpt"))
+
+
+def _encode_audio_to_tokens(args, generator, out_dir, alternative):
+    """multi_task_inference.py:124-150: --audio / --audio_dir -> `{name}_reason.pt` / `{name}_semantic.pt` in out_dir through the
+    generator's audio tokenizer (created from --codec_config on first use); returns (out_dir, names).  The tokenizer must carry the
+    three frozen SSL encoders; otherwise NotImplementedError names the ones its yaml did not provide."""
+    tok = getattr(generator, "_audio_tokenizer", None)
+    if tok is None and getattr(args, "codec_config", None):
+        tok = generator._audio_tokenizer = _load_codec(args, generator.device)
+    model = getattr(tok, "model", None)
+    missing = [f"{name} (yaml key {key})" for name, attr, key in SSL_ENCODERS if getattr(model, attr, None) is None]
+    if getattr(model, "ssl_features", None) is not None:          # an injected callable stands in for whatever is missing
+        missing = []
+    if tok is None or missing:
+        raise NotImplementedError("encoding raw audio needs the codec's frozen SSL encoders (out of scope, SURVEY.md §8f); "
+                                  f"{alternative} — not provided by the codec yaml: {', '.join(missing)}")
+    if args.audio and os.path.isfile(args.audio):
+        audio_list = [(os.path.splitext(os.path.basename(args.audio))[0], args.audio)]
+    else:
+        audio_list = [(os.path.splitext(os.path.basename(p))[0], p) for p in sorted(glob.glob(os.path.join(args.audio_dir, "*.wav")))]
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for name, path in audio_list:
+        with torch.no_grad():
+            reason, rec = tok.tokenize(path, return_reasoning_text=False)
+        torch.save(reason.cpu(), os.path.join(out_dir, f"{name}_reason.pt"))
+        torch.save(rec.cpu(), os.path.join(out_dir, f"{name}_semantic.pt"))
+        names.append(name)
+        print(f"[Encode] {path} -> {name}_reason.pt, {name}_semantic.pt")
+    return out_dir, names
+
+
 def run_understanding(args):
     task = args.task.strip().lower()
     _check_understanding_decode(args, task)
-    if (args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)):
-        raise NotImplementedError("encoding raw audio needs the codec's frozen SSL encoders (out of scope, SURVEY.md §8f); "
-                                  "pass --reason_pt + --semantic_pt or --token_dir")
-    if args.reason_pt and args.semantic_pt and os.path.isfile(args.reason_pt) and os.path.isfile(args.semantic_pt):
+    raw_audio = _has_raw_audio(args)
+    if raw_audio:
+        token_dir, names = args.output_dir, []
+    elif args.reason_pt and args.semantic_pt and os.path.isfile(args.reason_pt) and os.path.isfile(args.semantic_pt):
         token_dir = os.path.dirname(args.reason_pt) or "."
         names = [os.path.basename(args.reason_pt).replace("_reason.pt", "")]
     elif args.token_dir and os.path.isdir(args.token_dir):
@@ -192,6 +233,8 @@ def run_understanding(args):
     generator = _get_generator_class(task)(model, train_args, audio_tokenizer_config=args.audio_tokenizer_config,
                                            audio_model_path=args.audio_model_path, text_tokenizer_path=args.text_tokenizer_path,
                                            is_cfg=args.use_cfg)
+    if raw_audio:
+        token_dir, names = _encode_audio_to_tokens(args, generator, args.output_dir, "pass --reason_pt + --semantic_pt or --token_dir")
     task_prompt = _get_prompt_tensor(args, generator._text_tokenizer, args.task)
     results_path = args.results or os.path.join(args.output_dir, f"{task}_results.txt")
     os.makedirs(os.path.dirname(results_path) or ".", exist_ok=True)
@@ -316,15 +359,17 @@ def _run_speech_s2s(args, generator, task_prompt):
     import glob
     from . import parallel
     from .evaluation.speech_s2s import S2S_KEYS, S2S_TYPES
-    if (args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)):
-        raise NotImplementedError("encoding raw audio needs the codec's frozen SSL encoders (out of scope, SURVEY.md §8f); "
-                                  "pass --token_dir with the source *_reason.pt / *_semantic.pt")
-    if not (args.token_dir and os.path.isdir(args.token_dir)):
+    if _has_raw_audio(args):                                                  # :425-434: the sources go to <output_dir>/source
+        source_dir, names = _encode_audio_to_tokens(args, generator, os.path.join(args.output_dir, "source"),
+                                                    "pass --token_dir with the source *_reason.pt / *_semantic.pt")
+    elif args.token_dir and os.path.isdir(args.token_dir):
+        source_dir = args.token_dir
+        names = [os.path.basename(p).replace("_reason.pt", "") for p in sorted(glob.glob(os.path.join(args.token_dir, "*_reason.pt")))]
+    else:
         raise ValueError("speech_s2s requires --audio, --audio_dir, or --token_dir (source reason/semantic .pt).")
-    names = [os.path.basename(p).replace("_reason.pt", "") for p in sorted(glob.glob(os.path.join(args.token_dir, "*_reason.pt")))]
     items = []
     for name in names:
-        rp, sp = os.path.join(args.token_dir, f"{name}_reason.pt"), os.path.join(args.token_dir, f"{name}_semantic.pt")
+        rp, sp = os.path.join(source_dir, f"{name}_reason.pt"), os.path.join(source_dir, f"{name}_semantic.pt")
         if not os.path.isfile(sp):
             print(f"[Skip] {name}: missing source {rp} or {sp}")
             continue

@@ -655,3 +655,62 @@ def melspec(wav, n_mels=MEL_MELS):
     out = torch.empty(B, n_mels, T, dtype=torch.float32, device=wav.device)
     check(lib.ua2_melspec_db(ptr(out), ptr(spec), ptr(fb), B, T, MEL_BINS, n_mels, n_pad, MEL_MEAN, MEL_STD, stream()), "ua2_melspec_db")
     return out
+
+
+# ---- WavLM encoder: first conv layer, grouped positional conv, gated relative-position bias ------------------------------
+
+def wavlm_conv0(x, w, gn_w, gn_b, stride, eps=1e-5):
+    """x [B, N] fp32, w [C, K] -> gelu(GroupNorm_{groups = C}(conv1d(x, w, stride))) as [B, T0, C] time-major rows (ua2_wavlm_conv0)."""
+    assert x.dim() == 2 and x.dtype == torch.float32 and w.dim() == 2
+    B, N = x.shape
+    Cc, K = w.shape
+    n = lib.ua2_wavlm_conv0_workspace_bytes(B, N, Cc, K, int(stride))
+    ws = torch.empty(max(n // 8, 1), dtype=torch.float64, device=x.device)
+    T0 = (N - K) // int(stride) + 1 if N >= K else 0
+    y = torch.empty(B, max(T0, 0), Cc, dtype=torch.float32, device=x.device)
+    check(lib.ua2_wavlm_conv0(ptr(y), ptr(x.contiguous()), ptr(w.contiguous()), ptr(gn_w), ptr(gn_b), B, N, Cc, K, int(stride), float(eps),
+                              ptr(ws), ws.numel() * 8, stream()), "ua2_wavlm_conv0")
+    return y
+
+
+def pack_conv1d_grouped_weight(w, groups):
+    """nn.Conv1d(C, C, K, groups) weight [C, C / groups, K] fp32 (weight norm folded) -> the buffer ua2_conv1d_grouped takes:
+    ua2_pack_linear(fp32) of the [C, K * C / groups] matrix with reduction index (tap, channel in the group)."""
+    Cc, Cg, K = w.shape
+    assert w.is_cuda and Cc % groups == 0 and Cg == Cc // groups
+    wk = w.detach().float().permute(0, 2, 1).reshape(Cc, K * Cg).contiguous()
+    return pack_linear(wk, torch.float32)
+
+
+def conv1d_grouped(x, w_packed, B, T, groups, K, *, bias=None, resid=None, gelu=False, out=None):
+    """x [B * T, C] rows -> resid + act(grouped conv over time, padding K // 2, T outputs) [B * T, C] (ua2_conv1d_grouped)."""
+    Cc = x.shape[-1]
+    assert x.shape[0] == B * T and x.dtype == torch.float32
+    y = out if out is not None else torch.empty(B * T, Cc, dtype=torch.float32, device=x.device)
+    check(lib.ua2_conv1d_grouped(ptr(y), ptr(x), ptr(w_packed), ptr(bias), ptr(resid), B, T, Cc, int(groups), int(K), int(bool(gelu)), stream()),
+          "ua2_conv1d_grouped")
+    return y
+
+
+def relpos_gate(h, w, b, c, n_head):
+    """h [R, n_head * hs], w [8, hs], b [8], c [n_head] -> gate [R, n_head] fp32 (ua2_relpos_gate)."""
+    R, hs = h.shape[0], h.shape[1] // n_head
+    g = torch.empty(R, n_head, dtype=torch.float32, device=h.device)
+    check(lib.ua2_relpos_gate(ptr(g), ptr(h), ptr(w), ptr(b), ptr(c), R, n_head, hs, stream()), "ua2_relpos_gate")
+    return g
+
+
+def attn_relbias(*, dtype, R, q, row_pos, row_seq, kv, q_pos, gate, rel_tab, y=None, groups=None, y_packed=None):
+    """ua2_attn_relbias: ops.attn with score + gate[r, h] * rel_tab[h][key - q_pos[r] + tab_half]; q pre-scaled; rel_tab [n_head, 2 tab_half + 1]."""
+    a = AttnArgs()
+    a.y_packed = ptr(y_packed)
+    if groups is not None:
+        a.group_rows, a.group_seq, a.group_nkeys = ptr(groups[0]), ptr(groups[1]), ptr(groups[2])
+        a.n_groups, a.group_q_tiles = groups[0].shape[0], groups[3]
+    a.y = ptr(y)
+    a.dtype, a.R = dtype_code(dtype), R
+    a.q, a.row_pos, a.row_seq = ptr(q), ptr(row_pos), ptr(row_seq)
+    a.kv = kv
+    assert rel_tab.dim() == 2 and rel_tab.shape[0] == kv.n_head and rel_tab.shape[1] % 2 == 1 and rel_tab.dtype == torch.float32
+    assert q_pos.dtype == torch.int32 and q_pos.numel() == R and tuple(gate.shape) == (R, kv.n_head)
+    check(lib.ua2_attn_relbias(C.byref(a), ptr(q_pos), ptr(gate), ptr(rel_tab), rel_tab.shape[1] // 2, stream()), "ua2_attn_relbias")

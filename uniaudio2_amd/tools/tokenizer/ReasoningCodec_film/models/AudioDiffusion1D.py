@@ -167,11 +167,12 @@ class AudioThinking(nn.Module):
 class AudioDiffusion1D(nn.Module):
     def __init__(self, num_channels=None, unet_model_config_path=None, whisper_fea_dim=1024, wavlm_fea_dim=768, codec_dim=768,
                  encoder_depth=5, use_detokenizer=True, ssl_features: Optional[Callable] = None, device=None, whisper_encoder=None,
-                 bestrq_encoder=None, **unused):
+                 bestrq_encoder=None, wavlm_encoder=None, **unused):
         super().__init__()
         # frozen, loaded from its own checkpoint and prepared by its owner: kept out of this module's parameters / state dict
         object.__setattr__(self, "whisper_encoder", whisper_encoder)
         object.__setattr__(self, "bestrq_encoder", bestrq_encoder)
+        object.__setattr__(self, "wavlm_encoder", wavlm_encoder)
         self.max_t_len, self.sample_rate, self.sq_codec_latent = 30 * 50, 24000, 136
         self.whisper_fea_dim, self.wavlm_fea_dim, self.codec_dim = whisper_fea_dim, wavlm_fea_dim, codec_dim
         self.ssl_features = ssl_features
@@ -328,13 +329,33 @@ class AudioDiffusion1D(nn.Module):
         return self.whisper_encoder(mels)[:, :n_len, :].transpose(1, 2)
 
     @torch.inference_mode()
+    def get_wavlm_feature(self, wav_24k, len_semantic):
+        """:355-366: wav_24k (B, 1, N) or (B, N) at 24 kHz -> (B, Cl, n) WavLM features, the mean of hidden_states 6 .. 9 of the clip
+        resampled to 16 kHz with 160 zero samples appended, cut to n = min(T, 2 * len_semantic) frames."""
+        if self.wavlm_encoder is None:
+            raise NotImplementedError("get_wavlm_feature needs a WavLMEncoder (AudioDiffusion1D(wavlm_encoder=...))")
+        from ..reason_tokenizer import resample
+        wav = wav_24k[:, 0, :] if wav_24k.dim() == 3 else wav_24k
+        wav_16k = resample(wav.float().contiguous(), 24000, 16000)
+        wav_16k = torch.cat([wav_16k, torch.zeros(wav_16k.shape[0], 160, dtype=torch.float32, device=wav_16k.device)], 1)      # :358
+        feat = self.wavlm_encoder(wav_16k.contiguous())
+        n = min(feat.shape[1], 2 * int(len_semantic))
+        return feat[:, :n, :].transpose(1, 2)
+
+    @torch.inference_mode()
     def fetch_codes_batch(self, input_audios, spectrograms, additional_feats=None, return_reasoning_text=False, film_masks=None):
         """:493-551.  The frozen SSL encoders are the injected `ssl_features` callable (see the module docstring).  film_masks
         (3, B) bool: the three FiLM draws of this call made by the caller (ReasoningTokenizer.audio2token draws them for the
         reference's whole chunk and computes only the rows whose tokens are kept)."""
         if return_reasoning_text:
             raise NotImplementedError("the reasoning-text LLM of AudioThinking is not part of the token path and is not built")
-        if self.ssl_features is None:
+        have_all = self.whisper_encoder is not None and self.bestrq_encoder is not None and self.wavlm_encoder is not None
+        if self.ssl_features is None and not have_all:
+            if self.wavlm_encoder is not None:
+                missing = " / ".join(n for n, e in (("Whisper", self.whisper_encoder), ("BEST-RQ", self.bestrq_encoder)) if e is None)
+                raise NotImplementedError(f"tokenising audio needs the frozen {missing} encoder(s) next to the WavLM encoder; "
+                                          "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
+                                          "fetch_codes_from_features")
             if self.bestrq_encoder is not None:
                 missing = "WavLM encoder" if self.whisper_encoder is not None else "Whisper / WavLM encoders"
                 raise NotImplementedError(f"tokenising audio needs the frozen {missing} (out of scope, SURVEY.md §2.1); "
@@ -347,13 +368,15 @@ class AudioDiffusion1D(nn.Module):
             raise NotImplementedError("tokenising audio needs the frozen Whisper / WavLM / BEST-RQ encoders (out of scope, SURVEY.md §2.1); "
                                       "construct AudioDiffusion1D(ssl_features=...) with a callable that returns their features, or call "
                                       "fetch_codes_from_features")
-        f = dict(self.ssl_features(input_audios, spectrograms))
+        f = dict(self.ssl_features(input_audios, spectrograms)) if self.ssl_features is not None else {}
         if self.bestrq_encoder is not None and ("bestrq_acoustic" not in f or "bestrq_semantic" not in f):
             f["bestrq_acoustic"], f["bestrq_semantic"] = self.bestrq_encoder.extract_continous_embeds_multiple(input_audios)      # :503
         if "whisper" not in f and self.whisper_encoder is not None:
             if spectrograms is None:
                 raise ValueError("fetch_codes_batch: the Whisper encoder needs the log-mel `spectrograms` (B, 80, 3000)")
             f["whisper"] = self.get_whisper_feature(spectrograms, input_audios.shape[-1], f["bestrq_semantic"].shape[2])
+        if "wavlm" not in f and self.wavlm_encoder is not None:
+            f["wavlm"] = self.get_wavlm_feature(input_audios, f["bestrq_semantic"].shape[2])                                      # :505
         return self.fetch_codes_from_features(f["whisper"], f["wavlm"], f["bestrq_acoustic"], f["bestrq_semantic"], film_masks=film_masks)
 
     # ---- decode side -----------------------------------------------------------------------------------------------

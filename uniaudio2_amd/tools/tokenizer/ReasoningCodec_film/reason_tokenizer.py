@@ -16,10 +16,11 @@ Mirror of the reference's tools/tokenizer/ReasoningCodec_film/reason_tokenizer.p
   * `tokenize(wav path) -> (reason (8, T_r), rec (8, T_s))` (:377-387): load, down-mix, resample to 24 kHz
     (torchaudio's windowed-sinc algorithm restated as one MFMA GEMM, `resample`), then `audio2token`
     (:86-129): tile the clip to 30-s segments (+240 samples), `model.fetch_codes_batch` per batch of 6
-    segments, crop to int(dur * 12.5) + 1 / int(dur * 5) + 1 tokens.  The frozen WavLM / BEST-RQ encoders inside
-    fetch_codes_batch are an injected callable (models/AudioDiffusion1D.py); the Whisper branch runs on the device
-    when the model carries a `whisper_encoder`: `get_whisper_features` (:67-72) = 24 -> 16 kHz `resample` + the
-    log-mel kernel (ua2_logmel).  `tokenize(tensor)` passes tensors through (:387-388).
+    segments, crop to int(dur * 12.5) + 1 / int(dur * 5) + 1 tokens.  The three frozen SSL encoders inside
+    fetch_codes_batch (Whisper, BEST-RQ, WavLM) run on the device when the model carries them (`whisper_encoder`,
+    `bestrq_encoder`, `wavlm_encoder`; models/AudioDiffusion1D.py), and an injected callable supplies whatever it does not;
+    the Whisper branch's `get_whisper_features` (:67-72) = 24 -> 16 kHz `resample` + the log-mel kernel (ua2_logmel).
+    `tokenize(tensor)` passes tensors through (:387-388).
 """
 import math
 import os
@@ -191,7 +192,8 @@ class ReasoningTokenizer:
         self.feature_extractor = feature_extractor
         self.whisper_dtype = torch.bfloat16                 # _load_released: the reference runs the encoder under bf16 autocast (:117)
         self.bestrq_dtype = torch.float32                   # the reference runs BEST-RQ with autocast disabled (AudioDiffusion1D.py:502); bfloat16 = opt-in speed plan
-        self.skip_discarded_segments = True                 # audio2token: do not encode segments whose tokens the reference slices away
+        self.wavlm_dtype = torch.float32                    # the reference runs WavLM in fp32 (no autocast around get_wavlm_feature); bfloat16 = opt-in speed plan
+        self.skip_discarded_segments = True                # audio2token: do not encode segments whose tokens the reference slices away
         self.vq = (vq_phone, vq_semantic, vq_acoustic)
         if model is not None:
             self.vq = (model.vq_pronunciation_semantic, model.vq_structure_semantic, model.vq_acoustic)
@@ -202,9 +204,11 @@ class ReasoningTokenizer:
         """The reference's constructor (:22-66): yaml -> SQ-Codec (sq_config yaml `generator.config`, sq_resume['codec_model'],
         scalar24k.py:423-437) + AudioDiffusion1D (transformer_diffusion_config json; model_path['model'], 'module.' prefixes
         stripped, strict=False).  Of the frozen SSL encoders named in the yaml Whisper is loaded when `whisper_path` names an
-        existing directory (models/modeling_whisper.py) and BEST-RQ when its entry names an existing checkpoint file
-        (`bestrq_checkpoint`; models/PretrainedModel.py); WavLM is not (out of scope): decoding works, `tokenize(path)`
-        needs `model.ssl_features` for the WavLM features.  Widths of the encode side are read off the checkpoint."""
+        existing directory (models/modeling_whisper.py), BEST-RQ when its entry names an existing checkpoint file
+        (`bestrq_checkpoint`; models/PretrainedModel.py) and WavLM when `wav_lm_path` names an existing directory
+        (models/modeling_wavlm.py; plans: `whisper_dtype`, `bestrq_dtype`, `wavlm_dtype`).  With all three, `tokenize(path)` runs
+        from the released files alone; an encoder whose entry is absent is left out (decoding still works) and
+        `model.ssl_features` has to supply its features.  Widths of the encode side are read off the checkpoint."""
         import yaml
         from .models.AudioDiffusion1D import AudioDiffusion1D
         from .models.scalar24k import ScalarModel
@@ -241,6 +245,7 @@ class ReasoningTokenizer:
             from .models.modeling_whisper import WhisperEncoder
             object.__setattr__(self.model, "whisper_encoder", WhisperEncoder.from_pretrained(wp).to(self.device).prepare(self.whisper_dtype))
         self._load_bestrq(ta)
+        self._load_wavlm(ta)
         self.vq = (model.vq_pronunciation_semantic, model.vq_structure_semantic, model.vq_acoustic)
 
     def _load_bestrq(self, ta):
@@ -251,6 +256,15 @@ class ReasoningTokenizer:
             from .models import PretrainedModel
             object.__setattr__(self.model, "bestrq_encoder",
                                PretrainedModel.BESTRQ_Model(checkpoint_dir=bp, layers=(4, 11), device=self.device, dtype=self.bestrq_dtype))
+
+    def _load_wavlm(self, ta):
+        """AudioDiffusion1D.py:233-234: AutoModel.from_pretrained(wav_lm_path), read at hidden_states 6 .. 9 (:363) — set on the model when the
+        yaml's `wav_lm_path` names an existing directory."""
+        lp = ta.get("wav_lm_path")
+        if lp and os.path.isdir(lp):
+            from .models import modeling_wavlm
+            object.__setattr__(self.model, "wavlm_encoder",
+                               modeling_wavlm.WavLMEncoder.from_pretrained(lp, taps=(6, 7, 8, 9)).to(self.device).prepare(self.wavlm_dtype))
 
     @staticmethod
     def bestrq_checkpoint(ta):
