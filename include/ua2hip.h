@@ -387,6 +387,60 @@ int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_t ld, int32
 int ua2_ngram_filter(int32_t* out, int32_t ld, int32_t R, int32_t n, int32_t fallback,
                      int32_t* hist, int32_t* hist_len, int32_t cap, void* stream);
 
+/* ---- beam search over the text head (entry points added under ABI v10) -------------------------------------
+ * The W <= 8 hypotheses ("slots") of a beam are rows 0 .. W - 1 of a decode frame.  All state lives in caller-owned device buffers:
+ *   score [W] fp32, fin [W] (0 live, 1 finished, 2 dead = holds no hypothesis), len [W] text ids so far, parent [W] (written by a step),
+ *   ctrl [4]: [0] steps run, [1] the step at which all W slots were first finished (-1 until then), [2..3] unused,
+ *   cand_logp / cand_id [W, 8]: scratch between the two launches of a step,
+ *   log [log_cap, W, 4] int32: per step and slot (parent, text id or -1, score bits, fin) — the host recovers a hypothesis's text by
+ *   walking the log backwards; a step at or past log_cap is not logged,
+ *   lp_inv [lp_n] fp32: 1 / lp(L), lp(L) = ((5 + L) / 6) ** length_penalty, computed by the host in float64 (index clamped to lp_n - 1).
+ * Start: score = (0, -inf, ..), fin = (0, 2, ..), len = 0, ctrl = (0, -1, 0, 0). */
+typedef struct ua2_beam_state {
+  float* score;
+  int32_t* fin;
+  int32_t* len;
+  int32_t* parent;
+  int32_t* ctrl;
+  float* cand_logp;
+  int32_t* cand_id;
+  int32_t* log;
+  int32_t log_cap;
+  const float* lp_inv;
+  int32_t lp_n;
+} ua2_beam_state;
+/* One step of the rule on logits [W, ld] fp32 (V columns used, W <= V <= ld).  Slots in slot order: a finished slot contributes
+ * itself; a live slot its W largest logits (NaN ordered as -inf; lowest id first among equals) in rank order with
+ * logp = (x - m) - logf(S), m the row maximum, S = sum of expf(x - m) as 1024 strided partial sums (column c in partial c % 1024,
+ * ascending c) joined by a fixed halving tree — the launch geometry (one 1024-thread workgroup per live row) is part of the contract.
+ * Column eos: the slot finishes, len unchanged, score + logp * lp_inv[len]; any other column k: len + 1, score + logp * lp_inv[len + 1],
+ * text id k (one rounded fp32 product, one rounded fp32 sum).  The new beam = the W candidates of highest score, equal scores in
+ * candidate order.  Writes score / fin / len / parent, token[j * token_ld] = the id slot j feeds back (0 for a finished slot;
+ * every id clamped into [0, V)), the log record, ctrl.  An eos outside [0, V) never matches.  Two launches. */
+int ua2_beam_step(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t eos, const ua2_beam_state* st,
+                  int32_t* token, int32_t token_ld, void* stream);
+/* One K or V pool of a paged cache for the fork: [pages, n_kv, 64, head_bytes / element size]; table = index of its page table. */
+typedef struct ua2_beam_pool {
+  void* pool;
+  int32_t table;
+  int32_t n_kv;
+  int32_t head_bytes;   /* bytes of one position of one head: a multiple of 16 */
+  int32_t reserved;
+} ua2_beam_pool;
+/* The K/V fork behind a step (or, parent == NULL: all parents 0, the start).  Page tables [table_rows, max_pages] in the static layout
+ * (sequence b owns pages b * max_pages ..), table_rows >= 2 W; every pool holds table_rows * max_pages pages.  Slot j (row j of the
+ * tables), n = row_pos[j] + pos_add the next position it writes (pos_add 0: before the first frame, 1: behind a frame's trunk),
+ * c = n / 64, p = parent[j] (clamped into [0, W)):
+ *   table[j][col < c] = OLD table[p][col]   (full pages are shared, never written again),
+ *   table[j][c] = page ((n & 1) * W + j) * max_pages + c   (its own page of page set n & 1: the sets alternate from step to step, so
+ *                 the pages read and the pages written by one call are disjoint),
+ *   positions [0, n % 64) of OLD table[p][c] are copied to that page in every pool (16-byte accesses; nothing when n % 64 == 0 or the
+ *   two pages are the same).  A position at or past 64 * max_pages changes no column and copies nothing.
+ * pools: DEVICE array of n_pools descriptors (bf16 and fp32 pools alike: bytes are copied); tables: host array of n_tables <= 3 device
+ * pointers.  Two launches (copy, then tables). */
+int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t* row_pos, int32_t pos_add, const ua2_beam_pool* pools,
+                     int32_t n_pools, int32_t* const* tables, int32_t n_tables, int32_t table_rows, int32_t max_pages, void* stream);
+
 /* ---- codec: residual vector quantisation ------------------------------------------------ */
 
 /* Nearest-codeword search, level by level on the residual (core_vq.py:179-185, 365-376; the live codec's
@@ -738,6 +792,12 @@ int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32_t n);
  * are keyed on n (switching the filter off and on again re-uses them); a new fallback, new buffers or a new cap drop them.
  * Modes 0 and 2 are never filtered. */
 int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, int32_t* hist, int32_t* hist_len, int32_t cap);
+/* Beam search of the text loop (feedback mode 3 of the frame entry point below).  W >= 1 attaches the caller-owned state (copied by
+ * value; the buffers stay alive while attached), the EOS id and the device array of the n_pools K / V pools of the three trunk
+ * GPTs (table index 0 = understanding expert, 1 = backbone, 2 = generation expert; their page tables, of max_batch rows, are the
+ * plan's).  Needs 1 <= W <= 8, 2 W <= max_batch (the pages of sequences W .. 2W - 1 are the second page set of the fork) and the
+ * three tables of one width.  W = 0 clears.  New buffers, a new W or a new EOS drop the captured frame graphs. */
+int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools, int32_t n_pools);
 /* cfg_scale > 1: frames of (conditional, unconditional) row pairs — rows 2p, 2p + 1; an even row count — sample from the guided
  * logits (ua2_cfg_mix); feedback mode 2 continues every row from its pair's conditional row. */
 int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale);
@@ -771,6 +831,11 @@ int ua2_stage3_feedback(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_e
  * (it consumes the prompt's last token, usually an audio step) and any sequence that will see an audio step later must run without it:
  * the skipped positions of the experts' caches are left unwritten. */
 #define UA2_FRAME_SKIP_AUDIO_EXPERTS 32
+/* mode 3 (with or without UA2_FRAME_SKIP_AUDIO_EXPERTS, under mode 1's precondition): a beam-search frame of R = W rows — trunk,
+ * lm_head, the beam step on its fp32 logits, the K/V fork, then the text feedback of mode 1 with the ids the step chose (tokens
+ * (0 x n_cb, id), masks (0.., 1), row_pos += 1; the frame log's text column holds them).  Checked before any launch: a beam is
+ * attached (the set_beam call above) and R equals its W; no classifier-free guidance, no n-gram filter, top-k = 1.  The caller keeps the step
+ * count within the state's log and length-penalty tables and every position within the caches. */
 int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card,
                      int32_t use_graph, void* stream);
 /* Expose intermediate buffers for tests: name in {"h_final","text_logits","audio_logits"}. */

@@ -80,6 +80,17 @@ class W8Entry(C.Structure):
     _fields_ = [("w", vp), ("q", vp), ("exp", vp)]
 
 
+class BeamState(C.Structure):
+    """ua2_beam_state: the caller-owned device buffers of a beam search (include/ua2hip.h)."""
+    _fields_ = [("score", vp), ("fin", vp), ("len", vp), ("parent", vp), ("ctrl", vp), ("cand_logp", vp), ("cand_id", vp),
+                ("log", vp), ("log_cap", i32), ("lp_inv", vp), ("lp_n", i32)]
+
+
+class BeamPool(C.Structure):
+    """ua2_beam_pool: one K or V pool of a paged cache for ua2_beam_reorder."""
+    _fields_ = [("pool", vp), ("table", i32), ("n_kv", i32), ("head_bytes", i32), ("reserved", i32)]
+
+
 ACT_NONE, ACT_PRELU, ACT_ELU, ACT_TANH, ACT_ROUND9 = 0, 1, 2, 3, 4
 EW_IDENTITY, EW_SILU, EW_SIGMOID, EW_TANH = 0, 1, 2, 3
 
@@ -156,6 +167,9 @@ _EXPORTS = {
     "ua2_relpos_gate": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "ua2_attn_relbias": (C.c_int, [C.POINTER(AttnArgs), vp, vp, vp, i32, vp]),
     "ua2_ngram_filter": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
+    "ua2_beam_step": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
+    "ua2_beam_reorder": (C.c_int, [i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),
+    "ua2_stage3_set_beam": (C.c_int, [vp, i32, i32, C.POINTER(BeamState), vp, i32]),
     "ua2_qknorm_rope_kv": (C.c_int, [C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, C.POINTER(KvGeom), vp]),
     "ua2_stage3_scratch_floats": (C.c_size_t, [C.POINTER(Stage3Desc)]),
     "ua2_stage3_create": (C.c_int, [C.POINTER(Stage3Desc), C.POINTER(vp)]),

@@ -1,0 +1,285 @@
+// Beam search over the text head, on the device (DESIGN.md §2 "beam search", §4; the rule is a corrected restatement of the
+// reference's evaluation/asr_task.py:438-576, whose own function cannot run).
+//
+// The W hypotheses of a beam are the W rows of one decode frame (rows = sequences 0 .. W - 1).  Per frame:
+//   ua2_beam_step     beam_topw_kernel    one 1024-thread workgroup per LIVE row over its fp32 logits: row maximum, sum of
+//                                         exp(x - m), the W best columns (value descending, id ascending), their log-softmax
+//                     beam_select_kernel  one workgroup: the <= W * W + W candidates in candidate order, the length-normalised
+//                                         scores, the W best (stable), the new per-slot state, parents, fed-back ids, one log record
+//   ua2_beam_reorder  beam_copy_kernel    the K/V fork: slot j's copy of its parent's partial 64-position page, every pool
+//                     beam_table_kernel   the page tables: shared full pages inherited from the parent, the new partial page
+// Nothing is permuted on the device but page-table entries and at most one partial page per pool and slot; the text of a hypothesis
+// is recovered on the host by walking the step log backwards.
+//
+// Reproducibility: the workgroup size of beam_topw_kernel (1024) is part of the contract — the sum of exponentials is 1024 strided
+// partial sums (column c goes to thread c % 1024, ascending c) joined by the fixed halving tree below, so a row's log-sum-exp has
+// the same bits whatever else runs.  The top-W selection is an arg-max over a total order (value, then lower id), so it does not
+// depend on geometry at all.
+#include "ua2_common.h"
+
+namespace {
+
+constexpr int kBeamMaxW = 8;
+constexpr int kTopwThreads = 1024;
+constexpr int kTopwBatch = 16;
+constexpr int kMaxCand = kBeamMaxW * kBeamMaxW + kBeamMaxW;
+
+__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
+__device__ __forceinline__ float beam_finite_or_ninf(float x) { return x == x ? x : -INFINITY; }   // a NaN is ordered as -inf
+
+// fin: 0 live, 1 finished, 2 dead (a slot that holds no hypothesis: slots 1 .. W - 1 before the first step)
+__global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __restrict__ logits, int ld, int V, int W,
+                                                                 const int32_t* __restrict__ fin, float* __restrict__ cand_logp,
+                                                                 int32_t* __restrict__ cand_id) {
+  __shared__ float red[kTopwThreads];
+  __shared__ float wv[kTopwThreads / 64];
+  __shared__ int wi[kTopwThreads / 64];
+  const int j = blockIdx.x, tid = threadIdx.x;
+  if (fin[j] != 0) return;                       // the whole workgroup: finished and dead slots produce no candidates from logits
+  const float* row = logits + (size_t)j * ld;
+  float lv[kBeamMaxW];
+  int li[kBeamMaxW];
+#pragma unroll
+  for (int k = 0; k < kBeamMaxW; ++k) { lv[k] = -INFINITY; li[k] = UA2_TOK_NONE; }
+  float m = -INFINITY;
+  // kTopwBatch independent loads in flight per thread (one load per iteration leaves the pass latency-bound: ~125 dependent
+  // round trips at the released vocabulary), then the columns in ascending order as before
+  for (int base = tid; base < V; base += kTopwBatch * kTopwThreads) {
+    float xs[kTopwBatch];
+#pragma unroll
+    for (int u = 0; u < kTopwBatch; ++u) {
+      const int c = base + u * kTopwThreads;
+      xs[u] = c < V ? beam_finite_or_ninf(row[c]) : -INFINITY;
+    }
+#pragma unroll
+    for (int u = 0; u < kTopwBatch; ++u) {
+      const int c = base + u * kTopwThreads;
+      const float x = xs[u];
+      if (c >= V) continue;
+      m = fmaxf(m, x);
+      if (beam_better(x, c, lv[kBeamMaxW - 1], li[kBeamMaxW - 1])) {
+        float cv = x;
+        int ci = c;
+#pragma unroll
+        for (int k = 0; k < kBeamMaxW; ++k)
+          if (beam_better(cv, ci, lv[k], li[k])) {
+            const float tv = lv[k]; const int ti = li[k];
+            lv[k] = cv; li[k] = ci; cv = tv; ci = ti;
+          }
+      }
+    }
+  }
+  red[tid] = m;
+  __syncthreads();
+  for (int s = kTopwThreads / 2; s >= 1; s >>= 1) {
+    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
+    __syncthreads();
+  }
+  m = red[0];
+  __syncthreads();
+  float part = 0.f;
+  if (m > -INFINITY)
+    for (int base = tid; base < V; base += kTopwBatch * kTopwThreads) {
+      float xs[kTopwBatch];
+#pragma unroll
+      for (int u = 0; u < kTopwBatch; ++u) {
+        const int c = base + u * kTopwThreads;
+        xs[u] = c < V ? beam_finite_or_ninf(row[c]) : -INFINITY;
+      }
+#pragma unroll
+      for (int u = 0; u < kTopwBatch; ++u)                 // ascending c, one rounded sum per column
+        if (base + u * kTopwThreads < V) part += expf(xs[u] - m);
+    }
+  red[tid] = part;
+  __syncthreads();
+  for (int s = kTopwThreads / 2; s >= 1; s >>= 1) {       // the fixed tree: red[t] += red[t + s], s = 512, 256, .., 1
+    if (tid < s) red[tid] = red[tid] + red[tid + s];
+    __syncthreads();
+  }
+  const float logS = logf(red[0]);
+  for (int r = 0; r < W; ++r) {
+    float bv = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (beam_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { wv[tid >> 6] = bv; wi[tid >> 6] = bi; }
+    __syncthreads();
+    bv = wv[0]; bi = wi[0];
+    for (int w = 1; w < kTopwThreads / 64; ++w)
+      if (beam_better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; }
+    if (bi != UA2_TOK_NONE && bi == li[0]) {      // the one thread that held the winner moves on to its next entry
+#pragma unroll
+      for (int k = 0; k + 1 < kBeamMaxW; ++k) { lv[k] = lv[k + 1]; li[k] = li[k + 1]; }
+      lv[kBeamMaxW - 1] = -INFINITY; li[kBeamMaxW - 1] = UA2_TOK_NONE;
+    }
+    if (tid == 0) {
+      // a row without a finite entry has no distribution: every candidate scores -inf
+      cand_logp[j * kBeamMaxW + r] = (m > -INFINITY) ? (bv - m) - logS : -INFINITY;
+      cand_id[j * kBeamMaxW + r] = min(max(bi, 0), V - 1);
+    }
+    __syncthreads();                              // wv / wi are rewritten by the next round
+  }
+}
+
+__global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, ua2_beam_state st, int32_t* __restrict__ token, int token_ld) {
+  __shared__ float cs[kMaxCand];
+  __shared__ int cpar[kMaxCand], ctok[kMaxCand], cfin[kMaxCand], clen[kMaxCand], taken[kMaxCand];
+  __shared__ float sscore[kBeamMaxW];
+  __shared__ int sfin[kBeamMaxW], slen[kBeamMaxW];
+  const int tid = threadIdx.x;
+  if (tid < W) { sfin[tid] = st.fin[tid]; sscore[tid] = st.score[tid]; slen[tid] = max(st.len[tid], 0); }
+  __syncthreads();
+  // candidate order: slots in slot order, a live slot's W columns in rank order.  Thread (j, r) = j * 8 + r fills the candidate of
+  // slot j, rank r at its place in that order (a finished slot has the one candidate, a dead slot none): the loads run side by side
+  int n = 0;
+  for (int i = 0; i < W; ++i) n += sfin[i] == 0 ? W : (sfin[i] == 1 ? 1 : 0);
+  {
+    const int j = tid / kBeamMaxW, r = tid % kBeamMaxW;
+    if (j < W && r < W) {
+      int at = r;
+      for (int i = 0; i < j; ++i) at += sfin[i] == 0 ? W : (sfin[i] == 1 ? 1 : 0);
+      const int f = sfin[j], L = slen[j];
+      const float sc = sscore[j];
+      if (f == 1 && r == 0) {
+        cs[at] = beam_finite_or_ninf(sc); cpar[at] = j; ctok[at] = -1; cfin[at] = 1; clen[at] = L; taken[at] = 0;
+      } else if (f == 0) {
+        const int k = st.cand_id[j * kBeamMaxW + r];
+        const float lp = beam_finite_or_ninf(st.cand_logp[j * kBeamMaxW + r]);
+        const bool is_eos = k == eos;
+        const int Ln = is_eos ? L : L + 1;        // the EOS id is not part of the text
+        // score + logp / lp(len): the host's float64 1 / lp as fp32, one rounded product, one rounded sum (no contraction)
+        const float s = __fadd_rn(sc, __fmul_rn(lp, st.lp_inv[min(Ln, st.lp_n - 1)]));
+        cs[at] = beam_finite_or_ninf(s); cpar[at] = j; ctok[at] = is_eos ? -1 : k; cfin[at] = is_eos ? 1 : 0; clen[at] = Ln; taken[at] = 0;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const int step = st.ctrl[0];
+  bool all_fin = true;
+  for (int t = 0; t < W; ++t) {                   // the W best; equal scores in candidate order (a stable descending sort)
+    int best = -1;
+    for (int i = 0; i < n; ++i)
+      if (!taken[i] && (best < 0 || cs[i] > cs[best])) best = i;
+    float s = -INFINITY;
+    int par = t, tok = -1, f = 2, L = 0;          // fewer candidates than slots (never after the first step): a dead slot
+    if (best >= 0) { taken[best] = 1; s = cs[best]; par = cpar[best]; tok = ctok[best]; f = cfin[best]; L = clen[best]; }
+    all_fin = all_fin && f == 1;
+    // every read of the old state is done (the candidates hold copies): write the new one
+    st.score[t] = s; st.fin[t] = f; st.len[t] = L; st.parent[t] = par;
+    token[(size_t)t * token_ld] = f == 0 ? min(max(tok, 0), V - 1) : 0;
+    if (step >= 0 && step < st.log_cap) {
+      int32_t* rec = st.log + ((size_t)step * W + t) * 4;
+      rec[0] = par; rec[1] = f == 0 ? min(max(tok, 0), V - 1) : -1; rec[2] = __float_as_int(s); rec[3] = f;
+    }
+  }
+  if (all_fin && st.ctrl[1] < 0) st.ctrl[1] = step;
+  st.ctrl[0] = step + 1;
+}
+
+struct BeamTables {
+  int32_t* t[3];
+};
+
+// slot j's private page for the column of position n: the static page (row, column) of page set n & 1 — set 0 = the pages of
+// sequences 0 .. W - 1, set 1 = those of sequences W .. 2W - 1 (the static layout: sequence b owns pages [b * max_pages, ..))
+__device__ __forceinline__ int beam_own_page(int n, int j, int W, int max_pages) { return (((n & 1) * W) + j) * max_pages + (n >> 6); }
+
+__global__ __launch_bounds__(256) void beam_copy_kernel(int W, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
+                                                        int pos_add, const ua2_beam_pool* __restrict__ pools, BeamTables T,
+                                                        int table_rows, int max_pages) {
+  const ua2_beam_pool P = pools[blockIdx.x];
+  const int j = blockIdx.y;
+  const int n = row_pos[j] + pos_add;              // the next position slot j writes
+  if (n < 0) return;
+  const int c = n >> 6, fill = n & 63;
+  if (fill == 0 || c >= max_pages) return;         // the position opens a new page: nothing to carry over
+  const int p = parent ? min(max(parent[j], 0), W - 1) : 0;
+  const int32_t* tab = T.t[min(max(P.table, 0), 2)];
+  const int src = min(max(tab[p * max_pages + c], 0), table_rows * max_pages - 1);
+  const int dst = beam_own_page(n, j, W, max_pages);
+  if (src == dst) return;                          // the start, slot 0: the prompt's page is already its own
+  const size_t head_bytes = (size_t)P.head_bytes, page_bytes = (size_t)P.n_kv * UA2_PAGE * head_bytes;
+  const char* s = (const char*)P.pool + (size_t)src * page_bytes;
+  char* d = (char*)P.pool + (size_t)dst * page_bytes;
+  const int nvec = (int)(fill * head_bytes / 16);  // the filled positions of one head: contiguous
+  for (int v = threadIdx.x; v < P.n_kv * nvec; v += blockDim.x) {
+    const int h = v / nvec, o = v - h * nvec;
+    const size_t off = (size_t)h * UA2_PAGE * head_bytes + (size_t)o * 16;
+    *reinterpret_cast<uint4*>(d + off) = *reinterpret_cast<const uint4*>(s + off);
+  }
+}
+
+// rows 0 .. W - 1 of every table: read everything, barrier, write — a slot's new row is its parent's OLD row
+__global__ __launch_bounds__(256) void beam_table_kernel(int W, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
+                                                         int pos_add, BeamTables T, int n_tables, int max_pages) {
+  extern __shared__ int32_t old[];
+  const int cells = W * max_pages;
+  for (int t = 0; t < n_tables; ++t) {
+    int32_t* tab = T.t[t];
+    for (int e = threadIdx.x; e < cells; e += blockDim.x) old[e] = tab[e];
+    __syncthreads();
+    for (int e = threadIdx.x; e < cells; e += blockDim.x) {
+      const int j = e / max_pages, col = e - j * max_pages;
+      const int n = row_pos[j] + pos_add;
+      if (n < 0) continue;
+      const int c = n >> 6;
+      const int p = parent ? min(max(parent[j], 0), W - 1) : 0;
+      if (col < c) tab[e] = old[p * max_pages + col];
+      else if (col == c) tab[e] = beam_own_page(n, j, W, max_pages);
+    }
+    __syncthreads();
+  }
+}
+
+int check_state(const ua2_beam_state* st, int W, const char* who) {
+  UA2_CHECK(W >= 1 && W <= kBeamMaxW, "%s: beam width must be in 1..%d, got %d", who, kBeamMaxW, W);
+  UA2_CHECK(st && st->score && st->fin && st->len && st->parent && st->ctrl && st->cand_logp && st->cand_id && st->log && st->lp_inv,
+            "%s: NULL state buffer", who);
+  UA2_CHECK(st->log_cap >= 1 && st->lp_n >= 2, "%s: log capacity %d / %d length-penalty entries", who, st->log_cap, st->lp_n);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ua2_beam_step(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t eos, const ua2_beam_state* st,
+                             int32_t* token, int32_t token_ld, void* stream) {
+  if (int rc = check_state(st, W, "ua2_beam_step")) return rc;
+  UA2_CHECK(logits && token && token_ld >= 1, "ua2_beam_step: NULL logits / token buffer");
+  UA2_CHECK(V >= W && ld >= V, "ua2_beam_step: need W <= V <= ld (W=%d V=%d ld=%d)", W, V, ld);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(beam_topw_kernel, dim3(W), dim3(kTopwThreads), 0, s, logits, ld, V, W, st->fin, st->cand_logp, st->cand_id);
+  UA2_LAUNCH_CHECK();
+  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(64), 0, s, W, V, eos, *st, token, token_ld);
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t* row_pos, int32_t pos_add, const ua2_beam_pool* pools,
+                                int32_t n_pools, int32_t* const* tables, int32_t n_tables, int32_t table_rows, int32_t max_pages,
+                                void* stream) {
+  UA2_CHECK(W >= 1 && W <= kBeamMaxW, "ua2_beam_reorder: beam width must be in 1..%d, got %d", kBeamMaxW, W);
+  UA2_CHECK(row_pos && tables && n_tables >= 1 && n_tables <= 3 && n_pools >= 0 && (n_pools == 0 || pools), "ua2_beam_reorder: bad arguments");
+  UA2_CHECK(pos_add == 0 || pos_add == 1, "ua2_beam_reorder: pos_add must be 0 (start) or 1 (end of a frame)");
+  UA2_CHECK(table_rows >= 2 * W, "ua2_beam_reorder: a beam of %d needs page tables of %d sequences, got %d", W, 2 * W, table_rows);
+  UA2_CHECK(max_pages >= 1 && (size_t)W * max_pages * sizeof(int32_t) <= 48 * 1024, "ua2_beam_reorder: max_pages=%d out of range", max_pages);
+  BeamTables T{};
+  for (int t = 0; t < n_tables; ++t) {
+    UA2_CHECK(tables[t] != nullptr, "ua2_beam_reorder: table %d is NULL", t);
+    T.t[t] = tables[t];
+  }
+  for (int t = n_tables; t < 3; ++t) T.t[t] = tables[0];
+  hipStream_t s = (hipStream_t)stream;
+  if (n_pools > 0) {
+    hipLaunchKernelGGL(beam_copy_kernel, dim3(n_pools, W), dim3(256), 0, s, W, parent, row_pos, pos_add, pools, T, table_rows, max_pages);
+    UA2_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(beam_table_kernel, dim3(1), dim3(256), (size_t)W * max_pages * sizeof(int32_t), s, W, parent, row_pos, pos_add, T,
+                     n_tables, max_pages);
+  UA2_LAUNCH_CHECK();
+  return 0;
+}

@@ -64,6 +64,10 @@ struct ua2_stage3 {
   // n-gram repeat filter of the text-feedback frames (ua2_stage3_set_ngram; ngram_n <= 1 = off): caller-owned device history
   int32_t ngram_n = 0, ngram_fallback = 0, ngram_cap = 0;
   int32_t *ngram_hist = nullptr, *ngram_hist_len = nullptr;
+  // beam search of the text loop (ua2_stage3_set_beam; beam_W == 0 = off): caller-owned device state, the K / V pools of the fork
+  int32_t beam_W = 0, beam_eos = -1, beam_n_pools = 0;
+  ua2_beam_state beam{};
+  const ua2_beam_pool* beam_pools = nullptr;
   // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
   struct W8Twin { const void* q; const int8_t* exp; };
   std::map<const void*, W8Twin> w8;
@@ -568,6 +572,32 @@ extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, 
   return 0;
 }
 
+extern "C" int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools, int32_t n_pools) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_beam: NULL handle");
+  auto drop = [&] {
+    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);   // recorded beam frames bake the state's pointers: drop them
+    h->graphs.clear();
+  };
+  if (W == 0) {
+    if (h->beam_W != 0) drop();
+    h->beam_W = 0;
+    return 0;
+  }
+  const ua2_stage3_desc& d = h->d;
+  UA2_CHECK(W >= 1 && W <= 8, "ua2_stage3_set_beam: beam width must be in 1..8, got %d", W);
+  UA2_CHECK(2 * W <= d.max_batch, "ua2_stage3_set_beam: a beam of %d needs a plan of %d sequences (max_batch), got %d", W, 2 * W, d.max_batch);
+  UA2_CHECK(st && st->score && st->fin && st->len && st->parent && st->ctrl && st->cand_logp && st->cand_id && st->log && st->lp_inv,
+            "ua2_stage3_set_beam: NULL state buffer");
+  UA2_CHECK(st->log_cap >= 1 && st->lp_n >= 2, "ua2_stage3_set_beam: log capacity %d / %d length-penalty entries", st->log_cap, st->lp_n);
+  UA2_CHECK(n_pools >= 0 && (n_pools == 0 || pools), "ua2_stage3_set_beam: missing pool descriptors");
+  UA2_CHECK(d.und.max_pages == d.backbone.max_pages && d.gen.max_pages == d.backbone.max_pages && d.backbone.max_pages >= 1 &&
+            (size_t)W * d.backbone.max_pages * sizeof(int32_t) <= 48 * 1024, "ua2_stage3_set_beam: the three trunk page tables must have one width");
+  UA2_CHECK(d.vt >= W, "ua2_stage3_set_beam: vocabulary smaller than the beam");
+  if (W != h->beam_W || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop();
+  h->beam_W = W; h->beam_eos = eos; h->beam = *st; h->beam_pools = pools; h->beam_n_pools = n_pools;
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale) {
   UA2_CHECK(h != nullptr && cfg_scale >= 1.f, "ua2_stage3_set_cfg: NULL handle or cfg_scale < 1");
   h->cfg_scale = cfg_scale;
@@ -589,7 +619,7 @@ extern "C" int ua2_stage3_trunk(ua2_stage3* h, int32_t R, void* stream) {
 // to a list nobody reads (:259), so the frame's audio ids do not depend on it: skipping lm_head + its arg-max (788 MB of weights
 // at 3072 x 128256 bf16 = 117 us of the 3.1 ms B = 1 frame, 220 us at 64 rows) leaves (reason, semantic) bit-identical
 // (model_new.py:617 computes it every frame).  generate_frame's (B, 9) API never sets it.
-static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bool skip_text = false) {
+static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bool skip_text = false, bool beam = false) {
   UA2_CHECK(h && R > 0 && R <= h->d.max_batch, "ua2_stage3_heads: R=%d out of range", R);
   hipStream_t s = (hipStream_t)stream;
   const ua2_stage3_desc& d = h->d;
@@ -642,7 +672,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   UA2_CHECK(!cfg || R % 2 == 0, "ua2_stage3_heads: classifier-free guidance needs (conditional, unconditional) row pairs, R=%d", R);
   const int key_shift = cfg ? 1 : 0;                       // the two rows of a pair hold the same guided logits and draw the same numbers
   auto text_tail = [&]() -> int {
-    if (skip_text) return 0;   // the sampler streams are keyed by (seed, draw index, row, stream id), so the audio streams' draws do not move
+    if (skip_text || beam) return 0;   // (beam frames: ua2_beam_step reads the fp32 logits and chooses the ids)  the sampler streams are keyed by (seed, draw index, row, stream id), so the audio streams' draws do not move
     if (cfg)
       if (int rc = ua2_cfg_mix(h->text_logits, d.vt, d.vt, h->cfg_scale, nullptr, h->pmax_t, h->pidx_t, R / 2, s)) return rc;
     if (h->topk == 1)
@@ -744,11 +774,27 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   const bool skip_experts = mode >= 0 && (mode & UA2_FRAME_SKIP_AUDIO_EXPERTS) != 0;
   if (mode >= 0) mode &= ~(UA2_FRAME_SKIP_TEXT_HEAD | UA2_FRAME_SKIP_AUDIO_EXPERTS);
   UA2_CHECK(!skip_text || mode == 0 || mode == 2, "ua2_stage3_frame: UA2_FRAME_SKIP_TEXT_HEAD goes with the audio-feedback modes (0, 2)");
-  UA2_CHECK(!skip_experts || mode == 1, "ua2_stage3_frame: UA2_FRAME_SKIP_AUDIO_EXPERTS goes with the text-feedback mode (1)");
+  UA2_CHECK(!skip_experts || mode == 1 || mode == 3, "ua2_stage3_frame: UA2_FRAME_SKIP_AUDIO_EXPERTS goes with the text-feedback modes (1, 3)");
+  const bool beam = mode == 3;
+  if (beam) {                                     // every argument of the beam launches is checked here, before the first launch
+    UA2_CHECK(h->beam_W >= 1, "ua2_stage3_frame: mode 3 needs a beam (ua2_stage3_set_beam)");
+    UA2_CHECK(R == h->beam_W, "ua2_stage3_frame: a beam frame has one row per slot (W=%d), got R=%d", h->beam_W, R);
+    UA2_CHECK(2 * R <= h->d.max_batch, "ua2_stage3_frame: a beam of %d needs a plan of %d sequences", R, 2 * R);
+    UA2_CHECK(!(h->cfg_scale > 1.f), "ua2_stage3_frame: beam search does not combine with classifier-free guidance");
+    UA2_CHECK(h->ngram_n <= 1, "ua2_stage3_frame: beam search does not combine with the n-gram filter");
+    UA2_CHECK(h->topk == 1, "ua2_stage3_frame: beam search needs top-k = 1 (it ranks the logits itself)");
+  }
   auto body = [&](hipStream_t st) -> int {
     if (int rc = trunk_impl(h, R, true, st, skip_experts)) return rc;
-    if (int rc = heads_impl(h, R, mode == 1, st, skip_text)) return rc;
+    if (int rc = heads_impl(h, R, mode == 1 || beam, st, skip_text, beam)) return rc;
     if (mode < 0) return 0;
+    if (beam) {
+      const ua2_stage3_desc& d = h->d;
+      if (int rc = ua2_beam_step(h->text_logits, d.vt, d.vt, R, h->beam_eos, &h->beam, d.out_tokens, d.n_cb + 1, st)) return rc;
+      int32_t* const tables[3] = {const_cast<int32_t*>(d.und.page_table), const_cast<int32_t*>(d.backbone.page_table), const_cast<int32_t*>(d.gen.page_table)};
+      if (int rc = ua2_beam_reorder(R, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
+      return feedback_impl(h, R, 1, reason_eos, reason_card, st, 0);   // out_tokens' text column holds the step's ids: the text feedback as it is
+    }
     return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0);
   };
   if (!use_graph) return body(s);
@@ -756,7 +802,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   memcpy(&tbits, &h->temperature, sizeof(int));
   memcpy(&cbits, &h->cfg_scale, sizeof(int));
   // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram)
-  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;
+  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;   // (mode 3: R is the beam width, and set_beam drops the graphs with the state)
   const auto key = std::make_tuple((int)R, (int)mode | (skip_text ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram,
                                    (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);
   auto it = h->graphs.find(key);

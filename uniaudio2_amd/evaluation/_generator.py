@@ -290,6 +290,22 @@ class GeneratorBase:
                 self._model.set_ngram(0)
         return self._text_loop(L, max_frames)
 
+    @torch.inference_mode()
+    def _beam_search_text(self, tokens, tokens_mask, beam_width, length_penalty, early_stopping, max_length) -> str:
+        """The loop of generate_asr_beam_search (asr_task.py:438-576) on the device: Model_stage3.beam_search."""
+        beam_width = int(beam_width)
+        if not 1 <= beam_width <= 8:
+            raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
+        st = getattr(self._model, "_st", None)
+        if st is not None and st["B"] < 2 * beam_width:       # the K/V fork keeps a second page set: 2 W sequences
+            self._model.setup_caches(2 * beam_width)
+        self._set_sampling(1, 1.0)
+        ids, _, _ = self._model.beam_search(tokens, tokens_mask.bool(), beam_width=beam_width, length_penalty=length_penalty,
+                                            max_length=max_length, eos_id=TEXT_EOS, early_stopping=early_stopping,
+                                            chunk_frames=self.chunk_frames,
+                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
+        return self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long))
+
     def _text_loop(self, L, max_frames):
         text, frame, done = [], 0, False
         while not done and frame < max_frames:

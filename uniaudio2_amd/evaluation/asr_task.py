@@ -1,6 +1,6 @@
-"""Mirror of the reference's evaluation/asr_task.py `Generator`: greedy `generate_asr` and the n-gram-constrained
-`generate_asr_with_ngram_sampling` (:329-432).  Not mirrored: the beam search (:438-, calls a method Model_stage3 lacks —
-SURVEY Appendix A.9)."""
+"""Mirror of the reference's evaluation/asr_task.py `Generator`: greedy `generate_asr`, the n-gram-constrained
+`generate_asr_with_ngram_sampling` (:329-432) and `generate_asr_beam_search` (:438-576) — the last as a working restatement of the
+rule the reference wrote down: its own function calls a method Model_stage3 lacks (:593) and cannot run."""
 import torch
 
 from ._generator import GeneratorBase
@@ -30,6 +30,22 @@ class Generator(GeneratorBase):
         tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature, no_repeat_ngram_size=no_repeat_ngram_size,
                                    ngram_fallback=fallback_token)
+
+    @torch.inference_mode()
+    def generate_asr_beam_search(self, task_prompt, task_name, text_token=None, semantic_token=None, reason_token=None,
+                                 beam_width: int = 5, length_penalty: float = 0.6, no_repeat_ngram_size: int = 3,
+                                 early_stopping: bool = True, max_length: int = 500) -> str:
+        """asr_task.py:438-576 with the reference's parameter names, order and defaults; returns the decoded text of the best
+        hypothesis.  The search rule is the reference's: per live hypothesis the beam_width most probable next ids,
+        score += log p / ((5 + length) / 6) ** length_penalty, EOS (128001) finishes a hypothesis without entering its text, the
+        beam_width best candidates survive, the search ends when all are finished or after max_length steps, the highest score
+        wins.  It runs on the device: the hypotheses are the rows of one frame and fork their K/V page-wise
+        (Model_stage3.beam_search; the plan is re-made for 2 * beam_width sequences when it is smaller).
+        `no_repeat_ngram_size` is accepted and has no effect, exactly as in the reference, whose `_apply_ngram_constraint`
+        (:610-628) bans an always-empty set.  As for generate_asr_with_ngram_sampling the prefill is generate_asr's
+        (forward_prefix of prompt[:-1]), not the reference's training-mode forward (:476)."""
+        tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
+        return self._beam_search_text(tokens, mask, beam_width, length_penalty, early_stopping, max_length)
 
     # audio_music_caption_task.py uses the same prompt layout and loop under another name
     generate_audio_caption = generate_asr

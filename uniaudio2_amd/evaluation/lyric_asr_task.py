@@ -19,6 +19,11 @@ class Generator(_AsrGenerator):
         tokens, mask = self.prepare_lyric_asr_task(task_prompt, reason_token, semantic_token)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature)
 
+    def generate_asr_beam_search(self, *args, **kwargs):
+        """The reference's lyric Generator has no beam search either."""
+        raise ValueError("beam search is not available for lyric_recognition: the reference's lyric Generator "
+                         "(evaluation/lyric_asr_task.py) has no generate_asr_beam_search")
+
     def generate_asr_with_ngram_sampling(self, *args, **kwargs):
         """The reference's lyric Generator has no n-gram variant (the CLI's `--decode_type ngram` fails there with AttributeError)."""
         raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import Stage3Desc, W8Entry, check, lib, vp
+from .._lib import BeamPool, BeamState, Stage3Desc, W8Entry, check, lib, vp
 from .config import Config as gpt_config
 from .lit_model import GPT
 
@@ -38,6 +38,18 @@ class ModelArgs:
 
 
 _UNSET = object()      # "argument left out" where None is a meaningful value
+
+
+def backtrack_beam_log(log, slot):
+    """log [steps, W, 4] (parent, text id or -1, score bits, fin) as ua2_beam_step writes it: the text ids of the hypothesis that
+    ends in `slot` — the device never permutes histories, the host walks the parents back."""
+    ids, j = [], int(slot)
+    for t in range(len(log) - 1, -1, -1):
+        parent, tok = int(log[t][j][0]), int(log[t][j][1])
+        if tok >= 0:
+            ids.append(tok)
+        j = parent
+    return ids[::-1]
 
 
 def ragged_schedule(n_frames):
@@ -162,6 +174,7 @@ class Model_stage3(nn.Module):
         self._text_fed_back = False    # the last frame run was a text-feedback frame (every row now holds masks audio 0 / text 1)
         self._ngram = None             # (n, fallback, capacity) of the text frames' n-gram filter (set_ngram); None = off
         self._ngram_hi = 0             # upper bound of every live row's n-gram history length (host side: no device sync)
+        self._beam = None              # the running beam search (begin_beams .. end_beams); None = off
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
             self.set_order_free_rows(self.order_free_rows)
         if weight_dtype is not None:
@@ -379,10 +392,20 @@ class Model_stage3(nn.Module):
             if mode not in (0, 2):
                 raise ValueError("skip_text_head applies to the audio-feedback modes (0, 2)")
             mode = mode | 16                                  # UA2_FRAME_SKIP_TEXT_HEAD
-        if skip_audio_experts and mode != 1:
-            raise ValueError("skip_audio_experts applies to the text-feedback mode (1)")
+        if skip_audio_experts and mode not in (1, 3):
+            raise ValueError("skip_audio_experts applies to the text-feedback modes (1, 3)")
         self._need()
         st = self._st
+        if mode == 3:
+            # a beam frame: one row per slot; every step writes one record of the step log and reads one more length-penalty entry
+            bm = self._beam
+            if bm is None:
+                raise ValueError("mode 3 runs between begin_beams and end_beams")
+            if batch != bm["W"]:
+                raise ValueError(f"a beam frame has one row per slot: batch must be {bm['W']}, got {batch}")
+            if bm["steps"] + n_frames > bm["cap"]:
+                raise ValueError(f"beam step log full: {bm['steps']} + {n_frames} steps > max_length {bm['cap']} (begin_beams)")
+            bm["steps"] += n_frames
         if mode == 1 and self._ngram is not None:
             # every text frame appends one id to each row's n-gram history: never filter against a truncated one
             if self._ngram_hi + n_frames > self._ngram[2]:
@@ -408,7 +431,7 @@ class Model_stage3(nn.Module):
             m = mode | 32 if (skip_audio_experts and self._text_fed_back) else mode
             check(lib.ua2_stage3_frame(self._h, batch, m, reason_eos, reason_card, int(use_graph), s),
                   "ua2_stage3_frame")
-            self._text_fed_back = mode == 1
+            self._text_fed_back = mode in (1, 3)
             if frame_events is not None:           # measurement hook: one event after every frame (bench.py p50 / p99)
                 frame_events[i].record()
         return st["frame_log"][start:start + n_frames, :batch]
@@ -515,6 +538,130 @@ class Model_stage3(nn.Module):
         self._pos_hi = hi
         self._load_rows(tokens.reshape(B, W), tokens_mask.reshape(B, W), pos, torch.arange(B, device=tokens.device))
         self._st["forbid"][:B].fill_(int(forbid_prefix))
+
+    # ---- beam search of the text loop (include/ua2hip.h ua2_beam_step / ua2_beam_reorder) -------------------------
+    def _static_page_tables(self):
+        """Sequence b owns pages [b * max_pages, (b + 1) * max_pages): the layout setup_caches starts from."""
+        for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert):
+            pt = g.kv_cache.page_table
+            pt.copy_(torch.arange(pt.numel(), dtype=torch.int32, device=pt.device).view_as(pt))
+
+    @torch.inference_mode()
+    def begin_beams(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
+                    eos_id: int = 128001):
+        """Start of a beam search over one prompt: tokens (L, 9), tokens_mask (L, 9).  Prefills prompt[:-1] as sequence 0, loads the
+        prompt's last frame into the W = beam_width rows of the decode state, attaches the beam state to the executor and gives every
+        slot its view of the prompt's K/V (shared full pages, a copy of the partial one).  Slot 0 starts live with score 0, the others
+        dead.  Run steps with generate_frames(n, W, 3); end_beams() must follow (beam_search does so in a `finally`)."""
+        self._need()
+        st = self._st
+        W, max_length = int(beam_width), int(max_length)
+        if not 1 <= W <= 8:
+            raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
+        if st["B"] < 2 * W:
+            raise ValueError(f"beam search with beam_width={W} needs setup_caches(max_batch_size={2 * W}) or larger (the pages of "
+                             f"sequences {W}..{2 * W - 1} are the second page set of the K/V fork); this plan holds {st['B']}")
+        if max_length < 1:
+            raise ValueError("max_length must be >= 1")
+        if self._cfg > 1.0 or self._ngram is not None or (self._sampling is not None and self._sampling[0] != 1):
+            raise ValueError("beam search runs without classifier-free guidance, without the n-gram filter and with topk = 1")
+        if self._beam is not None:
+            raise ValueError("a beam search is already running (end_beams)")
+        dev = st["device"]
+        tokens, tokens_mask = tokens.to(dev), tokens_mask.bool().to(dev)
+        L = tokens.shape[0]
+        self._check_positions(L - 1 + max_length - 1)
+        self.reset_caches()
+        self._static_page_tables()
+        pos = torch.arange(0, L, device=dev).unsqueeze(0)
+        self.forward_prefix(tokens[None, :-1], tokens_mask=tokens_mask[None], input_pos=pos[:, :-1])
+        self.begin_decode(tokens[-1:].unsqueeze(0).repeat(W, 1, 1), tokens_mask[-1:].unsqueeze(0).repeat(W, 1, 1),
+                          torch.tensor([L - 1], device=dev))
+        # state: one int32 buffer carved into the fields of ua2_beam_state (score and cand_logp are fp32 views of their words)
+        words = torch.zeros(4 * 8 + 4 + 2 * 64 + max_length * W * 4, dtype=torch.int32, device=dev)
+        f = lambda a, n: words[a:a + n]
+        score, fin, ln, parent, ctrl = f(0, 8).view(torch.float32), f(8, 8), f(16, 8), f(24, 8), f(32, 4)
+        cand_logp, cand_id, log = f(36, 64).view(torch.float32), f(100, 64), f(164, max_length * W * 4)
+        score.fill_(float("-inf")); score[0] = 0.0
+        fin.fill_(2); fin[0] = 0
+        ctrl[1] = -1
+        lp_inv = torch.tensor([1.0 / (((5 + n) / 6) ** float(length_penalty)) for n in range(max_length + 1)], dtype=torch.float64)
+        lp_inv = lp_inv.to(torch.float32).to(dev)
+        bs = BeamState(score.data_ptr(), fin.data_ptr(), ln.data_ptr(), parent.data_ptr(), ctrl.data_ptr(), cand_logp.data_ptr(),
+                       cand_id.data_ptr(), log.data_ptr(), max_length, lp_inv.data_ptr(), max_length + 1)
+        pools, tables = [], []
+        esz = torch.empty(0, dtype=st["dtype"]).element_size()
+        for ti, g in enumerate((self.audio_understanding_expert, self.backbone, self.audio_generation_expert)):
+            kv, cfg = g.kv_cache, g.config
+            tables.append(kv.page_table)
+            if (cfg.head_size * esz) % 16:
+                raise ValueError("beam search copies K/V in 16-byte units: head_size * element size must be a multiple of 16")
+            pools += [BeamPool(t.data_ptr(), ti, cfg.n_query_groups, cfg.head_size * esz, 0) for t in kv.k + kv.v]
+        raw = bytes((BeamPool * len(pools))(*pools))
+        pools_dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+        tabs = (vp * 3)(*[t.data_ptr() for t in tables])
+        max_pages = self.backbone.kv_cache.max_pages
+        self._beam = dict(W=W, cap=max_length, steps=0, eos=int(eos_id), L=L, words=words, score=score, fin=fin, len=ln, ctrl=ctrl,
+                          log=log.view(max_length, W, 4), lp_inv=lp_inv, pools=pools_dev, state=bs)
+        check(lib.ua2_stage3_set_beam(self._h, W, int(eos_id), C.byref(bs), pools_dev.data_ptr(), len(pools)), "ua2_stage3_set_beam")
+        # the start of the fork: all parents 0, before the first frame (pos_add 0)
+        check(lib.ua2_beam_reorder(W, None, st["row_pos"].data_ptr(), 0, pools_dev.data_ptr(), len(pools), tabs, 3, st["B"], max_pages,
+                                   ops.stream()), "ua2_beam_reorder")
+
+    def beams_all_finished(self) -> int:
+        """The step at which all W slots were first finished, -1 while one is live (one 4-byte read: the only thing the host reads
+        between chunks)."""
+        return int(self._beam["ctrl"][1].item())
+
+    @torch.inference_mode()
+    def end_beams(self):
+        """End of a beam search: reads the state and the step log, recovers every slot's text ids by walking the log backwards,
+        restores the static page tables and detaches the beam state — a later greedy call behaves as if no search had happened.
+        Slots still live count as finished with their score unchanged.  Returns (best ids, best score, hypotheses) with hypotheses =
+        [dict(ids, score, finished)] in slot order; the best is the highest score, the first such slot on ties."""
+        bm, self._beam = self._beam, None
+        try:
+            if bm is None:
+                raise ValueError("no beam search is running (begin_beams)")
+            torch.cuda.synchronize()
+            ctrl = bm["ctrl"].cpu().tolist()
+            steps = min(ctrl[0], bm["cap"])
+            log = bm["log"][:steps].cpu().numpy()
+            score, fin = bm["score"][:bm["W"]].cpu().tolist(), bm["fin"][:bm["W"]].cpu().tolist()
+        finally:
+            if self._h is not None:
+                check(lib.ua2_stage3_set_beam(self._h, 0, 0, None, None, 0), "ua2_stage3_set_beam")
+                self._static_page_tables()
+        self.beam_info = dict(steps=steps, all_finished=ctrl[1])       # steps run; the step at which all slots were first finished (-1: never)
+        hyps = [dict(ids=backtrack_beam_log(log, j), score=float(score[j]), finished=fin[j] == 1) for j in range(bm["W"])]
+        best = max(range(bm["W"]), key=lambda j: (hyps[j]["score"] if fin[j] != 2 else float("-inf"), -j))
+        return hyps[best]["ids"], hyps[best]["score"], hyps
+
+    @torch.inference_mode()
+    def beam_search(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
+                    eos_id: int = 128001, early_stopping: bool = True, chunk_frames: int = 16, use_graph: bool = True,
+                    skip_audio_experts: bool = True):
+        """Beam search over the text continuation of one prompt (the reference's evaluation/asr_task.py:438-576 rule,
+        corrected).  tokens / tokens_mask (L, 9).  The W hypotheses run as the W rows of one frame; the search stops when all W are
+        finished or after max_length steps.  With all W finished a further step reproduces the beam, so the result does not depend on
+        chunk_frames, and stopping there is what early_stopping=False would compute as well (the reference keeps looping over
+        finished beams without changing them).  Returns (best ids, best score, all W hypotheses)."""
+        self.begin_beams(tokens, tokens_mask, beam_width, length_penalty, max_length, eos_id)
+        try:
+            done = 0
+            while done < max_length:
+                n = min(int(chunk_frames), max_length - done)
+                self.generate_frames(n, int(beam_width), 3, use_graph=use_graph, skip_audio_experts=skip_audio_experts)
+                done += n
+                if self.beams_all_finished() >= 0:
+                    break
+        except BaseException:
+            try:
+                self.end_beams()
+            except Exception:
+                pass
+            raise
+        return self.end_beams()
 
     def buffer(self, name: str, rows: int):
         """Intermediate buffers for tests: 'h_final' (rows, C), 'text_logits' (rows, Vt), 'audio_logits' (rows, 8, Va)."""

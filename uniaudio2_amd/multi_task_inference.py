@@ -17,9 +17,14 @@ Differences, all explicit:
   * --decode_type ngram (ASR / Yue_ASR: generate_asr_with_ngram_sampling, greedy, n = 3, as the reference's :310-322) runs the
     n-gram filter on the device; its prefill is generate_asr's (the reference's trains-mode prefill leaves the experts' caches
     empty, evaluation/asr_task.py).  lyric_recognition + ngram raises ValueError (the reference's lyric Generator has no such
-    method: AttributeError); the caption / understanding / s2t tasks ignore the flag, as the reference does.  --decode_type
-    beamsearch raises NotImplementedError (the reference's beam search is dead code); so does any non-greedy
-    --decode_type for the generation tasks.
+    method: AttributeError); the caption / understanding / s2t tasks ignore the flag, as the reference does.
+  * Beam search: `--beam_width N` (N in 1..8; default 0 = off) with `--length_penalty` (default 0.6), for --task ASR / Yue_ASR under
+    --decode_type greedy, runs Generator.generate_asr_beam_search — the reference's search rule (evaluation/asr_task.py:438-576) on the
+    device, the N hypotheses as the rows of one frame.  --decode_type beamsearch itself still raises NotImplementedError: the
+    reference's function behind that flag cannot run (it calls a method its model lacks), and the message points to --beam_width.
+    --beam_width with --decode_type ngram, with lyric_recognition or with a caption / understanding / s2t task raises ValueError.
+    Any non-greedy --decode_type for the generation tasks raises NotImplementedError.  No trained checkpoint ships with this
+    repository: the search is verified on toy and random weights, not for task quality.
   * Encoding raw audio (--audio / --audio_dir; the understanding tasks and the speech_s2s source) runs the codec's three frozen
     SSL encoders (Whisper, WavLM, BEST-RQ) on the device when the codec yaml (--codec_config) names all three checkpoints
     (`whisper_path`, `wav_lm_path`, `best_rq_ckpt`): `tokenize(path)`, the `{name}_reason.pt` / `{name}_semantic.pt` pair written to
@@ -172,7 +177,22 @@ def _check_understanding_decode(args, task):
     """multi_task_inference.py:310-322 of the reference: ngram reaches generate_asr_with_ngram_sampling for the ASR tasks and is
     ignored by the others; its lyric Generator lacks the method.  Beam search is dead code there."""
     if args.decode_type == "beamsearch":
-        raise NotImplementedError("--decode_type beamsearch is not on the device path (the reference's beam search is dead code)")
+        raise NotImplementedError("--decode_type beamsearch is not routed: the reference's generate_asr_beam_search cannot run (it calls "
+                                  "Model_stage3.get_next_logits, which does not exist); the working search is --beam_width N "
+                                  "(with --decode_type greedy, --task ASR / Yue_ASR)")
+    bw = int(getattr(args, "beam_width", 0) or 0)
+    if bw < 0 or bw > 8:
+        raise ValueError(f"--beam_width must be in 0..8 (0 = off), got {bw}")
+    if bw >= 1:
+        if args.decode_type == "ngram":
+            raise ValueError("--beam_width does not combine with --decode_type ngram: the reference's beam search bans no n-gram "
+                             "(its _apply_ngram_constraint works on an empty set) and its n-gram loop is greedy")
+        if task == "lyric_recognition":
+            raise ValueError("--beam_width is not available for lyric_recognition: the reference's lyric Generator "
+                             "(evaluation/lyric_asr_task.py) has no generate_asr_beam_search")
+        if task not in ("asr", "yue_asr"):
+            raise ValueError(f"--beam_width is not available for {task}: the reference defines beam search for the ASR Generator "
+                             "only (evaluation/asr_task.py); the caption / understanding / s2t generators have no such method")
     if args.decode_type == "ngram" and task == "lyric_recognition":
         raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "
                          "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")
@@ -235,6 +255,8 @@ def run_understanding(args):
                                            is_cfg=args.use_cfg)
     if raw_audio:
         token_dir, names = _encode_audio_to_tokens(args, generator, args.output_dir, "pass --reason_pt + --semantic_pt or --token_dir")
+    if int(getattr(args, "beam_width", 0) or 0) >= 1:            # the K/V fork of a beam of N keeps two page sets: a plan of 2 N sequences
+        model.setup_caches(2 * int(args.beam_width))
     task_prompt = _get_prompt_tensor(args, generator._text_tokenizer, args.task)
     results_path = args.results or os.path.join(args.output_dir, f"{task}_results.txt")
     os.makedirs(os.path.dirname(results_path) or ".", exist_ok=True)
@@ -268,6 +290,9 @@ def run_understanding(args):
             elif task in ("audio_caption", "music_caption"):                                       # :329-342
                 text_out = generator.generate_audio_caption(task_prompt, task_name=task, reason_token=reason, semantic_token=semantic,
                                                             temperature=args.temperature, topk=1, cfg_scale=args.cfg_scale)
+            elif int(getattr(args, "beam_width", 0) or 0) >= 1:                                     # asr, yue_asr (checked above)
+                text_out = generator.generate_asr_beam_search(task_prompt, task_name=task, reason_token=reason, semantic_token=semantic,
+                                                              beam_width=args.beam_width, length_penalty=args.length_penalty)
             elif args.decode_type == "ngram":                                                       # :316-321: asr, yue_asr
                 text_out = generator.generate_asr_with_ngram_sampling(task_prompt, task_name=task, reason_token=reason,
                                                                       semantic_token=semantic, temperature=args.temperature, topk=1,
@@ -513,6 +538,12 @@ def get_parser():
                    help="stage 1, bf16 (extension): LM launches of at least this many rows (batched prefill, decode frames of that many "
                         "sequences) take the order-free 256-row-tile GEMM — faster, but a sequence's ids may then depend on what shares "
                         "its batch.  Default 0 = off: every row keeps the bits of its single-sequence run")
+    p.add_argument("--beam_width", type=int, default=0,
+                   help="ASR / Yue_ASR with --decode_type greedy (extension): N in 1..8 decodes with beam search over N hypotheses on the "
+                        "device (the reference's generate_asr_beam_search rule, which its own --decode_type beamsearch cannot run).  "
+                        "Default 0 = off")
+    p.add_argument("--length_penalty", type=float, default=0.6,
+                   help="--beam_width: exponent of the length normalisation ((5 + length) / 6) ** length_penalty (the reference's default 0.6)")
     p.add_argument("--batch_size", type=int, default=1,
                    help="utterances decoded together per GPU (extension; TTS / Yue_TTS with --text_file; 1 = one by one as the reference)")
     return p
