@@ -267,7 +267,7 @@ int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
  * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
- * of ua2_skinny.hip: main + combine count once); -1 for an unknown
+ * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
  * call getenv on every launch); a process that changes one of them afterwards (the tests do) calls this to have them read again. */
@@ -831,6 +831,16 @@ int ua2_stage3_feedback(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_e
  * (it consumes the prompt's last token, usually an audio step) and any sequence that will see an audio step later must run without it:
  * the skipped positions of the experts' caches are left unwritten. */
 #define UA2_FRAME_SKIP_AUDIO_EXPERTS 32
+/* mode 0 | UA2_FRAME_DEFER_TEXT_HEAD (feedback mode 0 only; not together with UA2_FRAME_SKIP_TEXT_HEAD): the frame is a
+ * UA2_FRAME_SKIP_TEXT_HEAD frame — no lm_head, no rider, no text sample, -1 in the log's text column, 0 as the next frame's masked text
+ * token — that also keeps its R rows of h_final (fp32) in slot counters[0] % cap_frames of a stash ring of the plan, cap_frames =
+ * ua2_stage3_defer_rows() / R.  In that loop the text id has no consumer inside the model (it is fed back under a zero mask), so the
+ * text ids of different frames depend neither on each other nor on anything else the loop computes: ua2_stage3_text_flush computes
+ * them for up to UA2_DEFER_CAP_ROWS stashed rows with ONE pass over lm_head's weights instead of one pass per frame.  At R <= 4 the
+ * copy is part of the feedback kernel (no launch is added to the frame); more rows take one small copy launch.  The flag and
+ * cap_frames select the captured graph. */
+#define UA2_FRAME_DEFER_TEXT_HEAD 64
+#define UA2_DEFER_CAP_ROWS 64
 /* mode 3 (with or without UA2_FRAME_SKIP_AUDIO_EXPERTS, under mode 1's precondition): a beam-search frame of R = W rows — trunk,
  * lm_head, the beam step on its fp32 logits, the K/V fork, then the text feedback of mode 1 with the ids the step chose (tokens
  * (0 x n_cb, id), masks (0.., 1), row_pos += 1; the frame log's text column holds them).  Checked before any launch: a beam is
@@ -838,6 +848,18 @@ int ua2_stage3_feedback(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_e
  * count within the state's log and length-penalty tables and every position within the caches. */
 int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card,
                      int32_t use_graph, void* stream);
+/* Rows of the stash ring in use: UA2_DEFER_CAP_ROWS, or UA2_DEFER_ROWS=n from the environment (clamped to 1 .. UA2_DEFER_CAP_ROWS; tests and
+ * sweeps), or 0 under UA2_NO_DEFER_TEXT_HEAD=1 (A/B: callers then run every frame undeferred).  Read once; ua2_debug_refresh_env re-reads. */
+int32_t ua2_stage3_defer_rows(void);
+/* The text ids of frames frame0 .. frame0 + n - 1 (log slots: the values counters[0] had when the UA2_FRAME_DEFER_TEXT_HEAD frames of R
+ * rows ran), stream-ordered behind them: lm_head over the n * R stashed rows — the launch ua2_stage3_heads builds for it, under
+ * UA2_SUM_ORDER_INVARIANT, through the same launcher, so a row's logits and arg-max partials carry the bits of its per-frame launch
+ * whichever kernel serves the row count — then the arg-max per row (tie and all-NaN rules of ua2_argmax_embed) into
+ * frame_log[((frame0 + j) * max_rows + m) * (n_cb + 1) + 0] for frame0 + j < log_frames.  The window must not wrap the ring
+ * (frame0 % cap_frames + n <= cap_frames): callers flush whenever a frame fills the last slot and once more at the end of a run of
+ * deferred frames, before the ring is written again.  Greedy, unguided plans (top-k = 1, no classifier-free guidance); the logits of a
+ * flush are scratch — "text_logits" keeps what the last undeferred frame wrote.  Counted as "text_flush" by ua2_debug_kernel_launches. */
+int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, int32_t n, void* stream);
 /* Expose intermediate buffers for tests: name in {"h_final","text_logits","audio_logits"}. */
 float* ua2_stage3_buffer(ua2_stage3* h, const char* name);
 

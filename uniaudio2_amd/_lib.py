@@ -182,6 +182,8 @@ _EXPORTS = {
     "ua2_stage3_feedback": (C.c_int, [vp, i32, i32, i32, i32, vp]),
     "ua2_stage3_frame": (C.c_int, [vp, i32, i32, i32, i32, i32, vp]),
     "ua2_stage3_buffer": (C.POINTER(C.c_float), [vp, C.c_char_p]),
+    "ua2_stage3_defer_rows": (i32, []),
+    "ua2_stage3_text_flush": (C.c_int, [vp, i32, i32, i32, vp]),
 }
 
 

@@ -26,6 +26,13 @@ struct ua2_stage3 {
   float *xa, *text, *xb, *hbuf, *xg, *hfin, *q, *act, *yattn, *xd, *curr_h;
   float *text_logits, *audio_logits, *pmax_t, *pmax_a;
   int32_t *pidx_t, *pidx_a;
+  // deferred text head (UA2_FRAME_DEFER_TEXT_HEAD / ua2_stage3_text_flush): a ring of UA2_DEFER_CAP_ROWS h_final rows (fp32, as lm_head's
+  // UA2_PRO_CAST prologue reads them) and the flush launch's own logits, arg-max partials and operand scratch — the per-frame
+  // text_logits / pmax_t / gemm_ws hold max_batch (max_rows) rows and keep what the last undeferred frame wrote
+  float *defer_stash = nullptr, *defer_logits = nullptr, *defer_pmax = nullptr;
+  int32_t* defer_pidx = nullptr;
+  void* defer_ws = nullptr;
+  size_t defer_ws_bytes = 0;
   void* gemm_ws;               // operand scratch of the large-M linear kernel (max_rows x widest K)
   size_t gemm_ws_bytes;
   void* act_ws;                // packed SwiGLU output handed straight to the down-projection (max_rows x widest intermediate)
@@ -80,7 +87,8 @@ size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
 
 struct Carve {
   size_t xa, text, xb, hbuf, xg, hfin, q, act, yattn, xd, curr_h, text_logits, audio_logits, pmax_t, pidx_t,
-      pmax_a, pidx_a, gemm_ws, gemm_ws_floats, act_ws, xh, xpk, ssq, split, split_floats, ptab_y, ptab_h, ptab_ssq, ptab_rows, ptab_q, ptab_k, ptab_v, ptab_qkv, range, range_floats, total;
+      pmax_a, pidx_a, gemm_ws, gemm_ws_floats, act_ws, xh, xpk, ssq, split, split_floats, ptab_y, ptab_h, ptab_ssq, ptab_rows, ptab_q, ptab_k, ptab_v, ptab_qkv, range, range_floats,
+      defer_stash, defer_logits, defer_pmax, defer_pidx, defer_ws, defer_ws_floats, total;
 };
 
 Carve carve(const ua2_stage3_desc& d) {
@@ -130,6 +138,11 @@ Carve carve(const ua2_stage3_desc& d) {
     c.ptab_k = take((rows * kvw * esz + 3) / 4);
     c.ptab_v = take((rows * kvw * esz + 3) / 4);
   }
+  // deferred text head: UA2_DEFER_CAP_ROWS rows of h_final, of lm_head's logits and partials, and the many-row kernels' packed operand
+  c.defer_stash = take((size_t)UA2_DEFER_CAP_ROWS * C); c.defer_logits = take((size_t)UA2_DEFER_CAP_ROWS * d.vt);
+  c.defer_pmax = take((size_t)UA2_DEFER_CAP_ROWS * npt); c.defer_pidx = take((size_t)UA2_DEFER_CAP_ROWS * npt);
+  c.defer_ws_floats = ua2_linear_workspace_bytes(d.dtype, UA2_DEFER_CAP_ROWS, (int64_t)C) / sizeof(float);
+  c.defer_ws = take(c.defer_ws_floats);
   c.total = off;
   return c;
 }
@@ -310,9 +323,17 @@ __global__ void bump_kernel(int32_t* c) { c[0] += 1; }
 __global__ void feedback_kernel(int R, int ncb, int mode, int reason_eos, int reason_card, int log_frames,
                                 int max_rows, int32_t* __restrict__ tokens, uint8_t* __restrict__ mask,
                                 int32_t* __restrict__ row_pos, int32_t* __restrict__ forbid,
-                                const int32_t* __restrict__ out, int32_t* __restrict__ log, int32_t* counters, int no_text) {
+                                const int32_t* __restrict__ out, int32_t* __restrict__ log, int32_t* counters, int no_text,
+                                const float* __restrict__ hfin, float* __restrict__ stash, int C, int cap_frames) {
   const int frame = counters[0];
   const int w = ncb + 1;
+  // UA2_FRAME_DEFER_TEXT_HEAD, frames of a few rows: this frame's h_final rows go into slot frame % cap_frames of the stash ring (the
+  // slot is a device value — the frame is a replayed graph).  cap_frames * R rows fit the ring (checked by the launcher); C % 4 == 0.
+  if (stash && frame >= 0) {
+    const size_t n4 = (size_t)R * C / 4;
+    float4* dst = reinterpret_cast<float4*>(stash + (size_t)(frame % cap_frames) * R * C);
+    for (size_t i = threadIdx.x; i < n4; i += blockDim.x) dst[i] = reinterpret_cast<const float4*>(hfin)[i];
+  }
   const bool audio_fb = (mode == 0 || mode == 2);
   for (int m = threadIdx.x; m < R; m += blockDim.x) {
     const int32_t* own = out + (size_t)m * w;
@@ -335,6 +356,46 @@ __global__ void feedback_kernel(int R, int ncb, int mode, int reason_eos, int re
   }
   __syncthreads();
   if (threadIdx.x == 0) counters[0] = frame + 1;
+}
+
+// the same stash for frames of more rows, as a launch of its own in front of the feedback (which advances counters[0]): one block per row
+__global__ void stash_rows_kernel(const float* __restrict__ hfin, float* __restrict__ stash, int R, int C, int cap_frames, const int32_t* __restrict__ counters) {
+  const int frame = counters[0], m = blockIdx.x;
+  if (frame < 0 || m >= R) return;
+  const float4* src = reinterpret_cast<const float4*>(hfin + (size_t)m * C);
+  float4* dst = reinterpret_cast<float4*>(stash + ((size_t)(frame % cap_frames) * R + m) * C);
+  for (int i = threadIdx.x; i < C / 4; i += blockDim.x) dst[i] = src[i];
+}
+
+// ua2_stage3_text_flush: row r = j * R + m of the flush launch is sequence m of frame frame0 + j.  The arg-max over lm_head's
+// per-16-column partials, as argmax_embed_kernel takes it (same candidates, same order, same tie and all-NaN rules: ua2_row_token),
+// written into the text column of that frame's log row.
+__global__ __launch_bounds__(256) void text_flush_kernel(int R, int n_part, int limit, const float* __restrict__ pmax, const int32_t* __restrict__ pidx,
+                                                         int32_t* __restrict__ log, int frame0, int log_frames, int max_rows, int w) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  __shared__ int tok_s;
+  const int r = blockIdx.x, j = r / R, m = r - j * R;
+  float bv = -INFINITY;
+  int bi = UA2_TOK_NONE;
+  for (int p = threadIdx.x; p < n_part; p += blockDim.x) {
+    const float v = pmax[(size_t)r * n_part + p];
+    const int i = pidx[(size_t)r * n_part + p];
+    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+  }
+  const int tok = ua2_row_token(bv, bi, limit, sv, si, &tok_s, [&] {
+    int lo = UA2_TOK_NONE;
+    for (int p = threadIdx.x; p < n_part; p += blockDim.x) lo = min(lo, pidx[(size_t)r * n_part + p]);
+    return lo;
+  });
+  if (threadIdx.x == 0 && frame0 + j < log_frames) log[((size_t)(frame0 + j) * max_rows + m) * w] = tok;
+}
+
+// rows of the stash ring in use: UA2_DEFER_ROWS=n (1 .. UA2_DEFER_CAP_ROWS, the default) for tests and sweeps; UA2_NO_DEFER_TEXT_HEAD=1: none (A/B)
+int defer_rows() {
+  static Ua2EnvInt rows{"UA2_DEFER_ROWS", UA2_DEFER_CAP_ROWS}, off{"UA2_NO_DEFER_TEXT_HEAD", 0};
+  if (off.get() == 1) return 0;
+  return std::min(std::max(rows.get(), 1), (int)UA2_DEFER_CAP_ROWS);
 }
 
 // table rows row0 .. row0 + n - 1: position of the step that consumes row g = i * va + id is i + 1; page table of the scratch cache: row r -> page r
@@ -387,6 +448,8 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
   h->act_ws = b + c.act_ws;
   h->xh = b + c.xh; h->xpk = b + c.xpk; h->ssq = b + c.ssq;
   h->split_ws = c.split_floats ? b + c.split : nullptr; h->split_ws_bytes = c.split_floats * sizeof(float);
+  h->defer_stash = b + c.defer_stash; h->defer_logits = b + c.defer_logits; h->defer_pmax = b + c.defer_pmax;
+  h->defer_pidx = (int32_t*)(b + c.defer_pidx); h->defer_ws = b + c.defer_ws; h->defer_ws_bytes = c.defer_ws_floats * sizeof(float);
   h->range_ws = c.range_floats ? b + c.range : nullptr; h->range_ws_bytes = c.range_floats * sizeof(float);
   // the scaled contract is the bf16 executor's (fp32 keeps the reference's operation order); A/B hook: UA2_NO_SCALED=1
   // Plans for more than 64 live sequences keep the prep form as well: at 256 rows the consumers' per-pass row-scale work and
@@ -746,7 +809,10 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
 
 extern "C" int ua2_stage3_heads(ua2_stage3* h, int32_t R, void* stream) { return heads_impl(h, R, false, stream); }
 
-static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card, void* stream, int no_text) {
+// defer_frames > 0 (UA2_FRAME_DEFER_TEXT_HEAD): the frame's h_final rows go into the stash ring of that many frame slots.  Up to 4 rows the
+// copy (48 KB at C = 3072) is part of feedback_kernel's one block — no launch is added to the B = 1 frame; more rows take a launch of
+// one block per row in front of it (one block would copy 390 KB at 32 rows: longer than the 3.5 us of a launch).
+static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card, void* stream, int no_text, int defer_frames = 0) {
   UA2_CHECK(h && R > 0 && R <= h->d.max_rows && mode >= 0 && mode <= 2, "ua2_stage3_feedback: bad arguments");
   const ua2_stage3_desc& d = h->d;
   if (mode == 1 && h->ngram_n > 1) {   // asr_task.py:371-375: the filtered id is what the log records and the next frame consumes
@@ -754,9 +820,20 @@ static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_
     if (int rc = ua2_ngram_filter(d.out_tokens, d.n_cb + 1, R, h->ngram_n, h->ngram_fallback, h->ngram_hist, h->ngram_hist_len,
                                   h->ngram_cap, stream)) return rc;
   }
+  const int C = d.backbone.n_embd;
+  bool fold = false;
+  if (defer_frames > 0) {
+    UA2_CHECK(mode == 0 && R <= d.max_batch && (int64_t)defer_frames * R <= UA2_DEFER_CAP_ROWS && C % 4 == 0,
+              "ua2_stage3_feedback: stash of %d frames x %d rows (mode %d) does not fit the ring of %d rows", defer_frames, R, mode, UA2_DEFER_CAP_ROWS);
+    fold = R <= 4;
+    if (!fold) {
+      hipLaunchKernelGGL(stash_rows_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, h->hfin, h->defer_stash, R, C, defer_frames, d.counters);
+      UA2_LAUNCH_CHECK();
+    }
+  }
   hipLaunchKernelGGL(feedback_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, R, d.n_cb, mode, reason_eos,
                      reason_card, d.log_frames, d.max_rows, d.tokens, d.mask, d.row_pos, d.forbid, d.out_tokens,
-                     d.frame_log, d.counters, no_text);
+                     d.frame_log, d.counters, no_text, h->hfin, fold ? h->defer_stash : nullptr, C, fold ? defer_frames : 1);
   UA2_LAUNCH_CHECK();
   return 0;
 }
@@ -770,9 +847,18 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
                                 int32_t use_graph, void* stream) {
   UA2_CHECK(h != nullptr, "ua2_stage3_frame: NULL handle");
   hipStream_t s = (hipStream_t)stream;
-  const bool skip_text = mode >= 0 && (mode & UA2_FRAME_SKIP_TEXT_HEAD) != 0;
+  const bool defer = mode >= 0 && (mode & UA2_FRAME_DEFER_TEXT_HEAD) != 0;
+  UA2_CHECK(!defer || (mode & UA2_FRAME_SKIP_TEXT_HEAD) == 0, "ua2_stage3_frame: UA2_FRAME_DEFER_TEXT_HEAD and UA2_FRAME_SKIP_TEXT_HEAD exclude each other");
+  const bool skip_text = defer || (mode >= 0 && (mode & UA2_FRAME_SKIP_TEXT_HEAD) != 0);     // a deferring frame is a skipping frame that keeps h_final
   const bool skip_experts = mode >= 0 && (mode & UA2_FRAME_SKIP_AUDIO_EXPERTS) != 0;
-  if (mode >= 0) mode &= ~(UA2_FRAME_SKIP_TEXT_HEAD | UA2_FRAME_SKIP_AUDIO_EXPERTS);
+  if (mode >= 0) mode &= ~(UA2_FRAME_SKIP_TEXT_HEAD | UA2_FRAME_SKIP_AUDIO_EXPERTS | UA2_FRAME_DEFER_TEXT_HEAD);
+  int defer_frames = 0;                            // frame slots of the stash ring: baked into the recorded frame, so part of its key
+  if (defer) {
+    UA2_CHECK(mode == 0, "ua2_stage3_frame: UA2_FRAME_DEFER_TEXT_HEAD goes with feedback mode 0");
+    UA2_CHECK(R > 0 && R <= h->d.max_batch, "ua2_stage3_frame: R=%d out of range", R);
+    defer_frames = defer_rows() / R;
+    UA2_CHECK(defer_frames >= 1, "ua2_stage3_frame: the stash ring (%d rows: UA2_DEFER_ROWS / UA2_NO_DEFER_TEXT_HEAD) holds no frame of %d rows", defer_rows(), R);
+  }
   UA2_CHECK(!skip_text || mode == 0 || mode == 2, "ua2_stage3_frame: UA2_FRAME_SKIP_TEXT_HEAD goes with the audio-feedback modes (0, 2)");
   UA2_CHECK(!skip_experts || mode == 1 || mode == 3, "ua2_stage3_frame: UA2_FRAME_SKIP_AUDIO_EXPERTS goes with the text-feedback modes (1, 3)");
   const bool beam = mode == 3;
@@ -795,7 +881,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
       if (int rc = ua2_beam_reorder(R, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
       return feedback_impl(h, R, 1, reason_eos, reason_card, st, 0);   // out_tokens' text column holds the step's ids: the text feedback as it is
     }
-    return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0);
+    return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0, defer_frames);
   };
   if (!use_graph) return body(s);
   int tbits, cbits;
@@ -803,7 +889,8 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   memcpy(&cbits, &h->cfg_scale, sizeof(int));
   // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram)
   const int ngram = mode == 1 ? h->ngram_n << 8 : 0;   // (mode 3: R is the beam width, and set_beam drops the graphs with the state)
-  const auto key = std::make_tuple((int)R, (int)mode | (skip_text ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram,
+  const int dkey = defer ? (UA2_FRAME_DEFER_TEXT_HEAD | defer_frames << 8) : 0;   // (mode 0 only: the n-gram bits belong to mode 1)
+  const auto key = std::make_tuple((int)R, (int)mode | (skip_text && !defer ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram | dkey,
                                    (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
@@ -823,6 +910,35 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
     it = h->graphs.emplace(key, exec).first;
   }
   UA2_HIP(hipGraphLaunch(it->second, s));
+  return 0;
+}
+
+extern "C" int32_t ua2_stage3_defer_rows(void) { return defer_rows(); }
+
+extern "C" int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, int32_t n, void* stream) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_text_flush: NULL handle");
+  const ua2_stage3_desc& d = h->d;
+  UA2_CHECK(R > 0 && R <= d.max_batch, "ua2_stage3_text_flush: R=%d out of range", R);
+  const int cap_frames = defer_rows() / R;
+  UA2_CHECK(cap_frames >= 1, "ua2_stage3_text_flush: the stash ring (%d rows) holds no frame of %d rows", defer_rows(), R);
+  UA2_CHECK(frame0 >= 0 && n >= 1 && n <= cap_frames && frame0 % cap_frames + n <= cap_frames && (int64_t)frame0 + n <= 0x7fffffff,
+            "ua2_stage3_text_flush: window [%d, %d + %d) wraps the ring of %d frames", frame0, frame0, n, cap_frames);
+  UA2_CHECK(h->topk == 1 && !(h->cfg_scale > 1.f && R > 1), "ua2_stage3_text_flush: the deferred text head is the greedy, unguided one");
+  const int C = d.backbone.n_embd, M = n * R;      // M <= cap_frames * R <= UA2_DEFER_CAP_ROWS: the rows every defer_* buffer holds
+  hipStream_t s = (hipStream_t)stream;
+  // the launch heads_impl builds for lm_head, over the stashed rows: the launcher picks the kernel by M as it does for a batch, and a
+  // row's bits depend on neither (row invariance), so ids and logits are those of the per-frame launch
+  ua2_linear_args a;
+  memset(&a, 0, sizeof(a));
+  a.workspace = h->defer_ws; a.workspace_bytes = h->defer_ws_bytes;
+  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
+  a.M = M; a.N = d.vt; a.K = C; a.x = h->defer_stash + (size_t)(frame0 % cap_frames) * R * C; a.ldx = C; a.w0 = d.lm_head;
+  a.y = h->defer_logits; a.ldy = d.vt; a.part_max = h->defer_pmax; a.part_idx = h->defer_pidx; a.sum_order = UA2_SUM_ORDER_INVARIANT;
+  if (int rc = lin(h, a, s)) return rc;
+  hipLaunchKernelGGL(text_flush_kernel, dim3(M), dim3(256), 0, s, R, h->npart_t, d.vt, h->defer_pmax, h->defer_pidx, d.frame_log, frame0,
+                     d.log_frames, d.max_rows, d.n_cb + 1);
+  UA2_LAUNCH_CHECK();
+  ua2_count_launch(UA2_CNT_TEXT_FLUSH);
   return 0;
 }
 

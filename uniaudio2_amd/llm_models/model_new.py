@@ -66,6 +66,26 @@ def ragged_schedule(n_frames):
         active = [active[r] for r in keep]
 
 
+DEFER_CAP_ROWS = 64     # include/ua2hip.h UA2_DEFER_CAP_ROWS: rows of the executor's stash ring
+
+
+def defer_windows(start: int, n_frames: int, R: int, cap_rows: int = DEFER_CAP_ROWS):
+    """Flush windows of a generate_frames call that defers its text head: the call's frames are log slots start .. start +
+    n_frames - 1, every frame but the last is deferred, and a deferred frame f of R rows sits in slot f % cap_frames of the
+    executor's stash ring (cap_frames = cap_rows // R).  Returns [(frame0, n), ...] in issue order: window (frame0, n) is
+    flushed right after frame frame0 + n - 1.  The windows tile the deferred frames, none crosses a multiple of cap_frames
+    (so none wraps the ring, and a slot is flushed before it is written again) and none holds more than cap_rows rows."""
+    cap_frames = cap_rows // R
+    if cap_frames < 1:
+        raise ValueError(f"a stash ring of {cap_rows} rows holds no frame of {R} rows")
+    out, f, end = [], start, start + n_frames - 1          # deferred frames: [start, end)
+    while f < end:
+        stop = min(end, (f // cap_frames + 1) * cap_frames)
+        out.append((f, stop - f))
+        f = stop
+    return out
+
+
 class Model_stage3(nn.Module):
     """Stage 3: text-audio joint model (inference)."""
 
@@ -170,6 +190,8 @@ class Model_stage3(nn.Module):
         self._h, self._st = h, st
         self._sampling = None
         self._cfg = 1.0
+        self._w8_on = False            # fp8 twins attached (set_w8)
+        self._order_free = 0           # set_order_free_rows
         self._pos_hi = 0
         self._text_fed_back = False    # the last frame run was a text-feedback frame (every row now holds masks audio 0 / text 1)
         self._ngram = None             # (n, fallback, capacity) of the text frames' n-gram filter (set_ngram); None = off
@@ -193,9 +215,11 @@ class Model_stage3(nn.Module):
             raise ValueError("this plan was built without fp8 weights (setup_caches(..., weight_dtype=torch.float8_e4m3fn))")
         if not on:
             check(lib.ua2_stage3_set_w8(self._h, None, 0), "ua2_stage3_set_w8")
+            self._w8_on = False
             return
         tab = (W8Entry * len(w8))(*[W8Entry(t.data_ptr(), q.data_ptr(), e.data_ptr()) for t, q, e in w8])
         check(lib.ua2_stage3_set_w8(self._h, tab, len(w8)), "ua2_stage3_set_w8")
+        self._w8_on = True
 
     def _destroy(self):
         if self._h is not None:
@@ -373,12 +397,26 @@ class Model_stage3(nn.Module):
         the bits of its single-sequence run)."""
         self._need()
         check(lib.ua2_stage3_set_order_free_rows(self._h, int(rows)), "ua2_stage3_set_order_free_rows")
+        self._order_free = int(rows)
+
+    def _defer_cap_rows(self, batch: int, mode: int, n_frames: int, skip_text_head: bool) -> int:
+        """Rows of the stash ring a generate_frames call may defer its text head into; 0 = the call runs every frame as it is."""
+        st = self._st
+        if mode != 0 or skip_text_head or n_frames < 2 or DEFER_CAP_ROWS // batch < 2:
+            return 0
+        if (self._sampling is not None and self._sampling[0] != 1) or self._cfg != 1.0 or self._w8_on:
+            return 0                   # top-k sampling, guided pairs and fp8 plans keep lm_head in the frame
+        if st["dtype"] == torch.bfloat16 and 0 < self._order_free <= batch:
+            return 0                   # the order-free opt-in covers frames of `batch` rows: their lm_head is not row-invariant
+        cap = int(lib.ua2_stage3_defer_rows())   # UA2_DEFER_ROWS (tests, sweeps); 0 under UA2_NO_DEFER_TEXT_HEAD=1
+        return cap if cap // batch >= 1 else 0
 
     # ---- MI355X-native fast path ---------------------------------------------------------------
     @torch.inference_mode()
     def generate_frames(self, n_frames: int, batch: int, mode: int, reason_eos: int = -1, reason_card: int = 0,
                         max_pos: Optional[int] = None, use_graph: bool = True, frame_events=None,
-                        skip_text_head: bool = False, skip_audio_experts: bool = False) -> torch.Tensor:
+                        skip_text_head: bool = False, skip_audio_experts: bool = False,
+                        defer_text_head: bool = True) -> torch.Tensor:
         """Runs `n_frames` frames back to back from the state left by the previous frame (first
         call: after `begin_decode`).  mode 0 = audio feedback (evaluation/tts_task.py:259-280),
         1 = text feedback (evaluation/asr_task.py:668-682; the depth decoder is skipped there — its samples are
@@ -387,7 +425,15 @@ class Model_stage3(nn.Module):
         skip_text_head (modes 0 and 2): lm_head and the text sample are skipped — the audio loops feed the text id back under
         a zero mask and never read it (tts_task.py:259,274-277), so the audio columns are bit-identical with and without it;
         the text column of the log then holds -1.  The reference-shaped generate_frame always computes it.
-        Mode 1 under set_ngram(n >= 2): the log's text column and the fed-back text id are the n-gram-filtered ids."""
+        Mode 1 under set_ngram(n >= 2): the log's text column and the fed-back text id are the n-gram-filtered ids.
+        defer_text_head (mode 0 without skip_text_head; greedy, unguided, no fp8 twins, not under the order-free opt-in, n_frames
+        >= 2, batch <= 32; UA2_NO_DEFER_TEXT_HEAD=1 turns it off): in the audio loop the text id is fed back under a zero mask, so
+        the text ids of different frames are independent of each other and of the audio ids.  Every frame but the call's last
+        runs as UA2_FRAME_DEFER_TEXT_HEAD — no lm_head, its h_final rows kept in a 64-row ring — and lm_head runs once per
+        64 // batch frames over the kept rows (ua2_stage3_text_flush, windows: defer_windows): one pass over its weights instead
+        of one per frame, the same ids and logits bit for bit (row invariance).  The last frame runs whole, so text_logits,
+        out_tokens and the fed-back state hold after the call what they hold without deferral; every flush is issued before the
+        call returns, so the returned log slice is complete in stream order and nothing deferred outlives the call."""
         if skip_text_head:
             if mode not in (0, 2):
                 raise ValueError("skip_text_head applies to the audio-feedback modes (0, 2)")
@@ -424,13 +470,20 @@ class Model_stage3(nn.Module):
         if mode == 1 and self._ngram is not None:
             self._ngram_hi += n_frames
         s = ops.stream()
+        cap_rows = self._defer_cap_rows(batch, mode, n_frames, skip_text_head) if defer_text_head else 0
+        flush_after = {f0 + n - 1: (f0, n) for f0, n in defer_windows(start, n_frames, batch, cap_rows)} if cap_rows else {}
         for i in range(n_frames):
             # skip_audio_experts (text-only continuations: asr_task.py:666-682 and twins): from the session's SECOND text-feedback frame on
             # every row is a text step fed back by the executor itself (masks audio 0 / text 1) — the first frame consumes the prompt's
             # last token, which may be an audio step, and runs whole.  UA2_FRAME_SKIP_AUDIO_EXPERTS = 32.
             m = mode | 32 if (skip_audio_experts and self._text_fed_back) else mode
+            if cap_rows and i < n_frames - 1:
+                m = mode | 64                      # UA2_FRAME_DEFER_TEXT_HEAD
             check(lib.ua2_stage3_frame(self._h, batch, m, reason_eos, reason_card, int(use_graph), s),
                   "ua2_stage3_frame")
+            if start + i in flush_after:           # the frame filled the ring's last slot, or is the call's last deferred one
+                f0, n = flush_after[start + i]
+                check(lib.ua2_stage3_text_flush(self._h, batch, f0, n, s), "ua2_stage3_text_flush")
             self._text_fed_back = mode in (1, 3)
             if frame_events is not None:           # measurement hook: one event after every frame (bench.py p50 / p99)
                 frame_events[i].record()
