@@ -250,6 +250,15 @@ int ua2_linear(const ua2_linear_args* a, void* stream);
  * LOCAL_ATTN with RESIDUAL.  Anything else is an error (never a silent launch on the bf16 form).  Same grid, waves, chunk ranges and
  * summation order as the bf16 launch of that (N, K): bit-identical outputs.  Counted as "gemv_w8" by ua2_debug_kernel_launches. */
 int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream);
+/* [v10, addition] The many-row counterpart: one launch on the fp8 twins through the weights-stationary kernel (csrc/ua2_skinny.hip,
+ * skinny2_kernel with W8 = true) — the batched decode frame, 6 .. UA2_SKINNY_W8_MAX_ROWS rows (default 64; 0 / "off" = never).  Served: UA2_BF16,
+ * K % 64 == 0, more rows than the launchers give the decode kernel, a workspace (or x_packed), a Linear geometry of the released widths
+ * (K = 2048 / 3072 / 8192 with a STORE / RESIDUAL / SWIGLU / QKV_ROPE epilogue), prologues NORM / CAST / SCALED (through x_packed).
+ * Anything else — fewer or more rows, fp32, GELU, a toy shape, a forced tile variant without an fp8 form — is an error naming this entry
+ * point, never a launch on the bf16 form.  Same grid, waves, K ranges, chunk order and range-order sum as the bf16 launch of that shape
+ * (the exponent 2^e goes once on the reduced sum): bit-identical to ua2_linear on W' and, row by row, to ua2_linear_w8.  Counted as
+ * "skinny2_w8" by ua2_debug_kernel_launches.  ua2_linear_w8 itself keeps refusing more rows than the decode kernel takes. */
+int ua2_linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream);
 /* [v9] 1 when a launch with these arguments (sum_order = UA2_SUM_ORDER_FREE) will run on the order-free kernel (csrc/ua2_gemm2.hip) as it
  * stands — shape, alignment, the tile-count rule, scratch for K slabs; 0 when ua2_linear would take the row-invariant kernels instead.
  * Nothing is launched. */
@@ -266,7 +275,7 @@ size_t ua2_linear_workspace_bytes(int dtype, int64_t M, int64_t K);
 int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
- * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
+ * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
  * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
@@ -278,6 +287,11 @@ void ua2_debug_refresh_env(void);
  * `stream`, bracketed by hipEvents recorded on that same stream, waits for the stop event and
  * returns the elapsed milliseconds in *ms_out.  No other work is enqueued in between. */
 int ua2_linear_chain_timed(const ua2_linear_args* args, int32_t n, int32_t iters, void* stream, float* ms_out);
+/* [v10, addition] The same chain through ua2_linear_w8_many: launch i on the fp8 twins w0[i] (and w1[i]; w1 may be NULL when no launch is a
+ * SWIGLU one).  Same host path and the same events as ua2_linear_chain_timed, so the two figures of one shape can be compared
+ * (tools/ubench/skinny_shapes.py --w8). */
+int ua2_linear_w8_many_chain_timed(const ua2_linear_args* args, const ua2_w8_ref* w0, const ua2_w8_ref* w1, int32_t n, int32_t iters, void* stream,
+                                   float* ms_out);
 
 /* Decode/prefill attention over the paged cache: one query row per (row, head); one workgroup per (row, kv-head)
  * walks positions 0..row_pos (waves own contiguous ranges, online softmax, fixed-order merge in LDS) and writes the

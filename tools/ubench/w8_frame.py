@@ -1,7 +1,11 @@
 """Decode frame of the fp8 weight-only plan (setup_caches(weight_dtype=torch.float8_e4m3fn)) against the bf16 plan on the original
 weights, released sizes, random init, graph replay.
 
-  python tools/ubench/w8_frame.py [--frames 200] [--batches 1 2 5]   ms per frame p50 / p99, the two plans alternated (A B B A) per batch
+  python tools/ubench/w8_frame.py [--frames 200] [--batches 1 2 5]   ms per frame p50 / p99 per batch, three configurations interleaved in one
+                                                                      process (on off bf16 bf16 off on): the fp8 plan, the fp8 plan with
+                                                                      UA2_SKINNY_W8_MAX_ROWS=0 (frames of more than 5 rows read the bf16 twin: the
+                                                                      behaviour before the fp8 weights-stationary kernel) and the bf16 plan; the two
+                                                                      runs of a configuration give the run-to-run spread
   python tools/ubench/w8_frame.py --quality                           logit distance of the first 8 teacher-forced frames (fp8 vs bf16 plan)
   rocprofv3 --kernel-trace --stats -d DIR -o w8 -- python tools/ubench/w8_frame.py --profile
                                                                       20 frames of each plan at B = 1, un-graphed, for tools/rocpd_stats.py --by-grid
@@ -115,18 +119,37 @@ def main():
               f"audio logits rms diff {rms(al_q - al_b):.3e} max {float((al_q - al_b).abs().max()):.3e} (logit rms {rms(al_b):.3f}); "
               f"ids equal {same}/{8 * 9}", flush=True)
         return
-    print(f"# ms per decode frame, graph replay, {a.frames} frames after 20 warm-up frames; order per batch: bf16, fp8, fp8, bf16", flush=True)
+    from uniaudio2_amd._lib import lib
+    print(f"# ms per decode frame, graph replay, {a.frames} frames after 20 warm-up frames; order per batch: fp8, fp8 with UA2_SKINNY_W8_MAX_ROWS=0, "
+          f"bf16, bf16, fp8 with UA2_SKINNY_W8_MAX_ROWS=0, fp8", flush=True)
+    names = {"on": "fp8_e4m3          ", "off": "fp8_e4m3 rows=0   ", "bf16": "bf16              "}
+
+    def limit(cfg):          # the launchers read the knob when a frame graph is captured: set it, have it re-read, drop the captured graphs
+        if cfg == "off":
+            os.environ["UA2_SKINNY_W8_MAX_ROWS"] = "0"
+        else:
+            os.environ.pop("UA2_SKINNY_W8_MAX_ROWS", None)
+        lib.ua2_debug_refresh_env()
+
     for B in a.batches:
-        res = {False: [], True: []}
-        for fp8 in (False, True, True, False):
-            plan(model, B, fp8)
-            res[fp8].append(time_frames(model, dev, B, a.frames))
-        for fp8 in (False, True):
-            for i, (p50, p99, mean) in enumerate(res[fp8]):
-                print(f"B={B} {'fp8_e4m3' if fp8 else 'bf16    '} run {i}: p50 {p50:.3f} ms  p99 {p99:.3f} ms  mean {mean:.3f} ms", flush=True)
-        b50 = min(r[0] for r in res[False])
-        q50 = min(r[0] for r in res[True])
-        print(f"B={B} ratio fp8 / bf16 (best p50 of each): {q50 / b50:.3f}  ({b50:.3f} -> {q50:.3f} ms)", flush=True)
+        res = {"on": [], "off": [], "bf16": []}
+        try:
+            for cfgs in (("on", "off"), ("bf16", "bf16"), ("off", "on")):
+                plan(model, B, cfgs[0] != "bf16")
+                for cfg in cfgs:
+                    limit(cfg)
+                    if cfg != "bf16":
+                        model.set_w8(True)
+                    res[cfg].append(time_frames(model, dev, B, a.frames))
+        finally:
+            limit("on")
+        for cfg in ("on", "off", "bf16"):
+            for i, (p50, p99, mean) in enumerate(res[cfg]):
+                print(f"B={B} {names[cfg]} run {i}: p50 {p50:.3f} ms  p99 {p99:.3f} ms  mean {mean:.3f} ms", flush=True)
+        best = {cfg: min(r[0] for r in res[cfg]) for cfg in res}
+        spread = max(abs(res[cfg][0][0] - res[cfg][1][0]) for cfg in res)
+        print(f"B={B} best p50: fp8 {best['on']:.3f} ms | fp8 rows=0 {best['off']:.3f} ms | bf16 {best['bf16']:.3f} ms | fp8 / rows=0 {best['on'] / best['off']:.3f} | "
+              f"fp8 / bf16 {best['on'] / best['bf16']:.3f} | run-to-run spread (largest |run 0 - run 1| of a configuration) {spread:.3f} ms", flush=True)
 
 
 if __name__ == "__main__":

@@ -122,6 +122,7 @@ _EXPORTS = {
     "ua2_packed_bytes_w8": (C.c_size_t, [i64, i64]),
     "ua2_pack_linear_w8": (C.c_int, [vp, C.c_int, C.c_int, i64, i64, vp, vp, vp, C.c_int, vp]),
     "ua2_linear_w8": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), vp]),
+    "ua2_linear_w8_many": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), vp]),
     "ua2_stage3_set_w8": (C.c_int, [vp, C.POINTER(W8Entry), i32]),
     "ua2_linear_order_free_accepts": (C.c_int, [C.POINTER(LinearArgs)]),
     "ua2_debug_force_general_linear": (C.c_int, [C.c_int]),
@@ -135,6 +136,7 @@ _EXPORTS = {
     "ua2_stage3_set_ngram": (C.c_int, [vp, i32, i32, vp, vp, i32]),
     "ua2_linear_workspace_bytes": (C.c_size_t, [C.c_int, i64, i64]),
     "ua2_linear_chain_timed": (C.c_int, [C.POINTER(LinearArgs), i32, i32, vp, C.POINTER(C.c_float)]),
+    "ua2_linear_w8_many_chain_timed": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), i32, i32, vp, C.POINTER(C.c_float)]),
     "ua2_attn": (C.c_int, [C.POINTER(AttnArgs), vp]),
     "ua2_attn_local": (C.c_int, [C.POINTER(AttnArgs), vp]),
     "ua2_embed_frame": (C.c_int, [C.c_int, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -193,7 +193,7 @@ inline void ua2_allow_big_lds() {
 }
 
 // ---- test hooks (ua2hip.h ABI v9): launch counters per kernel family, and UA2_* environment variables read once -------------
-enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_N = 7 };
+enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_SKINNY2_W8 = 7, UA2_CNT_N = 8 };
 extern std::atomic<int64_t> g_ua2_launches[UA2_CNT_N];
 extern std::atomic<int> g_ua2_env_gen;              // bumped by ua2_debug_refresh_env
 inline void ua2_count_launch(int family) { g_ua2_launches[family].fetch_add(1, std::memory_order_relaxed); }
@@ -215,14 +215,16 @@ struct Ua2EnvInt {
 };
 
 // fp8 (OCP e4m3fn) weight-only twins of a launch's w0 / w1 (include/ua2hip.h ua2_pack_linear_w8): image + per-column exponents.
-// strict: the caller asked for the fp8 kernel by name (ua2_linear_w8) — a launch it does not serve is an error, never the bf16 twin.
+// strict: the caller asked for an fp8 kernel by name — a launch it does not serve is an error, never the bf16 twin: the decode kernel
+// (ua2_linear_w8), or with `many` the weights-stationary kernel (ua2_linear_w8_many).
 struct Ua2W8 {
   const void *q0 = nullptr, *q1 = nullptr;
   const int8_t *e0 = nullptr, *e1 = nullptr;
-  bool strict = false;
+  bool strict = false, many = false;
 };
 // internal launchers used by both the op-level ABI and the frame executor
-// w8 != NULL: launches that the decode kernel serves stream the fp8 image instead of a.w0 / a.w1 (the same bits: a.w0 / a.w1 hold W')
+// w8 != NULL: launches that the decode kernel or the weights-stationary kernel (6 .. UA2_SKINNY_W8_MAX_ROWS rows) serves stream the fp8
+// image instead of a.w0 / a.w1 (the same bits: a.w0 / a.w1 hold W')
 int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
 int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_attn_local_launch(const ua2_attn_args& a, hipStream_t s);

@@ -1144,8 +1144,13 @@ int skinny2_max_rows(int64_t N, int64_t K, int nt) {
   return 320;
 }
 
+// the conditions under which launch_dt below hands a launch to the weights-stationary kernel
+bool prefers_skinny2(const ua2_linear_args& a, int nt, int force) {
+  return force != 5 && a.dtype == UA2_BF16 && a.M <= skinny2_max_rows(a.N, a.K, nt) && a.N < 32768;
+}
+
 template <int DT>
-int launch_dt(const ua2_linear_args& a, hipStream_t s, int force) {
+int launch_dt(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8) {
   const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
   const ua2_gemv_geometry geo = ua2_pick_gemv_geometry(a.dtype, a.N, a.K, nt);
   if (a.x_packed) {
@@ -1170,10 +1175,11 @@ int launch_dt(const ua2_linear_args& a, hipStream_t s, int force) {
   const bool skinny_ok = geo.waves * nt * kSkinnyMT * 1024 <= 128 * 1024;
   // The weights-stationary form (ua2_skinny.hip) serves the model's bf16 shapes up to a few hundred rows: measured against
   // the tiled kernel it wins up to 256 rows everywhere except the 128k-column lm_head (profiles/r3_skinny_sweep.txt).
-  const bool prefer2 = force != 5 && a.dtype == UA2_BF16 && a.M <= skinny2_max_rows(a.N, a.K, nt) && a.N < 32768;
+  const bool prefer2 = prefers_skinny2(a, nt, force);
   const bool old_skinny = skinny_ok && (force == 4 || (force != 5 && choose_skinny(a, nt)));
   if (prefer2 || old_skinny)
-    if (const int rc = ua2_skinny2_try_launch(a, geo, s); rc <= 0) return rc;
+    if (const int rc = ua2_skinny2_try_launch(a, geo, s, w8); rc <= 0) return rc;
+  if (w8 && w8->strict) return 1;                  // asked for by name: never another kernel on the twin in its place
   if (old_skinny) {
     switch (a.epilogue) {
       case UA2_EPI_STORE: launch_skinny<DT, UA2_EPI_STORE>(a, geo, s); break;
@@ -1206,12 +1212,24 @@ extern "C" size_t ua2_linear_workspace_bytes(int dtype, int64_t M, int64_t K) {
   return (size_t)((M + 15) / 16) * (size_t)((K + kc - 1) / kc) * 1024;
 }
 
-int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force) {
-  if (a.prologue != UA2_PRO_CAST && a.prologue != UA2_PRO_NORM && !(a.prologue == UA2_PRO_SCALED && a.x_packed)) return 1;
-  if (!a.x_packed && (!a.workspace || a.workspace_bytes < ua2_linear_workspace_bytes(a.dtype, a.M, a.K))) return 1;
-  const int rt = ua2_gemv_rows_per_tile(a.dtype, a.K);
-  if (rt < 1) return 1;                          // the decode kernel cannot take this K at all: nothing to be identical with
-  if (!force && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K)) return 1;   // a few rows: the decode kernel (operand rows live in LDS); up to `rt` rows it COULD (forced mode 2 / row-major hand-overs)
-  if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s, force);
-  return launch_dt<UA2_F32>(a, s, force);
+// Does the many-row path take this launch at all?  (the one statement of it: ua2_gemm_try_launch and ua2_gemm_w8_serves both ask here)
+static bool gemm_takes(const ua2_linear_args& a, int force) {
+  if (a.prologue != UA2_PRO_CAST && a.prologue != UA2_PRO_NORM && !(a.prologue == UA2_PRO_SCALED && a.x_packed)) return false;
+  if (!a.x_packed && (!a.workspace || a.workspace_bytes < ua2_linear_workspace_bytes(a.dtype, a.M, a.K))) return false;
+  if (ua2_gemv_rows_per_tile(a.dtype, a.K) < 1) return false;   // the decode kernel cannot take this K at all: nothing to be identical with
+  // a few rows: the decode kernel (operand rows live in LDS); up to rows_per_tile rows it COULD (forced mode 2 / row-major hand-overs)
+  return force || a.M > ua2_gemv_rows_preferred(a.dtype, a.K);
+}
+
+bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2W8& w8) {
+  if (a.dtype != UA2_BF16 || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % 64 || a.sum_order == UA2_SUM_ORDER_FREE || a.y_ln_w) return false;
+  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
+  if (!gemm_takes(a, 0) || !prefers_skinny2(a, nt, 0)) return false;
+  return ua2_skinny2_try_launch(a, ua2_pick_gemv_geometry(a.dtype, a.N, a.K, nt), nullptr, &w8, true) == 0;
+}
+
+int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8) {
+  if (!gemm_takes(a, force)) return 1;
+  if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s, force, w8);
+  return launch_dt<UA2_F32>(a, s, force, w8);
 }

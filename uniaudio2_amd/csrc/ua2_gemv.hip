@@ -54,11 +54,7 @@ __device__ __forceinline__ void local_attn_prologue(const ua2_linear_args& a, ch
 // Eight OCP e4m3fn codes -> the bf16 B fragment of one chunk, exactly (an e4m3 value has 4 significant bits and sits inside the bf16
 // exponent range, subnormals included): v_cvt_pk_f32_fp8 x 4, v_cvt_pk_bf16_f32 x 4.  The row's power-of-two scale is NOT applied here
 // but once on the reduced tile (a power of two commutes with every fp32 rounding of the chain and of the cross-wave sum).
-__device__ __forceinline__ u32x4 dequant_e4m3x8(unsigned d0, unsigned d1) {
-  const f32x2_hw f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
-  const f32x2_hw f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
-  return u32x4{pack_bf16x2(f0[0], f0[1]), pack_bf16x2(f1[0], f1[1]), pack_bf16x2(f2[0], f2[1]), pack_bf16x2(f3[0], f3[1])};
-}
+// (dequant_e4m3x8: ua2_linear_common.h — the weights-stationary kernel of ua2_skinny.hip reads the same image.)
 
 // 1 KiB burst of the weight image that load `u` of the round starting at chunk `cb` fetches (`last` = the wave's last chunk: clamped, never predicated)
 template <int W8>

@@ -117,7 +117,13 @@ __global__ void w8_pack_kernel(const void* __restrict__ src, const int8_t* __res
 static int g_force_general = 0;
 
 int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
-  const bool w8_strict = w8 && w8->strict;
+  const bool w8_many = w8 && w8->strict && w8->many;
+  const bool w8_strict = w8 && w8->strict && !w8->many;
+  if (w8_many)
+    UA2_CHECK(ua2_gemm_w8_serves(a, *w8),
+              "ua2_linear_w8_many: not a launch the fp8 weights-stationary kernel serves (UA2_BF16, K %% 64 == 0, %d to %d rows [UA2_SKINNY_W8_MAX_ROWS], "
+              "a released Linear geometry with a STORE / RESIDUAL / SWIGLU / QKV_ROPE epilogue, workspace or x_packed, a built variant)",
+              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) + 1 : 0, ua2_skinny_w8_max_rows());
   if (w8_strict)
     UA2_CHECK(a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_w8_ok(a),
               "ua2_linear_w8: not a launch the fp8 decode kernel serves (UA2_BF16, K %% 64 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed)",
@@ -159,8 +165,8 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
   if (a.x_packed) {   // operand handed over in fragment order by its producer: only the many-row kernels read it
     UA2_CHECK((a.prologue == UA2_PRO_CAST || a.prologue == UA2_PRO_SCALED) && g_force_general != 2,
               "ua2_linear: x_packed needs PRO_CAST / PRO_SCALED and the many-row kernels");
-    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 4 ? g_force_general : 3);
-    UA2_CHECK(rc <= 0, "ua2_linear: x_packed launch not applicable");
+    const int rc = ua2_gemm_try_launch(a, s, w8_many ? 0 : (g_force_general >= 4 ? g_force_general : 3), w8);
+    UA2_CHECK(rc <= 0, "%s: x_packed launch not applicable", w8_many ? "ua2_linear_w8_many" : "ua2_linear");
     return rc;
   }
   if (a.prologue == UA2_PRO_SCALED) {   // row-major hand-over: one row tile, the decode kernel
@@ -202,8 +208,13 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
     ua2_set_error("ua2_linear: bad dtype %d", a.dtype);
     return -1;
   }
+  if (w8_many) {    // by name: the weights-stationary kernel on the fp8 image or an error (ua2_gemm_w8_serves above said it takes the launch)
+    const int rc = ua2_gemm_try_launch(a, s, 0, w8);
+    UA2_CHECK(rc <= 0, "ua2_linear_w8_many: the fp8 weights-stationary kernel did not take the launch");
+    return rc;
+  }
   if (g_force_general != 2 && !w8_strict) {
-    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0);  // many rows: packed operand, 128-row tiles
+    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8);  // many rows: packed operand, 128-row tiles
     if (rc <= 0) return rc;
   }
   const int rc = ua2_gemv_try_launch(a, s, w8);  // decode regime: LDS-staged activations, all loads up front
@@ -307,4 +318,37 @@ extern "C" int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, con
   if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
   w8.strict = true;
   return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
+}
+
+static int linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, hipStream_t s) {
+  UA2_CHECK(a != nullptr && w0 != nullptr && w0->q && w0->exp, "ua2_linear_w8_many: NULL args or fp8 twin of w0");
+  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->q && w1->exp), "ua2_linear_w8_many: SWIGLU needs the fp8 twin of w1");
+  Ua2W8 w8;
+  w8.q0 = w0->q; w8.e0 = w0->exp;
+  if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
+  w8.strict = w8.many = true;
+  return ua2_linear_launch(*a, s, &w8);
+}
+
+extern "C" int ua2_linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream) {
+  return linear_w8_many(a, w0, w1, (hipStream_t)stream);
+}
+
+extern "C" int ua2_linear_w8_many_chain_timed(const ua2_linear_args* args, const ua2_w8_ref* w0, const ua2_w8_ref* w1, int32_t n, int32_t iters,
+                                              void* stream, float* ms_out) {
+  UA2_CHECK(args && w0 && n > 0 && iters > 0 && ms_out, "ua2_linear_w8_many_chain_timed: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipEvent_t e0, e1;
+  UA2_HIP(hipEventCreate(&e0));
+  UA2_HIP(hipEventCreate(&e1));
+  UA2_HIP(hipEventRecord(e0, s));
+  for (int it = 0; it < iters; ++it)
+    for (int i = 0; i < n; ++i)
+      if (int rc = linear_w8_many(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s)) return rc;
+  UA2_HIP(hipEventRecord(e1, s));
+  UA2_HIP(hipEventSynchronize(e1));
+  UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return 0;
 }

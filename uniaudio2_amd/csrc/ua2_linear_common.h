@@ -13,9 +13,14 @@ ua2_gemv_geometry ua2_pick_gemv_geometry(int dtype, int N, int K, int nt);
 int ua2_gemv_rows_per_tile(int dtype, int K);
 // large-M path; returns 1 when not applicable (no workspace, ATTN prologue, few rows)
 // force: 0 = only when M spans more than one row tile; 3 = whenever possible; 4 / 5 = likewise, skinny / tiled form
-int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force);
+// w8: fp8 twins of the launch's weights, handed on to the weights-stationary kernel (the other many-row kernels read a.w0 / a.w1 = W')
+int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8 = nullptr);
 // batched-decode form (ua2_skinny.hip): 0 = launched, 1 = shape outside its table (the older skinny kernel serves it)
-int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s);
+// w8: streams the fp8 image where its fp8 form takes the launch; dry: launches nothing, 0 = the fp8 form would take it
+int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2W8* w8 = nullptr, bool dry = false);
+int ua2_skinny_w8_max_rows();                      // UA2_SKINNY_W8_MAX_ROWS (default 64; 0 = never)
+// would ua2_linear_launch hand this launch to skinny2_kernel<W8 = true, ...>?  (the whole chain: many-row path, weights-stationary kernel, an fp8 form)
+bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2W8& w8);
 // order-free form (ua2_gemm2.hip: 256-row tiles, one chain over K): 0 = launched, 1 = launch outside its forms; operand already packed
 int ua2_gemm2_try_launch(const ua2_linear_args& a, hipStream_t s);
 
@@ -46,6 +51,15 @@ template <> struct AFrag<UA2_F32> {
     for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v[e], b[e], acc, 0, 0, 0);
   }
 };
+
+// fp8 weight image (include/ua2hip.h ua2_pack_linear_w8): eight OCP e4m3fn codes (two dwords of a lane's 16-byte load) -> the bf16
+// B fragment of one chunk, exactly: v_cvt_pk_f32_fp8 x 4, v_cvt_pk_bf16_f32 x 4.  One definition for every kernel that streams the image
+// (ua2_gemv.hip gemv_w8_kernel, ua2_skinny.hip skinny2_kernel<W8 = true, ...>): the same codes become the same fragment wherever they are read.
+__device__ __forceinline__ u32x4 dequant_e4m3x8(unsigned d0, unsigned d1) {
+  const f32x2_hw f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d0, true);
+  const f32x2_hw f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)d1, true);
+  return u32x4{pack_bf16x2(f0[0], f0[1]), pack_bf16x2(f1[0], f1[1]), pack_bf16x2(f2[0], f2[1]), pack_bf16x2(f3[0], f3[1])};
+}
 
 // ---- A-operand producers (row m, K offset k0, EPL consecutive values) -----------------------
 

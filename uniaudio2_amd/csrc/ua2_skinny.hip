@@ -43,8 +43,17 @@ constexpr int kRsrcFlags = 0x00020000;   // raw buffer, dword data format (gfx9 
 // RPW (round 6): K ranges per wave.  NWV stays the number of RANGES (the bit contract: `red` holds one partial per range, added in range
 // order); with RPW = 2 a workgroup is NWV / 2 waves that walk two consecutive ranges each — all 2 x CH weight fragments in flight at once as
 // before, and twice the registers per wave for a deeper operand ring (K = 8192 at 16 ranges: 128 registers per wave leave LA = 1).
-template <int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0, int RPW = 1>
-__global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linear_args a, const u32x4* __restrict__ apack, const int passes) {
+// W8 (fp8 weights, include/ua2hip.h ua2_pack_linear_w8; `w8` is read by the W8 instantiations only): the weight streams are the fp8
+// images of `w8` instead of a.w0 / a.w1 — one 16-byte lane load carries the lane's B fragments of TWO chunks (2j: bytes 0-7, 2j + 1:
+// bytes 8-15), so a wave requests half as many 1 KiB bursts and
+// keeps them as they came: the resident weights (or the ring) are fp8 in registers, half the bf16 form's, and a chunk's fragment is expanded
+// (dequant_e4m3x8: exact) immediately in front of its MFMAs.  The column's scale 2^e goes once on the reduced sum, in front of the
+// epilogue, as in gemv_w8_kernel (a power of two commutes with every fp32 rounding of the chains and of the range-order sum).  Everything
+// else — grid, waves, ranges, chunk order, `red`, the sum, the epilogue items — is the W8 = false text, so the bits are those of the bf16
+// form on W' and of the decode kernel on the image.
+// (W8 leads the parameter list: the tail stays SC, WD, RPW, which is how the compiled instantiations are told apart by name.)
+template <bool W8, int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0, int RPW = 1>
+__global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linear_args a, const u32x4* __restrict__ apack, const int passes, const Ua2W8 w8) {
   constexpr int DT = UA2_BF16;
   constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;   // weight matrices
   constexpr int NS = NM * CT;                           // weight streams per wave: stream s = matrix s / CT, column tile s % CT
@@ -54,6 +63,9 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
   static_assert(CHT % LA == 0 && LA <= CHT, "the operand ring must tile a wave's chunks");
   constexpr int WR = WD > 0 ? WD : CHT;                 // weight chunks a wave holds at a time
   static_assert(WR <= CHT && CHT % WR == 0, "the weight ring must tile a range");
+  // fp8: a wave's range starts on an even chunk and has an even length (c0 = wave * CHT), so it is whole bursts of two chunks; so is the ring
+  static_assert(!W8 || (CH % 2 == 0 && CHT % 2 == 0 && WR % 2 == 0), "the fp8 image is read two chunks at a time: even ranges, even rings");
+  constexpr int WL = W8 ? WR / 2 : WR;                  // 16-byte weight loads a wave holds per stream
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* red = reinterpret_cast<float*>(smem);          // [NWV][NS][MT][256]
   float* rstd_l = red + NWV * NS * MT * 256;            // [MT * passes * 16] row scales (UA2_PRO_SCALED)
@@ -66,12 +78,15 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
   // costs no 64-bit vector address arithmetic and no address registers (with flat global loads the compiler kept a 64-bit
   // VGPR pair per stream and spilled operand fragments at 16 waves per workgroup).
   const unsigned voff = (unsigned)(c0 * 64 + lane) * 16u;
+  const unsigned wvoff = W8 ? (unsigned)((c0 >> 1) * 64 + lane) * 16u : voff;      // fp8: burst c0 / 2 of the tile's nchunks / 2
+  constexpr int wbytes = (W8 ? nchunks / 2 : nchunks) * 1024;                      // one column tile of one weight stream
   __amdgpu_buffer_rsrc_t wr[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     const int nt = min((int)blockIdx.x * CT + s % CT, ntiles - 1);
-    const char* base = reinterpret_cast<const char*>((s / CT) ? a.w1 : a.w0) + (size_t)nt * nchunks * 1024;
-    wr[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, nchunks * 1024, kRsrcFlags);
+    const void* w = W8 ? ((s / CT) ? w8.q1 : w8.q0) : ((s / CT) ? a.w1 : a.w0);
+    const char* base = reinterpret_cast<const char*>(w) + (size_t)nt * wbytes;
+    wr[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, wbytes, kRsrcFlags);
   }
   // the operand: [mtiles][nchunks] fragments of 1 KiB (< 4 GiB: the launcher checks)
   const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(apack), 0, (unsigned)mtiles * (unsigned)(nchunks * 1024), kRsrcFlags);
@@ -80,7 +95,8 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
   auto aoff = [&](int mt) { return (unsigned)min(mt, mtiles - 1) * (unsigned)(nchunks * 1024); };
   auto lda = [&](unsigned tile_off, int chunk) { return __builtin_amdgcn_raw_buffer_load_b128(ar, voff, tile_off + (unsigned)chunk * 1024u, 0); };
 
-  auto ldw = [&](int s, int chunk) { return __builtin_amdgcn_raw_buffer_load_b128(wr[s], voff, chunk * 1024, 2); };   // aux 2 = nt: streamed once
+  // load `l` of the wave's range: chunk l (bf16) / chunks 2l and 2l + 1 (fp8)
+  auto ldw = [&](int s, int l) { return __builtin_amdgcn_raw_buffer_load_b128(wr[s], wvoff, l * 1024, 2); };   // aux 2 = nt: streamed once
 
   // UA2_PRO_SCALED: sum-of-squares partials of the pass's rows — a 16-lane group per row, SW sweeps over the MT * 16 rows —
   // requested at the head of the pass (pass 0: before the weight burst), reduced after its chunk loop, into rstd_l
@@ -100,12 +116,21 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
     }
   };
   if constexpr (SC) ssq_request(0);
+  // fp8: the exponents of this thread's epilogue column in each of the wave's column tiles (16 bytes per tile, N padded to 16: in bounds
+  // for every thread) — requested by EVERY thread, unpredicated, before the weight burst: a load under a lane predicate ends in a
+  // vmcnt(0) in front of the burst (ua2_gemv.hip)
+  int wexp[W8 ? NS : 1];
+  if constexpr (W8) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+      wexp[s] = ((s / CT) ? w8.e1 : w8.e0)[min((int)blockIdx.x * CT + s % CT, ntiles - 1) * 16 + (tid & 15)];
+  }
 
   // Issue order: a wave's loads retire in order, so the first operand chunks (L2 hits, needed first) go out BEFORE the weight
   // burst (HBM).  (A "rolling window" form — weights and operand of a chunk travelling together through a ring, consumed in
   // issue order — was measured and lost 5-20 %: it caps the weight bytes in flight per wave at the ring depth,
   // profiles/r3_skinny_sweep.txt.)
-  u32x4 af[LA][MT], wf[NS][WR];
+  u32x4 af[LA][MT], wf[NS][WL];
   {
     unsigned o[MT];
 #pragma unroll
@@ -117,7 +142,7 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
   }
   __builtin_amdgcn_sched_barrier(0);                    // the machine scheduler may not hoist the weight burst above these
 #pragma unroll
-  for (int u = 0; u < WR; ++u)
+  for (int u = 0; u < WL; ++u)
 #pragma unroll
     for (int s = 0; s < NS; ++s) wf[s][u] = ldw(s, u);
   __builtin_amdgcn_sched_barrier(0);
@@ -138,22 +163,49 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
       for (int mi = 0; mi < MT; ++mi) acc[s][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < CHT; ++u) {
+      if constexpr (W8) {                                // chunk u: half (u & 1) of load (u % WR) / 2, expanded here and nowhere kept
+        // (left to itself the compiler hoists every conversion above the pass loop — the fragments do not change from pass to pass — and
+        // above the chunk loop: all the range's fragments resident as bf16, the bf16 form's registers plus the image's.  The empty asm makes the
+        // burst's registers opaque at the point of use; the barrier keeps the scheduler from moving the conversions up from there.)
+        __builtin_amdgcn_sched_barrier(0);
+        u32x4 wb[NS];
 #pragma unroll
-      for (int mi = 0; mi < MT; ++mi) {
-        AFrag<DT> f;
-        f.v = af[u % LA][mi];
+        for (int s = 0; s < NS; ++s) {
+          asm volatile("" : "+v"(wf[s][(u % WR) >> 1]));
+          const u32x4 w = wf[s][(u % WR) >> 1];
+          wb[s] = dequant_e4m3x8(w[(u & 1) * 2], w[(u & 1) * 2 + 1]);
+        }
 #pragma unroll
-        for (int s = 0; s < NS; ++s) f.mma(wf[s][u % WR], acc[s][mi]);
+        for (int mi = 0; mi < MT; ++mi) {
+          AFrag<DT> f;
+          f.v = af[u % LA][mi];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) f.mma(wb[s], acc[s][mi]);
+        }
+      } else {
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) {
+          AFrag<DT> f;
+          f.v = af[u % LA][mi];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) f.mma(wf[s][u % WR], acc[s][mi]);
+        }
       }
       // refill the slot just consumed: chunk u + LA of this pass, or the first chunks of the next pass (always requested —
       // a branch around a load costs a full vmcnt(0) somewhere; past the last pass the clamped tile is read and dropped)
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi)
         af[u % LA][mi] = (u + LA < CHT) ? lda(oc[mi], u + LA) : lda(on[mi], u + LA - CHT);
-      if constexpr (WD > 0) {                            // the weight ring: chunk u's slot takes chunk u + WD (behind the operand refill)
+      if constexpr (WD > 0 && !W8) {                     // the weight ring: chunk u's slot takes chunk u + WD (behind the operand refill)
         if (u + WR < CHT) {
 #pragma unroll
           for (int s = 0; s < NS; ++s) wf[s][u % WR] = ldw(s, u + WR);
+        }
+      }
+      if constexpr (WD > 0 && W8) {                      // fp8 ring of WD / 2 bursts: refilled once per two chunks, when the odd half is consumed
+        if ((u & 1) && u - 1 + WR < CHT) {
+#pragma unroll
+          for (int s = 0; s < NS; ++s) wf[s][((u - 1) % WR) >> 1] = ldw(s, (u - 1 + WR) >> 1);
         }
       }
       if (u % CH == CH - 1) {                            // end of a range: its partial chain goes to the range's slot of `red`
@@ -212,6 +264,13 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
 #pragma unroll
           for (int w = 0; w < NWV; ++w) sacc += red[(((w * NS + t * CT + ct) * MT) + mi) * 256 + srcl];
           v[t] = sacc;
+          // fp8 weights: the column's scale 2^e, once, on the reduced sum (exact: e in [-117, 120] keeps 2^e a normal float)
+          if constexpr (W8) {
+            int e = wexp[t * CT];
+#pragma unroll
+            for (int c = 1; c < CT; ++c) e = (ct == c) ? wexp[t * CT + c] : e;
+            v[t] = __fmul_rn(sacc, __uint_as_float((unsigned)(e + 127) << 23));
+          }
         }
         linear_epilogue<DT, EPI, NM>(a, v, tile, row, col, pre, m0, min(16, a.M - m0));
       }
@@ -352,12 +411,15 @@ int rsplit_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream
 
 // VGPRs a variant needs: resident weights + operand ring + accumulators + addressing / epilogue slack.  Variants over the
 // per-wave budget (512 per SIMD shared by NWV / 4 waves) spill and are not built.
-constexpr int regs_needed(int nm, int ct, int mt, int ch, int la, int nwv = 16, bool sc = false, int wd = 0, int rpw = 1) {
+// w8: the fp8 form — the held weights are half as many registers (two chunks per 16-byte load); one expanded fragment per stream (4) and one
+// exponent per stream (1) live next to them.  Never more than the bf16 count (a wave holds >= 4 chunks per stream).
+constexpr int regs_needed(int nm, int ct, int mt, int ch, int la, int nwv = 16, bool sc = false, int wd = 0, int rpw = 1, bool w8 = false) {
   const int sw = (mt * 16 + nwv / rpw * 4 - 1) / (nwv / rpw * 4), npl = (nwv * ch + 7) / 8;      // the scaled consumer's sum-of-squares partials
   // ring forms: the partials are dead before the accumulators come alive (reduced behind the burst, in front of the chunk loop): only
   // what they need beyond the accumulators' registers counts
   const int acc = nm * ct * mt * 4, scx = sc ? sw * npl + 40 : 0;
-  return nm * ct * (wd > 0 ? wd : ch * rpw) * 4 + la * mt * 4 + acc + 20 + (wd > 0 ? (scx > acc ? scx - acc : 0) : scx);
+  const int held = wd > 0 ? wd : ch * rpw, wregs = w8 ? nm * ct * (held * 2 + 5) : nm * ct * held * 4;
+  return wregs + la * mt * 4 + acc + 20 + (wd > 0 ? (scx > acc ? scx - acc : 0) : scx);
 }
 
 struct Variant { int ct, mt, la, passes, wd = 0, rpw = 1; };
@@ -375,16 +437,59 @@ bool env_variant(Variant& v, bool& off) {
 template <int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0, int RPW = 1>
 int launch_one(const ua2_linear_args& a, int passes, hipStream_t s) {
   constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
-  constexpr auto kern = skinny2_kernel<EPI, CT, MT, CH, NWV, LA, SC, WD, RPW>;
+  constexpr auto kern = skinny2_kernel<false, EPI, CT, MT, CH, NWV, LA, SC, WD, RPW>;
   constexpr size_t red_bytes = (size_t)NWV * NM * CT * MT * 1024;
   if constexpr (red_bytes > 156 * 1024) return 1;
   const size_t smem = red_bytes + (size_t)passes * MT * 16 * sizeof(float);
   ua2_allow_big_lds<kern>();
   const int mtiles = ua2_ceil_div(a.M, 16), ntiles = ua2_ceil_div(a.N, 16);
   const dim3 grid(ua2_ceil_div(ntiles, CT), ua2_ceil_div(mtiles, MT * passes));
-  hipLaunchKernelGGL(kern, grid, dim3(NWV / RPW * 64), smem, s, a, reinterpret_cast<const u32x4*>(a.x_packed ? a.x_packed : a.workspace), passes);
+  hipLaunchKernelGGL(kern, grid, dim3(NWV / RPW * 64), smem, s, a, reinterpret_cast<const u32x4*>(a.x_packed ? a.x_packed : a.workspace), passes, Ua2W8{});
   ua2_count_launch(UA2_CNT_SKINNY2);
   return 0;
+}
+
+template <int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0>
+int launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, int passes, hipStream_t s, bool dry) {
+  constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
+  constexpr auto kern = skinny2_kernel<true, EPI, CT, MT, CH, NWV, LA, SC, WD>;
+  constexpr size_t red_bytes = (size_t)NWV * NM * CT * MT * 1024;
+  if constexpr (red_bytes > 156 * 1024) return 1;
+  if (dry) return 0;                                     // the question was only whether the form exists
+  const size_t smem = red_bytes + (size_t)passes * MT * 16 * sizeof(float);
+  ua2_allow_big_lds<kern>();
+  const int mtiles = ua2_ceil_div(a.M, 16), ntiles = ua2_ceil_div(a.N, 16);
+  const dim3 grid(ua2_ceil_div(ntiles, CT), ua2_ceil_div(mtiles, MT * passes));
+  hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), smem, s, a, reinterpret_cast<const u32x4*>(a.x_packed ? a.x_packed : a.workspace), passes, w8);
+  ua2_count_launch(UA2_CNT_SKINNY2_W8);
+  return 0;
+}
+
+// The fp8 forms: the variants pick_variant can return (all variants give the same bits, and the fp8 launch of a shape takes the variant its
+// bf16 launch gets), each with and without the scaled consumer, and nothing of the experiment table beyond them.  An odd ring has no fp8
+// form (two chunks per load).
+template <int EPI, int CH, int NWV>
+int launch_variant_w8(const ua2_linear_args& a, const Ua2W8& w8, const Variant& v, hipStream_t s, bool dry) {
+  constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
+  if (v.rpw != 1) return 1;
+#define UA2_SK8(CT_, MT_, LA_, WD_)                                                                                              \
+  if (v.wd == WD_ && (WD_ == 0 || v.passes == 1) && v.ct == CT_ && v.mt == MT_ && v.la == LA_) {                                    \
+    constexpr bool tiles = CH % 2 == 0 && CH % LA_ == 0 && WD_ % 2 == 0 && WD_ < CH && (WD_ == 0 || CH % (WD_ ? WD_ : 1) == 0);     \
+    if constexpr (EPI != UA2_EPI_RESIDUAL && tiles && regs_needed(NM, CT_, MT_, CH, LA_, NWV, true, WD_, 1, true) <= 2048 / NWV) {  \
+      if (a.prologue == UA2_PRO_SCALED) return launch_one_w8<EPI, CT_, MT_, CH, NWV, LA_, true, WD_>(a, w8, v.passes, s, dry);          \
+    }                                                                                                                            \
+    if (a.prologue == UA2_PRO_SCALED) return 1;                                                                                  \
+    if constexpr (tiles && regs_needed(NM, CT_, MT_, CH, LA_, NWV, false, WD_, 1, true) <= 2048 / NWV)                             \
+      return launch_one_w8<EPI, CT_, MT_, CH, NWV, LA_, false, WD_>(a, w8, v.passes, s, dry);                                         \
+    return 1;                                                                                                                    \
+  }
+  if constexpr (EPI == UA2_EPI_SWIGLU) {
+    UA2_SK8(2, 4, 1, 6) UA2_SK8(2, 4, 2, 6) UA2_SK8(2, 4, 1, 4)
+  }
+  if (v.wd != 0) return 1;
+  UA2_SK8(1, 4, 1, 0) UA2_SK8(1, 2, 2, 0) UA2_SK8(2, 4, 1, 0) UA2_SK8(2, 2, 2, 0)
+#undef UA2_SK8
+  return 1;
 }
 
 template <int EPI, int CH, int NWV>
@@ -475,8 +580,20 @@ Variant pick_variant(const ua2_linear_args& a, int waves, int ch, int nm) {
 
 }  // namespace
 
+// Rows up to which a launch with fp8 twins streams them through the W8 form of skinny2_kernel: the one-pass regime (<= 64 rows: four row tiles),
+// where the weight stream dominates the launch.  A cost default, not a correctness bound: above it the launch reads the bf16 twin W' through
+// the same kernel family and gives the same bits.  UA2_SKINNY_W8_MAX_ROWS=n (read once; again after ua2_debug_refresh_env); 0 / "off" = never.
+int ua2_skinny_w8_max_rows() {
+  static Ua2EnvInt lim{"UA2_SKINNY_W8_MAX_ROWS", 64};
+  return std::max(lim.get(), 0);
+}
+
 // Returns 0 when launched, 1 when this problem is outside the kernel's table (the caller uses the older skinny kernel).
-int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s) {
+// w8: fp8 twins of the launch's weight(s) — streamed instead of a.w0 / a.w1 when the launch is one the fp8 form takes (more rows than the
+// launchers give the decode kernel, up to ua2_skinny_w8_max_rows(), K % 64 == 0, a form of the table below); otherwise the launch reads the
+// bf16 twin as without them, except for a caller that asked for the fp8 kernel by name (w8->strict): 1, never the twin in its place.
+// dry (with w8): launch nothing, answer only whether the fp8 form would take the launch.
+int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2W8* w8, bool dry) {
   if (a.dtype != UA2_BF16) return 1;
   if (a.K % 32) return 1;
   const int nchunks = a.K / 32;
@@ -484,7 +601,11 @@ int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipS
   // the packed operand is addressed through one buffer resource (32-bit size / offsets): past 4 GiB the loads would wrap
   // and return zeros — leave such a problem to the tiled kernel
   if ((uint64_t)ua2_ceil_div(a.M, 16) * (uint64_t)nchunks * 1024ull >= (1ull << 32)) return 1;
-  if (getenv("UA2_SKINNY2") == nullptr)                   // a forced variant means the sweep tool is measuring skinny2_kernel itself
+  const bool strict = w8 && w8->strict;
+  const bool use_w8 = w8 && w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && a.K % 64 == 0 &&
+                      a.M > ua2_gemv_rows_preferred(a.dtype, a.K) && a.M <= ua2_skinny_w8_max_rows();
+  if ((strict || dry) && !use_w8) return 1;
+  if (getenv("UA2_SKINNY2") == nullptr && !strict && !dry)   // a forced variant means the sweep tool is measuring skinny2_kernel itself
     if (const int rc = rsplit_try_launch(a, geo, s); rc <= 0) return rc;
   const int ch = nchunks / geo.waves;
   const int nm = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
@@ -496,17 +617,31 @@ int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipS
   if (off) return 1;
   if (v.passes < 1) v.passes = 1;
   int rc = 1;
+  // K = 3072: 12 ranges x 8 chunks (grids <= 320 tiles) or 8 x 12 (large grids: SwiGLU, lm_head)
+  // K = 8192: 16 x 16
+  // K = 2048: 16 x 4 (small grids) or 8 x 8 (SwiGLU, audio_head)
+#define UA2_GEOS                                                                                            \
+  UA2_GEO(UA2_EPI_QKV_ROPE, 8, 12) UA2_GEO(UA2_EPI_RESIDUAL, 8, 12) UA2_GEO(UA2_EPI_STORE, 8, 12)           \
+  UA2_GEO(UA2_EPI_SWIGLU, 12, 8) UA2_GEO(UA2_EPI_STORE, 12, 8) UA2_GEO(UA2_EPI_QKV_ROPE, 12, 8)             \
+  UA2_GEO(UA2_EPI_RESIDUAL, 16, 16)                                                                         \
+  UA2_GEO(UA2_EPI_QKV_ROPE, 4, 16) UA2_GEO(UA2_EPI_RESIDUAL, 4, 16) UA2_GEO(UA2_EPI_STORE, 4, 16)           \
+  UA2_GEO(UA2_EPI_SWIGLU, 8, 8) UA2_GEO(UA2_EPI_STORE, 8, 8)
+  if (use_w8) {                                           // the same table: only the weight stream differs
+#define UA2_GEO(EPI_, CH_, NWV_) \
+    if (a.epilogue == EPI_ && ch == CH_ && geo.waves == NWV_) rc = launch_variant_w8<EPI_, CH_, NWV_>(a, *w8, v, s, dry);
+    UA2_GEOS
+#undef UA2_GEO
+    if (dry) return rc;
+    if (rc == 0) { UA2_LAUNCH_CHECK(); return 0; }
+    // no fp8 form of this shape / variant (toy sizes, an odd forced ring): by name an error upstream, otherwise the twin below
+    if (strict) return 1;
+    rc = 1;
+  }
 #define UA2_GEO(EPI_, CH_, NWV_) \
   if (a.epilogue == EPI_ && ch == CH_ && geo.waves == NWV_) rc = launch_variant<EPI_, CH_, NWV_>(a, v, s);
-  // K = 3072: 12 ranges x 8 chunks (grids <= 320 tiles) or 8 x 12 (large grids: SwiGLU, lm_head)
-  UA2_GEO(UA2_EPI_QKV_ROPE, 8, 12) UA2_GEO(UA2_EPI_RESIDUAL, 8, 12) UA2_GEO(UA2_EPI_STORE, 8, 12)
-  UA2_GEO(UA2_EPI_SWIGLU, 12, 8) UA2_GEO(UA2_EPI_STORE, 12, 8) UA2_GEO(UA2_EPI_QKV_ROPE, 12, 8)
-  // K = 8192: 16 x 16
-  UA2_GEO(UA2_EPI_RESIDUAL, 16, 16)
-  // K = 2048: 16 x 4 (small grids) or 8 x 8 (SwiGLU, audio_head)
-  UA2_GEO(UA2_EPI_QKV_ROPE, 4, 16) UA2_GEO(UA2_EPI_RESIDUAL, 4, 16) UA2_GEO(UA2_EPI_STORE, 4, 16)
-  UA2_GEO(UA2_EPI_SWIGLU, 8, 8) UA2_GEO(UA2_EPI_STORE, 8, 8)
+  UA2_GEOS
 #undef UA2_GEO
+#undef UA2_GEOS
   UA2_CHECK(!(forced && rc == 1), "UA2_SKINNY2=%d,%d,%d,%d,%d,%d is not built for this geometry (epilogue %d, %d ranges x %d chunks)", v.ct, v.mt,
             v.la, v.passes, v.wd, v.rpw, a.epilogue, geo.waves, ch);
   if (rc == 0) UA2_LAUNCH_CHECK();

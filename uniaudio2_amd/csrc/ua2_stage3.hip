@@ -155,7 +155,9 @@ void fresh_args(const ua2_stage3* h, ua2_linear_args& a) {
 }
 
 // Every Linear of the frame goes through here: with fp8 twins attached, a launch whose weight(s) all have one hands them to the launcher,
-// which streams them where the decode kernel serves the launch (few rows) and reads a.w0 / a.w1 — the bf16 forms of W' — everywhere else.
+// which streams them where the decode kernel serves the launch (up to 5 rows) or the weights-stationary kernel does (6 ..
+// UA2_SKINNY_W8_MAX_ROWS rows of a released Linear shape: decode frames, and prefill chunks that small) and reads a.w0 / a.w1 — the bf16
+// forms of W' — everywhere else.  Same bits either way.
 int lin(const ua2_stage3* h, const ua2_linear_args& a, hipStream_t s) {
   if (h->w8.empty()) return ua2_linear_launch(a, s);
   const auto t0 = h->w8.find(a.w0);

@@ -119,7 +119,7 @@ class Model_stage3(nn.Module):
         weight_dtype: None | torch.float8_e4m3fn (left out: self.weight_dtype).  fp8 (bf16 plans only; LOSSY: relative rms error of a
         weight 2.7e-2 against bf16's 1.6e-3): every Linear of the four GPTs, projection, audio_head[i] and lm_head is replaced by
         W' = RNE_e4m3fn(W 2^-e) 2^e with a power-of-two scale per output row (ops.dequant_w8) — embeddings, norms, RoPE tables and
-        the K/V caches are not touched.  The packed bf16 weights then hold W' and the launches that go to the few-row decode kernel (frames of up to 5 rows by default) stream the fp8 images
+        the K/V caches are not touched.  The packed bf16 weights then hold W' and the launches of decode frames of up to 64 rows (the few-row decode kernel up to 5, the weights-stationary kernel above) stream the fp8 images
         (half the bytes); the plan is bit-identical to a bf16 plan loaded with W'.  Costs 1.5 x the bf16 weight memory."""
         p0 = self.projection.weight
         device, dtype = p0.device, (dtype or p0.dtype)

@@ -100,6 +100,14 @@ def linear_w8(args, w0, w1=None):
     check(lib.ua2_linear_w8(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8")
 
 
+def linear_w8_many(args, w0, w1=None):
+    """ua2_linear_w8_many: the many-row launch `args` (6 .. UA2_SKINNY_W8_MAX_ROWS rows, a workspace or x_packed; w0 / w1 = the bf16 twins)
+    on the fp8 twins w0, w1 = (q, exp) through the weights-stationary kernel; raises where that kernel does not serve the launch."""
+    r0 = _lib.W8Ref(ptr(w0[0]), ptr(w0[1]))
+    r1 = _lib.W8Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
+    check(lib.ua2_linear_w8_many(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8_many")
+
+
 def kv_geom(k_pool, v_pool, page_table, n_head, n_kv, head_size, ring_pages=0):
     g = KvGeom()
     g.ring_pages = ring_pages
@@ -158,6 +166,19 @@ def linear_chain_timed(args_list, iters):
     ms = C.c_float(0.0)
     check(lib.ua2_linear_chain_timed(arr, len(args_list), iters, stream(), C.byref(ms)), "ua2_linear_chain_timed")
     return ms.value / (len(args_list) * iters)
+
+
+def linear_w8_many_chain_timed(args_list, twins, iters):
+    """Average milliseconds per launch of the given launches through ua2_linear_w8_many, back to back, HIP-event timed: the fp8 side of
+    linear_chain_timed (same host path).  twins[i] = ((q, exp) of w0, (q, exp) of w1 or None)."""
+    n = len(args_list)
+    arr = (LinearArgs * n)(*args_list)
+    r0 = (_lib.W8Ref * n)(*[_lib.W8Ref(ptr(t[0][0]), ptr(t[0][1])) for t in twins])
+    has1 = any(t[1] is not None for t in twins)
+    r1 = (_lib.W8Ref * n)(*[_lib.W8Ref(ptr(t[1][0]), ptr(t[1][1])) if t[1] is not None else _lib.W8Ref() for t in twins]) if has1 else None
+    ms = C.c_float(0.0)
+    check(lib.ua2_linear_w8_many_chain_timed(arr, r0, r1, n, iters, stream(), C.byref(ms)), "ua2_linear_w8_many_chain_timed")
+    return ms.value / (n * iters)
 
 
 def attn_groups(pos, seq, n_head, n_kv, device, q_tiles=None):
