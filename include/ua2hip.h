@@ -76,7 +76,12 @@ enum ua2_sum_order { UA2_SUM_ORDER_INVARIANT = 0, UA2_SUM_ORDER_FREE = 1 };
 enum ua2_norm_kind {
   UA2_NORM_RMS_LIT = 0,   /* (x * rsqrt(mean(x^2) + eps)) * w           lit_model.py:883-890                     */
   UA2_NORM_RMS_MOSHI = 1, /* x * (alpha * rsqrt(eps + mean(x^2)))       llm_modules/transformer.py:34-46          */
-  UA2_NORM_LAYERNORM = 2  /* (x - mean) * rsqrt(var + eps) * w + b      nn.LayerNorm (create_norm_fn :111-112)    */
+  UA2_NORM_LAYERNORM = 2  /* (x - mean) * rsqrt(var + eps) * w + b      nn.LayerNorm (create_norm_fn :111-112).
+                             Two passes over the row, both in one fixed order (the corrected two-pass form): mean = sum(x) / K;
+                             then, with d = x - mean, var = mean(d^2) - (sum(d) / K)^2 — the CENTRED variance, not
+                             mean(x^2) - mean^2, which cancels once |mean| >> std — and the operand is
+                             ((x - mean) - sum(d) / K) * rsqrt(var + eps) * w + b: sum(d) / K is the rounding error the fp32
+                             sum left in the mean. */
 };
 /* RoPE flavours of UA2_EPI_QKV_ROPE */
 enum ua2_rope_mode {

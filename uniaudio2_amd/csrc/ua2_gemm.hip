@@ -46,7 +46,7 @@ __global__ __launch_bounds__(1024) void gemm_prep_kernel(const ua2_linear_args a
   const bool live = m < a.M;
   const float* xr = a.x + (size_t)(live ? m : 0) * a.ldx;
   const bool ln = (PRO == UA2_PRO_NORM) && a.norm_kind == UA2_NORM_LAYERNORM;
-  NormStat st{0.f, 1.f};
+  NormStat st{0.f, 1.f, 0.f};
   if constexpr (PRO == UA2_PRO_NORM) {
     // identical to the decode kernel's pass 1: thread t owns k = 4t, 4t + 4*nthreads, ...
     float ss = 0.f, sm = 0.f;
@@ -62,6 +62,18 @@ __global__ __launch_bounds__(1024) void gemm_prep_kernel(const ua2_linear_args a
     float t = 0.f, u = 0.f;
     for (int w = 0; w < nw; ++w) { t += ssq[w]; u += ssum[w]; }
     st = norm_stat(a, u, t);
+    if (ln) {                                  // the decode kernel's second pass (norm_stat_centred), same order
+      float cs = 0.f, sd = 0.f;
+      for (int k = tid * 4; k < a.K; k += nthreads * 4) centred4(cs, sd, *reinterpret_cast<const float4*>(xr + k), st.mean);
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
+      __syncthreads();                         // every thread has read the first pass's partials
+      if (lane == 0) { ssq[wave] = cs; ssum[wave] = sd; }
+      __syncthreads();
+      float c = 0.f, d = 0.f;
+      for (int w = 0; w < nw; ++w) { c += ssq[w]; d += ssum[w]; }
+      norm_stat_centred(a, st, c, d);
+    }
   }
   char* base = reinterpret_cast<char*>(apack) + (size_t)(m >> 4) * nchunks * 1024 + (size_t)(m & 15) * 16;
   for (int k = tid * 4; k < nchunks * KC; k += nthreads * 4) {
@@ -90,6 +102,44 @@ __global__ __launch_bounds__(1024) void gemm_prep_kernel(const ua2_linear_args a
       *reinterpret_cast<float4*>(dst) = t;
     }
   }
+}
+
+// Butterfly of NCH per-lane partial chains over the 64 lanes of a wave, for gemm_prep16_kernel.
+// The decode kernel butterflies every chain over its 64 lanes (s += shfl_xor(s, 32), 16, ..., 1): 12 shuffles per virtual wave.
+// Same adds with a sixth of the shuffles: at each level two chains share one exchange — the lanes whose bit is clear keep
+// chain A (own + partner's A), the others chain B — so the registers halve per level and a chain's total ends up in ch[0] of the
+// lanes its index selects (bit 0 -> lane bit 32, bit 1 -> 16, ...: chain_lane).  own + other, as the butterfly: the same bits.
+template <int NCH>
+__device__ __forceinline__ void chains_reduce(float (&ch)[NCH], int lane) {
+  int n = NCH;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const bool hi = (lane & o) != 0;
+    const int pairs = n / 2;
+#pragma unroll
+    for (int i = 0; i < NCH / 2; ++i) {
+      if (i < pairs) {
+        const float send = hi ? ch[2 * i] : ch[2 * i + 1], keep = hi ? ch[2 * i + 1] : ch[2 * i];
+        ch[i] = keep + __shfl_xor(send, o);
+      }
+    }
+    if (n & 1) {                                         // the odd one out: a plain butterfly level
+      const float last = ch[n - 1];
+      ch[pairs] = last + __shfl_xor(last, o);
+    }
+    n = pairs + (n & 1);
+  }
+}
+// lane holding chain w's total (in ch[0]) after the six levels
+template <int NCH>
+__device__ __forceinline__ constexpr int chain_lane(int w) {
+  int n2 = NCH, l = 0;
+  for (int o = 32; o >= 1; o >>= 1) {
+    const int pairs = n2 / 2;
+    if (w < 2 * pairs) { if (w & 1) l |= o; w >>= 1; } else { w = pairs; }
+    n2 = pairs + (n2 & 1);
+  }
+  return l;
 }
 
 // ---- prep, one row TILE per workgroup (K <= 4096 bf16 / 2048 fp32) -------------------------------------------------
@@ -135,7 +185,7 @@ __global__ __launch_bounds__(64 * ROWS) void gemm_prep16_kernel(const ua2_linear
       }
     }
   }
-  NormStat st{0.f, 1.f};
+  NormStat st{0.f, 1.f, 0.f};
   if constexpr (PRO == UA2_PRO_NORM) {
     // chains 0 .. NVW-1: sums of squares, NVW .. 2 NVW - 1: sums
     float ch[2 * NVW];
@@ -144,46 +194,30 @@ __global__ __launch_bounds__(64 * ROWS) void gemm_prep16_kernel(const ua2_linear
 #pragma unroll
     for (int p = 0; p < MAXV; ++p)                       // ascending p inside a chain = the decode kernel's ascending k
       if (4 * lane + 256 * p < a.K) { ch[p % NVW] = sumsq4(ch[p % NVW], v[p]); ch[NVW + p % NVW] = sum4(ch[NVW + p % NVW], v[p]); }
-    // The decode kernel butterflies every chain over its 64 lanes (s += shfl_xor(s, 32), 16, ..., 1): 12 shuffles per virtual wave.
-    // Same adds with a sixth of the shuffles: at each level two chains share one exchange — the lanes whose bit is clear keep
-    // chain A (own + partner's A), the others chain B — so the registers halve per level and a chain's total ends up in the lanes
-    // its index selects (bit 0 -> lane bit 32, bit 1 -> 16, ...).  own + other, as the butterfly: the same bits.
-    constexpr int NCH = 2 * NVW;
-    int n = NCH;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const bool hi = (lane & o) != 0;
-      const int pairs = n / 2;
-#pragma unroll
-      for (int i = 0; i < NCH / 2; ++i) {
-        if (i < pairs) {
-          const float send = hi ? ch[2 * i] : ch[2 * i + 1], keep = hi ? ch[2 * i + 1] : ch[2 * i];
-          ch[i] = keep + __shfl_xor(send, o);
-        }
-      }
-      if (n & 1) {                                       // the odd one out: a plain butterfly level
-        const float last = ch[n - 1];
-        ch[pairs] = last + __shfl_xor(last, o);
-      }
-      n = pairs + (n & 1);
-    }
-    // lane holding chain w's total after the six levels
-    auto lane_of = [](int w) {
-      int n2 = NCH, l = 0;
-      for (int o = 32; o >= 1; o >>= 1) {
-        const int pairs = n2 / 2;
-        if (w < 2 * pairs) { if (w & 1) l |= o; w >>= 1; } else { w = pairs; }
-        n2 = pairs + (n2 & 1);
-      }
-      return l;
-    };
+    chains_reduce<2 * NVW>(ch, lane);
     float t = 0.f, u = 0.f;
 #pragma unroll
     for (int w = 0; w < NVW; ++w) {
-      t += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ch[0]), lane_of(w)));
-      u += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ch[0]), lane_of(NVW + w)));
+      t += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ch[0]), chain_lane<2 * NVW>(w)));
+      u += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ch[0]), chain_lane<2 * NVW>(NVW + w)));
     }
     st = norm_stat(a, u, t);
+    if (ln) {                                  // the decode kernel's second pass (norm_stat_centred) in the same NVW + NVW chains
+      float cc[2 * NVW];
+#pragma unroll
+      for (int w = 0; w < 2 * NVW; ++w) cc[w] = 0.f;
+#pragma unroll
+      for (int p = 0; p < MAXV; ++p)
+        if (4 * lane + 256 * p < a.K) centred4(cc[p % NVW], cc[NVW + p % NVW], v[p], st.mean);
+      chains_reduce<2 * NVW>(cc, lane);
+      float c = 0.f, d = 0.f;
+#pragma unroll
+      for (int w = 0; w < NVW; ++w) {
+        c += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cc[0]), chain_lane<2 * NVW>(w)));
+        d += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cc[0]), chain_lane<2 * NVW>(NVW + w)));
+      }
+      norm_stat_centred(a, st, c, d);
+    }
   }
   // image row (16-row form) or this row's 16-byte slot of fragment block 0 (4-row form: element k of row m lives in block
   // k / KC at lane (k % KC) / EPL * 16 + (m & 15), as gemm_prep_kernel addresses it)

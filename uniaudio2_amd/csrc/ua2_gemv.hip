@@ -198,7 +198,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       }
     }
   } else if (one) {
-    NormStat st{0.f, 1.f};
+    NormStat st{0.f, 1.f, 0.f};
     if constexpr (PRO == UA2_PRO_NORM) {
       float ss = 0.f, sm = 0.f;
 #pragma unroll
@@ -213,6 +213,20 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       float t = 0.f, u = 0.f;
       for (int w = 0; w < nw; ++w) { t += ssq[w * 16]; u += ssum[w * 16]; }   // every thread, same order: no second barrier
       st = norm_stat(a, u, t);
+      if (ln) {                                // second pass (norm_stat_centred), the first pass's order
+        float cs = 0.f, sd = 0.f;
+#pragma unroll
+        for (int it = 0; it < XPT; ++it)
+          if ((tid + it * nthreads) * 4 < a.K) centred4(cs, sd, xv[it], st.mean);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
+        __syncthreads();                       // every thread has read the first pass's partials
+        if (lane == 0) { ssq[wave * 16] = cs; ssum[wave * 16] = sd; }
+        __syncthreads();
+        float c = 0.f, d = 0.f;
+        for (int w = 0; w < nw; ++w) { c += ssq[w * 16]; d += ssum[w * 16]; }
+        norm_stat_centred(a, st, c, d);
+      }
     }
 #pragma unroll
     for (int it = 0; it < XPT; ++it) {
@@ -252,11 +266,32 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
         rstd_s[tid] = st.rstd; mean_s[tid] = st.mean;
       }
       __syncthreads();
+      if (ln) {                                // second pass per row (norm_stat_centred), the first pass's order
+        for (int r0 = 0; r0 < rows; ++r0) {
+          const float* xr = a.x + (size_t)(m0 + r0) * a.ldx;
+          const float mean = mean_s[r0];
+          float cs = 0.f, sd = 0.f;
+          for (int k = tid * 4; k < a.K; k += nthreads * 4) centred4(cs, sd, *reinterpret_cast<const float4*>(xr + k), mean);
+#pragma unroll
+          for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
+          if (lane == 0) { ssq[wave * 16 + r0] = cs; ssum[wave * 16 + r0] = sd; }
+        }
+        __syncthreads();
+        if (tid < rows) {
+          float c = 0.f, d = 0.f;
+          for (int w = 0; w < nw; ++w) { c += ssq[w * 16 + tid]; d += ssum[w * 16 + tid]; }
+          NormStat st{mean_s[tid], 1.f, 0.f};
+          norm_stat_centred(a, st, c, d);
+          rstd_s[tid] = st.rstd;
+          ssum[tid] = st.mean_lo;              // row tid's own column of partials: nobody else reads it
+        }
+        __syncthreads();
+      }
     }
     for (int r0 = 0; r0 < rows; ++r0) {
       const float* xr = a.x + (size_t)(m0 + r0) * a.ldx;
-      NormStat st{0.f, 1.f};
-      if constexpr (PRO == UA2_PRO_NORM) { st.rstd = rstd_s[r0]; st.mean = mean_s[r0]; }
+      NormStat st{0.f, 1.f, 0.f};
+      if constexpr (PRO == UA2_PRO_NORM) { st.rstd = rstd_s[r0]; st.mean = mean_s[r0]; if (ln) st.mean_lo = ssum[r0]; }
       for (int k = tid * 4; k < nchunks * KC; k += nthreads * 4) {
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < a.K) {

@@ -86,24 +86,48 @@ __device__ __forceinline__ float sum4(float acc, const float4& t) {
   return acc;
 }
 
+// LayerNorm's second pass over a row: d = x - mean rounded once, then the centred sum of squares (fused accumulate) and the sum of
+// the differences, in sumsq4 / sum4's order
+__device__ __forceinline__ void centred4(float& csq, float& dsum, const float4& t, float mean) {
+  float d;
+  d = __fsub_rn(t.x, mean); csq = __fmaf_rn(d, d, csq); dsum = __fadd_rn(dsum, d);
+  d = __fsub_rn(t.y, mean); csq = __fmaf_rn(d, d, csq); dsum = __fadd_rn(dsum, d);
+  d = __fsub_rn(t.z, mean); csq = __fmaf_rn(d, d, csq); dsum = __fadd_rn(dsum, d);
+  d = __fsub_rn(t.w, mean); csq = __fmaf_rn(d, d, csq); dsum = __fadd_rn(dsum, d);
+}
+
 // ---- normalisation flavours of UA2_PRO_NORM -----------------------------------------------------
-struct NormStat { float mean, rstd; };
+// The RMS flavours need one pass over the row (sum of squares).  LayerNorm takes two (the corrected two-pass form): the first
+// pass's sum gives mean = sum / K; the second walks the row again with d = x - mean and gives the CENTRED sum of squares and
+// sum(d).  mean(x^2) - mean^2 loses every digit of the variance once |mean| >> std (a row of mean 1e3, std 1 came out with rstd
+// wrong by 8-10 %), and the fp32 sum of such a row is itself only good to ~1e-7 |mean| K^0.5, which shifts every x - mean by the
+// same amount: sum(d) / K is that error, kept as mean_lo and subtracted after mean — x - mean is exact there, so the centred value
+// carries one rounding of ITSELF instead of one of the mean.  var = csq / K - mean_lo^2.
+// Every kernel walks the second pass in the first one's order (same element -> thread map, same butterfly, same wave order), so
+// a row's statistics stay bit-identical whatever kernel and batch it is in.
+struct NormStat { float mean, rstd, mean_lo; };
 __device__ __forceinline__ NormStat norm_stat(const ua2_linear_args& a, float sum, float sumsq) {
   NormStat s;
-  const float ms = sumsq / (float)a.K;
+  s.mean_lo = 0.f;
   if (a.norm_kind == UA2_NORM_LAYERNORM) {
     s.mean = sum / (float)a.K;
-    s.rstd = 1.0f / sqrtf(fmaxf(__fsub_rn(ms, __fmul_rn(s.mean, s.mean)), 0.f) + a.eps);
+    s.rstd = 1.0f;                           // set by the second pass: norm_stat_centred
   } else {
     s.mean = 0.f;
-    s.rstd = 1.0f / sqrtf(ms + a.eps);     // torch.rsqrt(mean(x*x) + eps)  (lit :886-887; Moshi: eps + mean, same sum)
+    s.rstd = 1.0f / sqrtf(sumsq / (float)a.K + a.eps);     // torch.rsqrt(mean(x*x) + eps)  (lit :886-887; Moshi: eps + mean, same sum)
   }
   return s;
+}
+// csq = sum (x - mean)^2, dsum = sum (x - mean) of the second pass
+__device__ __forceinline__ void norm_stat_centred(const ua2_linear_args& a, NormStat& s, float csq, float dsum) {
+  s.mean_lo = dsum / (float)a.K;
+  const float var = fmaxf(__fsub_rn(csq / (float)a.K, __fmul_rn(s.mean_lo, s.mean_lo)), 0.f);
+  s.rstd = 1.0f / sqrtf(var + a.eps);                      // F.layer_norm: rsqrt(mean((x - mean)^2) + eps)
 }
 __device__ __forceinline__ float norm_apply(const ua2_linear_args& a, float x, float w, float b, const NormStat& s) {
   if (a.norm_kind == UA2_NORM_RMS_LIT) return __fmul_rn(__fmul_rn(x, s.rstd), w);      // (x*rstd)*w
   if (a.norm_kind == UA2_NORM_RMS_MOSHI) return __fmul_rn(x, __fmul_rn(w, s.rstd));    // x*(alpha*rstd)
-  return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x, s.mean), s.rstd), w), b);                    // layer norm
+  return __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fsub_rn(x, s.mean), s.mean_lo), s.rstd), w), b);   // layer norm
 }
 
 // ---- epilogues (thread = one (row, col) of the 16 x 16 output tile; v[t] = reduced sums) ----
