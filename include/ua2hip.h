@@ -459,6 +459,25 @@ typedef struct ua2_beam_pool {
  * pointers.  Two launches (copy, then tables). */
 int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t* row_pos, int32_t pos_add, const ua2_beam_pool* pools,
                      int32_t n_pools, int32_t* const* tables, int32_t n_tables, int32_t table_rows, int32_t max_pages, void* stream);
+/* Several beams in one frame (added under ABI v10 like the entry points above, which are their G = 1 case: same kernels, same bits).
+ * G >= 1 groups (utterances) of W <= 8 slots, G * W <= 64; group g's slot j is row r = g * W + j of the frame.  The structs keep their
+ * layout; group g's state lies at fixed strides from the base pointers of ua2_beam_state:
+ *   score / fin / len / parent + 8 g,  ctrl + 4 g,  cand_logp / cand_id + 64 g,  log + g * log_cap * W * 4  (its [log_cap, W, 4] log);
+ * lp_inv, lp_n, log_cap and eos are shared.  Every group starts as a single beam does.
+ * ua2_beam_step_groups: logits [G * W, ld], token rows g * W + j.  One 1024-thread workgroup per live row (the contract of the
+ *   log-sum-exp above), then one workgroup per group that reads and writes only that group's state, token rows and log; group g's
+ *   ctrl[1] latches the step at which all ITS slots were first finished.  A group whose slots are all finished is a fixed point of the
+ *   step, so it can keep running beside live ones.  A group's result does not depend on the other groups.
+ * ua2_beam_reorder_groups: parent strided 8 per group, values local to the group (0 .. W - 1; NULL: slot 0 of each group);
+ *   row_pos [G * W].  With R = G * W the two page sets are R-based: row r's own page for position n is
+ *   ((n & 1) * R + r) * max_pages + n / 64, and the parent of row g * W + j is row g * W + parent[8 g + j].  The table launch runs one
+ *   workgroup per group over its W rows (shared memory W * max_pages * 4 <= 48 KB); a group touches only its own table rows and
+ *   its own rows of the two page sets.  Checked before any launch: 1 <= W <= 8, G >= 1, G * W <= 64, table_rows >= 2 G W. */
+int ua2_beam_step_groups(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st,
+                         int32_t* token, int32_t token_ld, void* stream);
+int ua2_beam_reorder_groups(int32_t W, int32_t G, const int32_t* parent, const int32_t* row_pos, int32_t pos_add,
+                            const ua2_beam_pool* pools, int32_t n_pools, int32_t* const* tables, int32_t n_tables,
+                            int32_t table_rows, int32_t max_pages, void* stream);
 
 /* ---- codec: residual vector quantisation ------------------------------------------------ */
 
@@ -817,6 +836,10 @@ int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, int32_t* hi
  * plan's).  Needs 1 <= W <= 8, 2 W <= max_batch (the pages of sequences W .. 2W - 1 are the second page set of the fork) and the
  * three tables of one width.  W = 0 clears.  New buffers, a new W or a new EOS drop the captured frame graphs. */
 int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools, int32_t n_pools);
+/* The same for G groups of W slots (ua2_beam_step_groups; ua2_stage3_set_beam is G = 1): mode 3 frames then have R = G * W rows.  Needs
+ * G >= 1, G * W <= 64 and 2 G W <= max_batch.  A new G drops the captured frame graphs as a new W does. */
+int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
+                               int32_t n_pools);
 /* cfg_scale > 1: frames of (conditional, unconditional) row pairs — rows 2p, 2p + 1; an even row count — sample from the guided
  * logits (ua2_cfg_mix); feedback mode 2 continues every row from its pair's conditional row. */
 int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale);
@@ -860,10 +883,10 @@ int ua2_stage3_feedback(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_e
  * cap_frames select the captured graph. */
 #define UA2_FRAME_DEFER_TEXT_HEAD 64
 #define UA2_DEFER_CAP_ROWS 64
-/* mode 3 (with or without UA2_FRAME_SKIP_AUDIO_EXPERTS, under mode 1's precondition): a beam-search frame of R = W rows — trunk,
+/* mode 3 (with or without UA2_FRAME_SKIP_AUDIO_EXPERTS, under mode 1's precondition): a beam-search frame of R = G * W rows — trunk,
  * lm_head, the beam step on its fp32 logits, the K/V fork, then the text feedback of mode 1 with the ids the step chose (tokens
  * (0 x n_cb, id), masks (0.., 1), row_pos += 1; the frame log's text column holds them).  Checked before any launch: a beam is
- * attached (the set_beam call above) and R equals its W; no classifier-free guidance, no n-gram filter, top-k = 1.  The caller keeps the step
+ * attached (the set_beam calls above) and R equals its G * W; no classifier-free guidance, no n-gram filter, top-k = 1.  The caller keeps the step
  * count within the state's log and length-penalty tables and every position within the caches. */
 int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card,
                      int32_t use_graph, void* stream);

@@ -172,6 +172,9 @@ _EXPORTS = {
     "ua2_beam_step": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
     "ua2_beam_reorder": (C.c_int, [i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),
     "ua2_stage3_set_beam": (C.c_int, [vp, i32, i32, C.POINTER(BeamState), vp, i32]),
+    "ua2_beam_step_groups": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
+    "ua2_beam_reorder_groups": (C.c_int, [i32, i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),
+    "ua2_stage3_set_beam_groups": (C.c_int, [vp, i32, i32, i32, C.POINTER(BeamState), vp, i32]),
     "ua2_qknorm_rope_kv": (C.c_int, [C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, C.POINTER(KvGeom), vp]),
     "ua2_stage3_scratch_floats": (C.c_size_t, [C.POINTER(Stage3Desc)]),
     "ua2_stage3_create": (C.c_int, [C.POINTER(Stage3Desc), C.POINTER(vp)]),

@@ -1,13 +1,18 @@
 // Beam search over the text head, on the device (DESIGN.md §2 "beam search", §4; the rule is a corrected restatement of the
 // reference's evaluation/asr_task.py:438-576, whose own function cannot run).
 //
-// The W hypotheses of a beam are the W rows of one decode frame (rows = sequences 0 .. W - 1).  Per frame:
-//   ua2_beam_step     beam_topw_kernel    one 1024-thread workgroup per LIVE row over its fp32 logits: row maximum, sum of
-//                                         exp(x - m), the W best columns (value descending, id ascending), their log-softmax
-//                     beam_select_kernel  one workgroup: the <= W * W + W candidates in candidate order, the length-normalised
-//                                         scores, the W best (stable), the new per-slot state, parents, fed-back ids, one log record
-//   ua2_beam_reorder  beam_copy_kernel    the K/V fork: slot j's copy of its parent's partial 64-position page, every pool
-//                     beam_table_kernel   the page tables: shared full pages inherited from the parent, the new partial page
+// The W hypotheses of a beam are W rows of one decode frame; G beams ("groups": one per utterance) share a frame, group g's slot j
+// being row g * W + j (rows = sequences 0 .. G * W - 1; G = 1 is the single search).  Per frame:
+//   ua2_beam_step[_groups]     beam_topw_kernel    one 1024-thread workgroup per LIVE row over its fp32 logits: row maximum, sum of
+//                                                  exp(x - m), the W best columns (value descending, id ascending), their log-softmax
+//                              beam_select_kernel  one workgroup per group: the <= W * W + W candidates in candidate order, the
+//                                                  length-normalised scores, the W best (stable), the new per-slot state, parents,
+//                                                  fed-back ids, one log record
+//   ua2_beam_reorder[_groups]  beam_copy_kernel    the K/V fork: a slot's copy of its parent's partial 64-position page, every pool
+//                              beam_table_kernel   one workgroup per group: the page tables — shared full pages inherited from the
+//                                                  parent, the new partial page
+// A group's state lies at fixed strides from the base pointers of ua2_beam_state (8 slots, 4 ctrl words, 64 candidates, log_cap * W
+// log records per group); a group reads and writes only its own state, token rows, log and table rows.
 // Nothing is permuted on the device but page-table entries and at most one partial page per pool and slot; the text of a hypothesis
 // is recovered on the host by walking the step log backwards.
 //
@@ -20,6 +25,7 @@
 namespace {
 
 constexpr int kBeamMaxW = 8;
+constexpr int kBeamMaxRows = 64;
 constexpr int kTopwThreads = 1024;
 constexpr int kTopwBatch = 16;
 constexpr int kMaxCand = kBeamMaxW * kBeamMaxW + kBeamMaxW;
@@ -34,9 +40,10 @@ __global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __
   __shared__ float red[kTopwThreads];
   __shared__ float wv[kTopwThreads / 64];
   __shared__ int wi[kTopwThreads / 64];
-  const int j = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
+  const int j = (blockIdx.x / W) * kBeamMaxW + blockIdx.x % W;   // row g * W + slot -> the slot's place in its group's state
   if (fin[j] != 0) return;                       // the whole workgroup: finished and dead slots produce no candidates from logits
-  const float* row = logits + (size_t)j * ld;
+  const float* row = logits + (size_t)blockIdx.x * ld;
   float lv[kBeamMaxW];
   int li[kBeamMaxW];
 #pragma unroll
@@ -130,7 +137,11 @@ __global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, 
   __shared__ int cpar[kMaxCand], ctok[kMaxCand], cfin[kMaxCand], clen[kMaxCand], taken[kMaxCand];
   __shared__ float sscore[kBeamMaxW];
   __shared__ int sfin[kBeamMaxW], slen[kBeamMaxW];
-  const int tid = threadIdx.x;
+  const int tid = threadIdx.x, g = blockIdx.x;
+  st.score += g * kBeamMaxW; st.fin += g * kBeamMaxW; st.len += g * kBeamMaxW; st.parent += g * kBeamMaxW;
+  st.ctrl += g * 4; st.cand_logp += g * kBeamMaxW * kBeamMaxW; st.cand_id += g * kBeamMaxW * kBeamMaxW;
+  st.log += (size_t)g * st.log_cap * W * 4;
+  token += (size_t)g * W * token_ld;
   if (tid < W) { sfin[tid] = st.fin[tid]; sscore[tid] = st.score[tid]; slen[tid] = max(st.len[tid], 0); }
   __syncthreads();
   // candidate order: slots in slot order, a live slot's W columns in rank order.  Thread (j, r) = j * 8 + r fills the candidate of
@@ -185,23 +196,24 @@ struct BeamTables {
   int32_t* t[3];
 };
 
-// slot j's private page for the column of position n: the static page (row, column) of page set n & 1 — set 0 = the pages of
-// sequences 0 .. W - 1, set 1 = those of sequences W .. 2W - 1 (the static layout: sequence b owns pages [b * max_pages, ..))
-__device__ __forceinline__ int beam_own_page(int n, int j, int W, int max_pages) { return (((n & 1) * W) + j) * max_pages + (n >> 6); }
+// row r's private page for the column of position n: the static page (row, column) of page set n & 1 — set 0 = the pages of
+// sequences 0 .. R - 1, set 1 = those of sequences R .. 2R - 1 (the static layout: sequence b owns pages [b * max_pages, ..));
+// R = G * W rows, so a group owns W rows of either set and the groups' pages are disjoint
+__device__ __forceinline__ int beam_own_page(int n, int r, int R, int max_pages) { return (((n & 1) * R) + r) * max_pages + (n >> 6); }
 
-__global__ __launch_bounds__(256) void beam_copy_kernel(int W, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
+__global__ __launch_bounds__(256) void beam_copy_kernel(int W, int R, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
                                                         int pos_add, const ua2_beam_pool* __restrict__ pools, BeamTables T,
                                                         int table_rows, int max_pages) {
   const ua2_beam_pool P = pools[blockIdx.x];
-  const int j = blockIdx.y;
-  const int n = row_pos[j] + pos_add;              // the next position slot j writes
+  const int r = blockIdx.y, g = r / W, j = r - g * W;
+  const int n = row_pos[r] + pos_add;              // the next position the slot writes
   if (n < 0) return;
   const int c = n >> 6, fill = n & 63;
   if (fill == 0 || c >= max_pages) return;         // the position opens a new page: nothing to carry over
-  const int p = parent ? min(max(parent[j], 0), W - 1) : 0;
+  const int p = g * W + (parent ? min(max(parent[g * kBeamMaxW + j], 0), W - 1) : 0);   // the parent's row: within the group
   const int32_t* tab = T.t[min(max(P.table, 0), 2)];
   const int src = min(max(tab[p * max_pages + c], 0), table_rows * max_pages - 1);
-  const int dst = beam_own_page(n, j, W, max_pages);
+  const int dst = beam_own_page(n, r, R, max_pages);   // < 2 R * max_pages <= table_rows * max_pages (c < max_pages, r < R)
   if (src == dst) return;                          // the start, slot 0: the prompt's page is already its own
   const size_t head_bytes = (size_t)P.head_bytes, page_bytes = (size_t)P.n_kv * UA2_PAGE * head_bytes;
   const char* s = (const char*)P.pool + (size_t)src * page_bytes;
@@ -214,30 +226,32 @@ __global__ __launch_bounds__(256) void beam_copy_kernel(int W, const int32_t* __
   }
 }
 
-// rows 0 .. W - 1 of every table: read everything, barrier, write — a slot's new row is its parent's OLD row
-__global__ __launch_bounds__(256) void beam_table_kernel(int W, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
+// one workgroup per group, its rows g * W .. g * W + W - 1 of every table: read everything, barrier, write — a slot's new row is
+// its parent's OLD row
+__global__ __launch_bounds__(256) void beam_table_kernel(int W, int R, const int32_t* __restrict__ parent, const int32_t* __restrict__ row_pos,
                                                          int pos_add, BeamTables T, int n_tables, int max_pages) {
   extern __shared__ int32_t old[];
-  const int cells = W * max_pages;
+  const int cells = W * max_pages, g = blockIdx.x;
   for (int t = 0; t < n_tables; ++t) {
-    int32_t* tab = T.t[t];
+    int32_t* tab = T.t[t] + (size_t)g * W * max_pages;
     for (int e = threadIdx.x; e < cells; e += blockDim.x) old[e] = tab[e];
     __syncthreads();
     for (int e = threadIdx.x; e < cells; e += blockDim.x) {
       const int j = e / max_pages, col = e - j * max_pages;
-      const int n = row_pos[j] + pos_add;
+      const int n = row_pos[g * W + j] + pos_add;
       if (n < 0) continue;
       const int c = n >> 6;
-      const int p = parent ? min(max(parent[j], 0), W - 1) : 0;
+      const int p = parent ? min(max(parent[g * kBeamMaxW + j], 0), W - 1) : 0;
       if (col < c) tab[e] = old[p * max_pages + col];
-      else if (col == c) tab[e] = beam_own_page(n, j, W, max_pages);
+      else if (col == c) tab[e] = beam_own_page(n, g * W + j, R, max_pages);
     }
     __syncthreads();
   }
 }
 
-int check_state(const ua2_beam_state* st, int W, const char* who) {
+int check_state(const ua2_beam_state* st, int W, int G, const char* who) {
   UA2_CHECK(W >= 1 && W <= kBeamMaxW, "%s: beam width must be in 1..%d, got %d", who, kBeamMaxW, W);
+  UA2_CHECK(G >= 1 && G * W <= kBeamMaxRows, "%s: %d groups of %d slots: need 1 <= G and G * W <= %d rows", who, G, W, kBeamMaxRows);
   UA2_CHECK(st && st->score && st->fin && st->len && st->parent && st->ctrl && st->cand_logp && st->cand_id && st->log && st->lp_inv,
             "%s: NULL state buffer", who);
   UA2_CHECK(st->log_cap >= 1 && st->lp_n >= 2, "%s: log capacity %d / %d length-penalty entries", who, st->log_cap, st->lp_n);
@@ -246,27 +260,35 @@ int check_state(const ua2_beam_state* st, int W, const char* who) {
 
 }  // namespace
 
-extern "C" int ua2_beam_step(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t eos, const ua2_beam_state* st,
-                             int32_t* token, int32_t token_ld, void* stream) {
-  if (int rc = check_state(st, W, "ua2_beam_step")) return rc;
+extern "C" int ua2_beam_step_groups(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st,
+                                    int32_t* token, int32_t token_ld, void* stream) {
+  if (int rc = check_state(st, W, G, "ua2_beam_step")) return rc;
   UA2_CHECK(logits && token && token_ld >= 1, "ua2_beam_step: NULL logits / token buffer");
   UA2_CHECK(V >= W && ld >= V, "ua2_beam_step: need W <= V <= ld (W=%d V=%d ld=%d)", W, V, ld);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(beam_topw_kernel, dim3(W), dim3(kTopwThreads), 0, s, logits, ld, V, W, st->fin, st->cand_logp, st->cand_id);
+  hipLaunchKernelGGL(beam_topw_kernel, dim3(G * W), dim3(kTopwThreads), 0, s, logits, ld, V, W, st->fin, st->cand_logp, st->cand_id);
   UA2_LAUNCH_CHECK();
-  hipLaunchKernelGGL(beam_select_kernel, dim3(1), dim3(64), 0, s, W, V, eos, *st, token, token_ld);
+  hipLaunchKernelGGL(beam_select_kernel, dim3(G), dim3(64), 0, s, W, V, eos, *st, token, token_ld);
   UA2_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t* row_pos, int32_t pos_add, const ua2_beam_pool* pools,
-                                int32_t n_pools, int32_t* const* tables, int32_t n_tables, int32_t table_rows, int32_t max_pages,
-                                void* stream) {
+extern "C" int ua2_beam_step(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t eos, const ua2_beam_state* st,
+                             int32_t* token, int32_t token_ld, void* stream) {
+  return ua2_beam_step_groups(logits, ld, V, W, 1, eos, st, token, token_ld, stream);
+}
+
+extern "C" int ua2_beam_reorder_groups(int32_t W, int32_t G, const int32_t* parent, const int32_t* row_pos, int32_t pos_add,
+                                       const ua2_beam_pool* pools, int32_t n_pools, int32_t* const* tables, int32_t n_tables,
+                                       int32_t table_rows, int32_t max_pages, void* stream) {
   UA2_CHECK(W >= 1 && W <= kBeamMaxW, "ua2_beam_reorder: beam width must be in 1..%d, got %d", kBeamMaxW, W);
+  UA2_CHECK(G >= 1 && G * W <= kBeamMaxRows, "ua2_beam_reorder: %d groups of %d slots: need 1 <= G and G * W <= %d rows", G, W, kBeamMaxRows);
+  const int R = G * W;
   UA2_CHECK(row_pos && tables && n_tables >= 1 && n_tables <= 3 && n_pools >= 0 && (n_pools == 0 || pools), "ua2_beam_reorder: bad arguments");
   UA2_CHECK(pos_add == 0 || pos_add == 1, "ua2_beam_reorder: pos_add must be 0 (start) or 1 (end of a frame)");
-  UA2_CHECK(table_rows >= 2 * W, "ua2_beam_reorder: a beam of %d needs page tables of %d sequences, got %d", W, 2 * W, table_rows);
+  UA2_CHECK(table_rows >= 2 * R, "ua2_beam_reorder: %d beam(s) of %d need page tables of %d sequences, got %d", G, W, 2 * R, table_rows);
   UA2_CHECK(max_pages >= 1 && (size_t)W * max_pages * sizeof(int32_t) <= 48 * 1024, "ua2_beam_reorder: max_pages=%d out of range", max_pages);
+  UA2_CHECK((int64_t)table_rows * max_pages <= 0x7fffffff, "ua2_beam_reorder: %d x %d pages overflow a page index", table_rows, max_pages);
   BeamTables T{};
   for (int t = 0; t < n_tables; ++t) {
     UA2_CHECK(tables[t] != nullptr, "ua2_beam_reorder: table %d is NULL", t);
@@ -275,11 +297,17 @@ extern "C" int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t*
   for (int t = n_tables; t < 3; ++t) T.t[t] = tables[0];
   hipStream_t s = (hipStream_t)stream;
   if (n_pools > 0) {
-    hipLaunchKernelGGL(beam_copy_kernel, dim3(n_pools, W), dim3(256), 0, s, W, parent, row_pos, pos_add, pools, T, table_rows, max_pages);
+    hipLaunchKernelGGL(beam_copy_kernel, dim3(n_pools, R), dim3(256), 0, s, W, R, parent, row_pos, pos_add, pools, T, table_rows, max_pages);
     UA2_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(beam_table_kernel, dim3(1), dim3(256), (size_t)W * max_pages * sizeof(int32_t), s, W, parent, row_pos, pos_add, T,
+  hipLaunchKernelGGL(beam_table_kernel, dim3(G), dim3(256), (size_t)W * max_pages * sizeof(int32_t), s, W, R, parent, row_pos, pos_add, T,
                      n_tables, max_pages);
   UA2_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ua2_beam_reorder(int32_t W, const int32_t* parent, const int32_t* row_pos, int32_t pos_add, const ua2_beam_pool* pools,
+                                int32_t n_pools, int32_t* const* tables, int32_t n_tables, int32_t table_rows, int32_t max_pages,
+                                void* stream) {
+  return ua2_beam_reorder_groups(W, 1, parent, row_pos, pos_add, pools, n_pools, tables, n_tables, table_rows, max_pages, stream);
 }

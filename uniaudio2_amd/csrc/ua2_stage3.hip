@@ -71,8 +71,9 @@ struct ua2_stage3 {
   // n-gram repeat filter of the text-feedback frames (ua2_stage3_set_ngram; ngram_n <= 1 = off): caller-owned device history
   int32_t ngram_n = 0, ngram_fallback = 0, ngram_cap = 0;
   int32_t *ngram_hist = nullptr, *ngram_hist_len = nullptr;
-  // beam search of the text loop (ua2_stage3_set_beam; beam_W == 0 = off): caller-owned device state, the K / V pools of the fork
-  int32_t beam_W = 0, beam_eos = -1, beam_n_pools = 0;
+  // beam search of the text loop (ua2_stage3_set_beam[_groups]; beam_W == 0 = off): caller-owned device state of beam_G groups of
+  // beam_W slots, the K / V pools of the fork
+  int32_t beam_W = 0, beam_G = 1, beam_eos = -1, beam_n_pools = 0;
   ua2_beam_state beam{};
   const ua2_beam_pool* beam_pools = nullptr;
   // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
@@ -637,7 +638,8 @@ extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, 
   return 0;
 }
 
-extern "C" int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools, int32_t n_pools) {
+extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
+                                          int32_t n_pools) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_beam: NULL handle");
   auto drop = [&] {
     for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);   // recorded beam frames bake the state's pointers: drop them
@@ -645,12 +647,13 @@ extern "C" int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const 
   };
   if (W == 0) {
     if (h->beam_W != 0) drop();
-    h->beam_W = 0;
+    h->beam_W = 0; h->beam_G = 1;
     return 0;
   }
   const ua2_stage3_desc& d = h->d;
   UA2_CHECK(W >= 1 && W <= 8, "ua2_stage3_set_beam: beam width must be in 1..8, got %d", W);
-  UA2_CHECK(2 * W <= d.max_batch, "ua2_stage3_set_beam: a beam of %d needs a plan of %d sequences (max_batch), got %d", W, 2 * W, d.max_batch);
+  UA2_CHECK(G >= 1 && G * W <= 64, "ua2_stage3_set_beam: %d groups of %d slots: need 1 <= G and G * W <= 64 rows", G, W);
+  UA2_CHECK(2 * G * W <= d.max_batch, "ua2_stage3_set_beam: %d beam(s) of %d need a plan of %d sequences (max_batch), got %d", G, W, 2 * G * W, d.max_batch);
   UA2_CHECK(st && st->score && st->fin && st->len && st->parent && st->ctrl && st->cand_logp && st->cand_id && st->log && st->lp_inv,
             "ua2_stage3_set_beam: NULL state buffer");
   UA2_CHECK(st->log_cap >= 1 && st->lp_n >= 2, "ua2_stage3_set_beam: log capacity %d / %d length-penalty entries", st->log_cap, st->lp_n);
@@ -658,9 +661,13 @@ extern "C" int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const 
   UA2_CHECK(d.und.max_pages == d.backbone.max_pages && d.gen.max_pages == d.backbone.max_pages && d.backbone.max_pages >= 1 &&
             (size_t)W * d.backbone.max_pages * sizeof(int32_t) <= 48 * 1024, "ua2_stage3_set_beam: the three trunk page tables must have one width");
   UA2_CHECK(d.vt >= W, "ua2_stage3_set_beam: vocabulary smaller than the beam");
-  if (W != h->beam_W || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop();
-  h->beam_W = W; h->beam_eos = eos; h->beam = *st; h->beam_pools = pools; h->beam_n_pools = n_pools;
+  if (W != h->beam_W || G != h->beam_G || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop();
+  h->beam_W = W; h->beam_G = G; h->beam_eos = eos; h->beam = *st; h->beam_pools = pools; h->beam_n_pools = n_pools;
   return 0;
+}
+
+extern "C" int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools, int32_t n_pools) {
+  return ua2_stage3_set_beam_groups(h, W, 1, eos, st, pools, n_pools);
 }
 
 extern "C" int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale) {
@@ -866,8 +873,8 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   const bool beam = mode == 3;
   if (beam) {                                     // every argument of the beam launches is checked here, before the first launch
     UA2_CHECK(h->beam_W >= 1, "ua2_stage3_frame: mode 3 needs a beam (ua2_stage3_set_beam)");
-    UA2_CHECK(R == h->beam_W, "ua2_stage3_frame: a beam frame has one row per slot (W=%d), got R=%d", h->beam_W, R);
-    UA2_CHECK(2 * R <= h->d.max_batch, "ua2_stage3_frame: a beam of %d needs a plan of %d sequences", R, 2 * R);
+    UA2_CHECK(R == h->beam_G * h->beam_W, "ua2_stage3_frame: a beam frame has one row per slot (W=%d, groups=%d), got R=%d", h->beam_W, h->beam_G, R);
+    UA2_CHECK(2 * R <= h->d.max_batch, "ua2_stage3_frame: beams of %d rows need a plan of %d sequences", R, 2 * R);
     UA2_CHECK(!(h->cfg_scale > 1.f), "ua2_stage3_frame: beam search does not combine with classifier-free guidance");
     UA2_CHECK(h->ngram_n <= 1, "ua2_stage3_frame: beam search does not combine with the n-gram filter");
     UA2_CHECK(h->topk == 1, "ua2_stage3_frame: beam search needs top-k = 1 (it ranks the logits itself)");
@@ -878,9 +885,9 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
     if (mode < 0) return 0;
     if (beam) {
       const ua2_stage3_desc& d = h->d;
-      if (int rc = ua2_beam_step(h->text_logits, d.vt, d.vt, R, h->beam_eos, &h->beam, d.out_tokens, d.n_cb + 1, st)) return rc;
+      if (int rc = ua2_beam_step_groups(h->text_logits, d.vt, d.vt, h->beam_W, h->beam_G, h->beam_eos, &h->beam, d.out_tokens, d.n_cb + 1, st)) return rc;
       int32_t* const tables[3] = {const_cast<int32_t*>(d.und.page_table), const_cast<int32_t*>(d.backbone.page_table), const_cast<int32_t*>(d.gen.page_table)};
-      if (int rc = ua2_beam_reorder(R, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
+      if (int rc = ua2_beam_reorder_groups(h->beam_W, h->beam_G, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
       return feedback_impl(h, R, 1, reason_eos, reason_card, st, 0);   // out_tokens' text column holds the step's ids: the text feedback as it is
     }
     return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0, defer_frames);
@@ -890,7 +897,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   memcpy(&tbits, &h->temperature, sizeof(int));
   memcpy(&cbits, &h->cfg_scale, sizeof(int));
   // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram)
-  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;   // (mode 3: R is the beam width, and set_beam drops the graphs with the state)
+  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;   // (mode 3: R is groups x beam width, and set_beam drops the graphs with the state, W or G)
   const int dkey = defer ? (UA2_FRAME_DEFER_TEXT_HEAD | defer_frames << 8) : 0;   // (mode 0 only: the n-gram bits belong to mode 1)
   const auto key = std::make_tuple((int)R, (int)mode | (skip_text && !defer ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram | dkey,
                                    (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);

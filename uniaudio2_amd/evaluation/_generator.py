@@ -306,6 +306,25 @@ class GeneratorBase:
                                             skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
         return self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long))
 
+    @torch.inference_mode()
+    def _beam_search_text_batch(self, prompts, beam_width, length_penalty, max_length):
+        """generate_asr_beam_search over several prompts in one frame: Model_stage3.beam_search_batch.  prompts = [(tokens, mask)]."""
+        beam_width, G = int(beam_width), len(prompts)
+        if not 1 <= beam_width <= 8:
+            raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
+        if G < 1:
+            raise ValueError("beam search over an empty list of utterances")
+        if G * beam_width > 64:
+            raise ValueError(f"{G} utterances with beam_width={beam_width} are {G * beam_width} rows: a beam frame holds at most 64")
+        st = getattr(self._model, "_st", None)
+        if st is not None and st["B"] < 2 * G * beam_width:   # two page sets of G * W rows each
+            self._model.setup_caches(2 * G * beam_width)
+        self._set_sampling(1, 1.0)
+        out = self._model.beam_search_batch([(t, m.bool()) for t, m in prompts], beam_width=beam_width, length_penalty=length_penalty,
+                                            max_length=max_length, eos_id=TEXT_EOS, chunk_frames=self.chunk_frames,
+                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
+        return [self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long)) for ids, _, _ in out]
+
     def _text_loop(self, L, max_frames):
         text, frame, done = [], 0, False
         while not done and frame < max_frames:

@@ -47,6 +47,19 @@ class Generator(GeneratorBase):
         tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
         return self._beam_search_text(tokens, mask, beam_width, length_penalty, early_stopping, max_length)
 
+    @torch.inference_mode()
+    def generate_asr_beam_search_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, beam_width: int = 5,
+                                       length_penalty: float = 0.6, max_length: int = 500) -> list:
+        """generate_asr_beam_search for several utterances at once (an extension: the reference has no batched search).
+        reason_tokens / semantic_tokens: lists of (T, 8) tensors, one pair per utterance.  Each prompt is built with
+        prepare_asr_task; the utterances' beams are the row groups of one frame (Model_stage3.beam_search_batch), at most
+        64 // beam_width utterances; the plan is re-made for 2 * len(reason_tokens) * beam_width sequences when it is smaller.
+        Returns the decoded texts in the order given — each the text generate_asr_beam_search returns for that utterance alone."""
+        if len(reason_tokens) != len(semantic_tokens):
+            raise ValueError("one semantic tensor per reason tensor is needed")
+        prompts = [self.prepare_asr_task(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)]
+        return self._beam_search_text_batch(prompts, beam_width, length_penalty, max_length)
+
     # audio_music_caption_task.py uses the same prompt layout and loop under another name
     generate_audio_caption = generate_asr
 

@@ -443,12 +443,13 @@ class Model_stage3(nn.Module):
         self._need()
         st = self._st
         if mode == 3:
-            # a beam frame: one row per slot; every step writes one record of the step log and reads one more length-penalty entry
+            # a beam frame: one row per slot of every group; every step writes one record of each group's step log and reads one more
+            # length-penalty entry
             bm = self._beam
             if bm is None:
                 raise ValueError("mode 3 runs between begin_beams and end_beams")
-            if batch != bm["W"]:
-                raise ValueError(f"a beam frame has one row per slot: batch must be {bm['W']}, got {batch}")
+            if batch != bm["G"] * bm["W"]:
+                raise ValueError(f"a beam frame has one row per slot: batch must be {bm['G'] * bm['W']}, got {batch}")
             if bm["steps"] + n_frames > bm["cap"]:
                 raise ValueError(f"beam step log full: {bm['steps']} + {n_frames} steps > max_length {bm['cap']} (begin_beams)")
             bm["steps"] += n_frames
@@ -491,19 +492,24 @@ class Model_stage3(nn.Module):
 
     # ---- ragged batches / continuous batching (the reference has neither: SURVEY.md A.17, §8e) ------
     @torch.inference_mode()
-    def forward_prefix_ragged(self, tokens_list, mask_list):
+    def forward_prefix_ragged(self, tokens_list, mask_list, seq_ids=None):
         """Prefill of prompts of different lengths in one pass.  tokens_list[b] (L_b, 9), mask_list[b] (L_b, 9):
         the rows to cache for sequence b (callers pass prompt[:-1] as with forward_prefix); sequence b takes
-        page-table row b and positions 0..L_b-1.  Rows are issued time-major in chunks of `max_rows`, so a chunk
-        only ever needs K/V written by itself or by earlier chunks."""
+        page-table row seq_ids[b] (default b: rows 0..B-1; distinct, within the plan) and positions 0..L_b-1.  Rows are
+        issued time-major in chunks of `max_rows`, so a chunk only ever needs K/V written by itself or by earlier chunks."""
         self._need()
         st = self._st
         dev = st["device"]
         assert len(tokens_list) == len(mask_list) <= st["B"]
+        if seq_ids is None:
+            seq_ids = range(len(tokens_list))
+        seq_ids = [int(b) for b in seq_ids]
+        if len(seq_ids) != len(tokens_list) or len(set(seq_ids)) != len(seq_ids) or any(not 0 <= b < st["B"] for b in seq_ids):
+            raise ValueError(f"seq_ids must name {len(tokens_list)} distinct sequences of the plan (0..{st['B'] - 1}), got {seq_ids}")
         tk = torch.cat([t.reshape(-1, t.shape[-1]) for t in tokens_list]).to(dev)
         mk = torch.cat([m.reshape(-1, m.shape[-1]) for m in mask_list]).to(dev)
         ps = torch.cat([torch.arange(t.shape[0], device=dev) for t in tokens_list])
-        sq = torch.cat([torch.full((t.shape[0],), b, device=dev) for b, t in enumerate(tokens_list)])
+        sq = torch.cat([torch.full((t.shape[0],), b, device=dev) for b, t in zip(seq_ids, tokens_list)])
         order = torch.argsort(ps, stable=True)
         tk, mk, ps, sq = tk[order], mk[order], ps[order], sq[order]
         self._check_positions(int(ps.max().item()))
@@ -599,45 +605,41 @@ class Model_stage3(nn.Module):
             pt = g.kv_cache.page_table
             pt.copy_(torch.arange(pt.numel(), dtype=torch.int32, device=pt.device).view_as(pt))
 
-    @torch.inference_mode()
-    def begin_beams(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
-                    eos_id: int = 128001):
-        """Start of a beam search over one prompt: tokens (L, 9), tokens_mask (L, 9).  Prefills prompt[:-1] as sequence 0, loads the
-        prompt's last frame into the W = beam_width rows of the decode state, attaches the beam state to the executor and gives every
-        slot its view of the prompt's K/V (shared full pages, a copy of the partial one).  Slot 0 starts live with score 0, the others
-        dead.  Run steps with generate_frames(n, W, 3); end_beams() must follow (beam_search does so in a `finally`)."""
-        self._need()
+    def _beam_checks(self, W, G, max_length):
         st = self._st
-        W, max_length = int(beam_width), int(max_length)
         if not 1 <= W <= 8:
-            raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
-        if st["B"] < 2 * W:
-            raise ValueError(f"beam search with beam_width={W} needs setup_caches(max_batch_size={2 * W}) or larger (the pages of "
-                             f"sequences {W}..{2 * W - 1} are the second page set of the K/V fork); this plan holds {st['B']}")
+            raise ValueError(f"beam_width must be in 1..8, got {W}")
+        if G * W > 64:
+            raise ValueError(f"{G} prompts with beam_width={W} are {G * W} rows: a beam frame holds at most 64")
+        if st["B"] < 2 * G * W:
+            of = f"{G} prompts and " if G > 1 else ""
+            raise ValueError(f"beam search with {of}beam_width={W} needs setup_caches(max_batch_size={2 * G * W}) or larger (the pages of "
+                             f"sequences {G * W}..{2 * G * W - 1} are the second page set of the K/V fork); this plan holds {st['B']}")
         if max_length < 1:
             raise ValueError("max_length must be >= 1")
         if self._cfg > 1.0 or self._ngram is not None or (self._sampling is not None and self._sampling[0] != 1):
             raise ValueError("beam search runs without classifier-free guidance, without the n-gram filter and with topk = 1")
         if self._beam is not None:
             raise ValueError("a beam search is already running (end_beams)")
+
+    def _attach_beams(self, W, G, length_penalty, max_length, eos_id):
+        """The device state of G beams of W slots (include/ua2hip.h: group g at fixed strides from the base pointers), attached to
+        the executor, and the start of the fork for the rows the caller has loaded: every slot of a group gets slot 0's pages."""
+        st = self._st
         dev = st["device"]
-        tokens, tokens_mask = tokens.to(dev), tokens_mask.bool().to(dev)
-        L = tokens.shape[0]
-        self._check_positions(L - 1 + max_length - 1)
-        self.reset_caches()
-        self._static_page_tables()
-        pos = torch.arange(0, L, device=dev).unsqueeze(0)
-        self.forward_prefix(tokens[None, :-1], tokens_mask=tokens_mask[None], input_pos=pos[:, :-1])
-        self.begin_decode(tokens[-1:].unsqueeze(0).repeat(W, 1, 1), tokens_mask[-1:].unsqueeze(0).repeat(W, 1, 1),
-                          torch.tensor([L - 1], device=dev))
         # state: one int32 buffer carved into the fields of ua2_beam_state (score and cand_logp are fp32 views of their words)
-        words = torch.zeros(4 * 8 + 4 + 2 * 64 + max_length * W * 4, dtype=torch.int32, device=dev)
-        f = lambda a, n: words[a:a + n]
-        score, fin, ln, parent, ctrl = f(0, 8).view(torch.float32), f(8, 8), f(16, 8), f(24, 8), f(32, 4)
-        cand_logp, cand_id, log = f(36, 64).view(torch.float32), f(100, 64), f(164, max_length * W * 4)
-        score.fill_(float("-inf")); score[0] = 0.0
-        fin.fill_(2); fin[0] = 0
-        ctrl[1] = -1
+        n_log = max_length * W * 4
+        words = torch.zeros(G * (4 * 8 + 4 + 2 * 64 + n_log), dtype=torch.int32, device=dev)
+        at = [0]
+
+        def f(n):
+            at[0] += n
+            return words[at[0] - n:at[0]]
+        score, fin, ln, parent, ctrl = f(8 * G).view(torch.float32), f(8 * G), f(8 * G), f(8 * G), f(4 * G)
+        cand_logp, cand_id, log = f(64 * G).view(torch.float32), f(64 * G), f(G * n_log)
+        score.fill_(float("-inf")); score[::8] = 0.0
+        fin.fill_(2); fin[::8] = 0
+        ctrl[1::4] = -1
         lp_inv = torch.tensor([1.0 / (((5 + n) / 6) ** float(length_penalty)) for n in range(max_length + 1)], dtype=torch.float64)
         lp_inv = lp_inv.to(torch.float32).to(dev)
         bs = BeamState(score.data_ptr(), fin.data_ptr(), ln.data_ptr(), parent.data_ptr(), ctrl.data_ptr(), cand_logp.data_ptr(),
@@ -654,41 +656,126 @@ class Model_stage3(nn.Module):
         pools_dev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
         tabs = (vp * 3)(*[t.data_ptr() for t in tables])
         max_pages = self.backbone.kv_cache.max_pages
-        self._beam = dict(W=W, cap=max_length, steps=0, eos=int(eos_id), L=L, words=words, score=score, fin=fin, len=ln, ctrl=ctrl,
-                          log=log.view(max_length, W, 4), lp_inv=lp_inv, pools=pools_dev, state=bs)
-        check(lib.ua2_stage3_set_beam(self._h, W, int(eos_id), C.byref(bs), pools_dev.data_ptr(), len(pools)), "ua2_stage3_set_beam")
-        # the start of the fork: all parents 0, before the first frame (pos_add 0)
-        check(lib.ua2_beam_reorder(W, None, st["row_pos"].data_ptr(), 0, pools_dev.data_ptr(), len(pools), tabs, 3, st["B"], max_pages,
-                                   ops.stream()), "ua2_beam_reorder")
-
-    def beams_all_finished(self) -> int:
-        """The step at which all W slots were first finished, -1 while one is live (one 4-byte read: the only thing the host reads
-        between chunks)."""
-        return int(self._beam["ctrl"][1].item())
+        self._beam = dict(W=W, G=G, cap=max_length, steps=0, eos=int(eos_id), words=words, score=score.view(G, 8), fin=fin.view(G, 8),
+                          len=ln, ctrl=ctrl.view(G, 4), log=log.view(G, max_length, W, 4), lp_inv=lp_inv, pools=pools_dev, state=bs)
+        check(lib.ua2_stage3_set_beam_groups(self._h, W, G, int(eos_id), C.byref(bs), pools_dev.data_ptr(), len(pools)),
+              "ua2_stage3_set_beam_groups")
+        # the start of the fork: all parents slot 0 of their group, before the first frame (pos_add 0)
+        check(lib.ua2_beam_reorder_groups(W, G, None, st["row_pos"].data_ptr(), 0, pools_dev.data_ptr(), len(pools), tabs, 3, st["B"],
+                                          max_pages, ops.stream()), "ua2_beam_reorder_groups")
 
     @torch.inference_mode()
-    def end_beams(self):
-        """End of a beam search: reads the state and the step log, recovers every slot's text ids by walking the log backwards,
-        restores the static page tables and detaches the beam state — a later greedy call behaves as if no search had happened.
-        Slots still live count as finished with their score unchanged.  Returns (best ids, best score, hypotheses) with hypotheses =
-        [dict(ids, score, finished)] in slot order; the best is the highest score, the first such slot on ties."""
+    def begin_beams(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
+                    eos_id: int = 128001):
+        """Start of a beam search over one prompt: tokens (L, 9), tokens_mask (L, 9).  Prefills prompt[:-1] as sequence 0, loads the
+        prompt's last frame into the W = beam_width rows of the decode state, attaches the beam state to the executor and gives every
+        slot its view of the prompt's K/V (shared full pages, a copy of the partial one).  Slot 0 starts live with score 0, the others
+        dead.  Run steps with generate_frames(n, W, 3); end_beams() must follow (beam_search does so in a `finally`)."""
+        self._need()
+        st = self._st
+        W, max_length = int(beam_width), int(max_length)
+        self._beam_checks(W, 1, max_length)
+        dev = st["device"]
+        tokens, tokens_mask = tokens.to(dev), tokens_mask.bool().to(dev)
+        L = tokens.shape[0]
+        self._check_positions(L - 1 + max_length - 1)
+        self.reset_caches()
+        self._static_page_tables()
+        pos = torch.arange(0, L, device=dev).unsqueeze(0)
+        self.forward_prefix(tokens[None, :-1], tokens_mask=tokens_mask[None], input_pos=pos[:, :-1])
+        self.begin_decode(tokens[-1:].unsqueeze(0).repeat(W, 1, 1), tokens_mask[-1:].unsqueeze(0).repeat(W, 1, 1),
+                          torch.tensor([L - 1], device=dev))
+        self._attach_beams(W, 1, length_penalty, max_length, eos_id)
+
+    @torch.inference_mode()
+    def begin_beams_groups(self, prompts, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500, eos_id: int = 128001):
+        """Start of G = len(prompts) beam searches in one frame: prompts[g] = (tokens (L_g, 9), mask (L_g, 9)) of any lengths.  Group
+        g's slot j is row g * W + j.  Every prompt[:-1] is prefilled in one ragged pass, prompt g as sequence g * W (slot 0 of its
+        group then owns the prompt's pages); each prompt's last frame is loaded into its group's W rows at position L_g - 1; one
+        start fork gives every slot its view of its own prompt.  Run steps with generate_frames(n, G * W, 3); end_beams_groups()
+        must follow."""
+        self._need()
+        st = self._st
+        W, G, max_length = int(beam_width), len(prompts), int(max_length)
+        if G < 1:
+            raise ValueError("beam search over an empty list of prompts")
+        self._beam_checks(W, G, max_length)
+        dev = st["device"]
+        prompts = [(t.to(dev), m.bool().to(dev)) for t, m in prompts]
+        Ls = [int(t.shape[0]) for t, _ in prompts]
+        if min(Ls) < 1:
+            raise ValueError("an empty prompt")
+        self._check_positions(max(Ls) - 1 + max_length - 1)
+        self.reset_caches()
+        self._static_page_tables()
+        pre = [g for g in range(G) if Ls[g] > 1]
+        if pre:
+            self.forward_prefix_ragged([prompts[g][0][:-1] for g in pre], [prompts[g][1][:-1] for g in pre], seq_ids=[g * W for g in pre])
+        last_t = torch.stack([t[-1] for t, _ in prompts]).repeat_interleave(W, dim=0)
+        last_m = torch.stack([m[-1] for _, m in prompts]).repeat_interleave(W, dim=0)
+        pos = torch.tensor(Ls, device=dev).repeat_interleave(W) - 1
+        self.begin_decode(last_t.unsqueeze(1), last_m.unsqueeze(1), pos)
+        self._attach_beams(W, G, length_penalty, max_length, eos_id)
+
+    def beams_all_finished(self) -> int:
+        """The step at which every slot of every group had first finished (the last group's latch), -1 while one is live.  One copy of
+        the G ctrl records: the only thing the host reads between chunks."""
+        done = self._beam["ctrl"][:, 1].cpu().tolist()
+        return -1 if min(done) < 0 else max(done)
+
+    @torch.inference_mode()
+    def end_beams_groups(self):
+        """End of the searches: reads the state and every group's step log, recovers every slot's text ids by walking the log
+        backwards, restores the static page tables and detaches the beam state — a later greedy call behaves as if no search had
+        happened.  Slots still live count as finished with their score unchanged.  Returns one (best ids, best score, hypotheses) per
+        group with hypotheses = [dict(ids, score, finished)] in slot order; the best is the highest score, the first such slot on
+        ties.  beam_info_groups[g] = dict(steps, all_finished) of group g."""
         bm, self._beam = self._beam, None
         try:
             if bm is None:
                 raise ValueError("no beam search is running (begin_beams)")
             torch.cuda.synchronize()
+            W, G = bm["W"], bm["G"]
             ctrl = bm["ctrl"].cpu().tolist()
-            steps = min(ctrl[0], bm["cap"])
-            log = bm["log"][:steps].cpu().numpy()
-            score, fin = bm["score"][:bm["W"]].cpu().tolist(), bm["fin"][:bm["W"]].cpu().tolist()
+            steps = [min(c[0], bm["cap"]) for c in ctrl]
+            log = bm["log"][:, :max(steps)].cpu().numpy()
+            score, fin = bm["score"][:, :W].cpu().tolist(), bm["fin"][:, :W].cpu().tolist()
         finally:
             if self._h is not None:
                 check(lib.ua2_stage3_set_beam(self._h, 0, 0, None, None, 0), "ua2_stage3_set_beam")
                 self._static_page_tables()
-        self.beam_info = dict(steps=steps, all_finished=ctrl[1])       # steps run; the step at which all slots were first finished (-1: never)
-        hyps = [dict(ids=backtrack_beam_log(log, j), score=float(score[j]), finished=fin[j] == 1) for j in range(bm["W"])]
-        best = max(range(bm["W"]), key=lambda j: (hyps[j]["score"] if fin[j] != 2 else float("-inf"), -j))
-        return hyps[best]["ids"], hyps[best]["score"], hyps
+        # steps run; the step at which all slots of the group were first finished (-1: never)
+        self.beam_info_groups = [dict(steps=steps[g], all_finished=ctrl[g][1]) for g in range(G)]
+        self.beam_info = self.beam_info_groups[0]
+        out = []
+        for g in range(G):
+            hyps = [dict(ids=backtrack_beam_log(log[g][:steps[g]], j), score=float(score[g][j]), finished=fin[g][j] == 1) for j in range(W)]
+            best = max(range(W), key=lambda j: (hyps[j]["score"] if fin[g][j] != 2 else float("-inf"), -j))
+            out.append((hyps[best]["ids"], hyps[best]["score"], hyps))
+        return out
+
+    @torch.inference_mode()
+    def end_beams(self):
+        """End of a beam search over one prompt (begin_beams): end_beams_groups for its one group.  Returns (best ids, best score,
+        hypotheses); beam_info = dict(steps, all_finished)."""
+        return self.end_beams_groups()[0]
+
+    def _run_beams(self, rows, max_length, chunk_frames, use_graph, skip_audio_experts):
+        try:
+            done = 0
+            while done < max_length:
+                n = min(int(chunk_frames), max_length - done)
+                self.generate_frames(n, rows, 3, use_graph=use_graph, skip_audio_experts=skip_audio_experts)
+                done += n
+                if self.beams_all_finished() >= 0:
+                    break
+        except BaseException:
+            try:
+                self.end_beams_groups()
+            except Exception:
+                pass
+            raise
+        return self.end_beams_groups()
 
     @torch.inference_mode()
     def beam_search(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
@@ -700,21 +787,21 @@ class Model_stage3(nn.Module):
         chunk_frames, and stopping there is what early_stopping=False would compute as well (the reference keeps looping over
         finished beams without changing them).  Returns (best ids, best score, all W hypotheses)."""
         self.begin_beams(tokens, tokens_mask, beam_width, length_penalty, max_length, eos_id)
-        try:
-            done = 0
-            while done < max_length:
-                n = min(int(chunk_frames), max_length - done)
-                self.generate_frames(n, int(beam_width), 3, use_graph=use_graph, skip_audio_experts=skip_audio_experts)
-                done += n
-                if self.beams_all_finished() >= 0:
-                    break
-        except BaseException:
-            try:
-                self.end_beams()
-            except Exception:
-                pass
-            raise
-        return self.end_beams()
+        return self._run_beams(int(beam_width), int(max_length), chunk_frames, use_graph, skip_audio_experts)[0]
+
+    @torch.inference_mode()
+    def beam_search_batch(self, prompts, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500, eos_id: int = 128001,
+                          chunk_frames: int = 16, use_graph: bool = True, skip_audio_experts: bool = True):
+        """Beam search over several prompts at once: prompts[g] = (tokens (L_g, 9), mask (L_g, 9)); G * beam_width <= 64 rows, a plan
+        of 2 * G * beam_width sequences.  The G beams are the row groups of one frame, so G searches cost about one
+        search's frames.  Group g's result is what beam_search returns for prompts[g] alone — on the default (row-invariant) plan bit
+        for bit: a group that has finished keeps being stepped as a fixed point beside the live ones, and the loop stops when every
+        group has latched or after max_length steps.  Returns [(best ids, best score, hypotheses)] in the order of prompts."""
+        prompts = list(prompts)
+        if not prompts:
+            raise ValueError("beam_search_batch needs at least one prompt")
+        self.begin_beams_groups(prompts, beam_width, length_penalty, max_length, eos_id)
+        return self._run_beams(len(prompts) * int(beam_width), int(max_length), chunk_frames, use_graph, skip_audio_experts)
 
     def buffer(self, name: str, rows: int):
         """Intermediate buffers for tests: 'h_final' (rows, C), 'text_logits' (rows, Vt), 'audio_logits' (rows, 8, Va)."""

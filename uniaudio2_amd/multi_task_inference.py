@@ -23,6 +23,11 @@ Differences, all explicit:
     device, the N hypotheses as the rows of one frame.  --decode_type beamsearch itself still raises NotImplementedError: the
     reference's function behind that flag cannot run (it calls a method its model lacks), and the message points to --beam_width.
     --beam_width with --decode_type ngram, with lyric_recognition or with a caption / understanding / s2t task raises ValueError.
+    `--batch_size N` together with --beam_width W decodes the utterances of --token_dir / --audio_dir in chunks of N, the N beams as
+    row groups of one frame (Generator.generate_asr_beam_search_batch): the same results file as --batch_size 1 on the default plan,
+    in the order of the names, missing files skipped as before.  N * W is at most 64 (ValueError otherwise); the plan holds 2 * N * W
+    sequences — 128 sequences at 2048 positions are about 35 GB of K/V at the released sizes (135 kB per position).  Without
+    --beam_width the understanding tasks ignore --batch_size, as before.
     Any non-greedy --decode_type for the generation tasks raises NotImplementedError.  No trained checkpoint ships with this
     repository: the search is verified on toy and random weights, not for task quality.
   * Encoding raw audio (--audio / --audio_dir; the understanding tasks and the speech_s2s source) runs the codec's three frozen
@@ -193,6 +198,10 @@ def _check_understanding_decode(args, task):
         if task not in ("asr", "yue_asr"):
             raise ValueError(f"--beam_width is not available for {task}: the reference defines beam search for the ASR Generator "
                              "only (evaluation/asr_task.py); the caption / understanding / s2t generators have no such method")
+        bs = int(getattr(args, "batch_size", 1) or 1)
+        if bs * bw > 64:
+            raise ValueError(f"--batch_size {bs} x --beam_width {bw} = {bs * bw} rows: a beam frame holds at most 64 "
+                             "(lower --batch_size or --beam_width)")
     if args.decode_type == "ngram" and task == "lyric_recognition":
         raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "
                          "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")
@@ -235,6 +244,44 @@ def _encode_audio_to_tokens(args, generator, out_dir, alternative):
     return out_dir, names
 
 
+def _load_token_pair(token_dir, name):
+    """(reason, semantic) as (T, 8) long tensors (:304-308), or None (and the [Skip] line) when either file is missing."""
+    rp, sp = os.path.join(token_dir, f"{name}_reason.pt"), os.path.join(token_dir, f"{name}_semantic.pt")
+    if not os.path.isfile(rp) or not os.path.isfile(sp):
+        print(f"[Skip] {name}: missing reason/semantic .pt")
+        return None
+    return torch.load(rp, map_location="cpu").transpose(0, 1).long(), torch.load(sp, map_location="cpu").transpose(0, 1).long()
+
+
+def _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names, f_out):
+    """--beam_width with --batch_size N > 1: the names in their order, in chunks of N that exist (a missing file is skipped and does not
+    count), each chunk one generate_asr_beam_search_batch call; one results line per utterance, in the order of names."""
+    n = int(args.batch_size)
+    chunk = []
+
+    def flush():
+        if not chunk:
+            return
+        texts = generator.generate_asr_beam_search_batch(task_prompt, task_name=task, reason_tokens=[r for _, r, _ in chunk],
+                                                         semantic_tokens=[s for _, _, s in chunk], beam_width=args.beam_width,
+                                                         length_penalty=args.length_penalty)
+        if len(texts) != len(chunk):
+            raise RuntimeError(f"beam search returned {len(texts)} texts for {len(chunk)} utterances")
+        for (name, _, _), text_out in zip(chunk, texts):
+            f_out.write(f"{name}\t{text_out}\n")
+            print(f"[{task}] {name} -> {text_out[:80]}...")
+        del chunk[:]
+
+    for name in names:
+        pair = _load_token_pair(token_dir, name)
+        if pair is None:
+            continue
+        chunk.append((name, pair[0], pair[1]))
+        if len(chunk) == n:
+            flush()
+    flush()
+
+
 def run_understanding(args):
     task = args.task.strip().lower()
     _check_understanding_decode(args, task)
@@ -255,19 +302,21 @@ def run_understanding(args):
                                            is_cfg=args.use_cfg)
     if raw_audio:
         token_dir, names = _encode_audio_to_tokens(args, generator, args.output_dir, "pass --reason_pt + --semantic_pt or --token_dir")
-    if int(getattr(args, "beam_width", 0) or 0) >= 1:            # the K/V fork of a beam of N keeps two page sets: a plan of 2 N sequences
-        model.setup_caches(2 * int(args.beam_width))
+    beam_batch = int(getattr(args, "batch_size", 1) or 1) if int(getattr(args, "beam_width", 0) or 0) >= 1 else 1
+    if int(getattr(args, "beam_width", 0) or 0) >= 1:            # the K/V fork of a beam of W keeps two page sets: a plan of 2 W sequences
+        model.setup_caches(2 * int(args.beam_width) * max(1, min(beam_batch, len(names))))    # ... per utterance of a chunk
     task_prompt = _get_prompt_tensor(args, generator._text_tokenizer, args.task)
     results_path = args.results or os.path.join(args.output_dir, f"{task}_results.txt")
     os.makedirs(os.path.dirname(results_path) or ".", exist_ok=True)
     with open(results_path, "w") as f_out:
+        if beam_batch > 1:                                       # asr, yue_asr under --beam_width (checked above)
+            _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names, f_out)
+            names = []
         for name in names:
-            rp, sp = os.path.join(token_dir, f"{name}_reason.pt"), os.path.join(token_dir, f"{name}_semantic.pt")
-            if not os.path.isfile(rp) or not os.path.isfile(sp):
-                print(f"[Skip] {name}: missing reason/semantic .pt")
+            pair = _load_token_pair(token_dir, name)
+            if pair is None:
                 continue
-            reason = torch.load(rp, map_location="cpu").transpose(0, 1).long()          # (T, 8), :304-308
-            semantic = torch.load(sp, map_location="cpu").transpose(0, 1).long()
+            reason, semantic = pair                              # (T, 8)
             if task == "audio_understanding":
                 question = (args.question or "").strip()
                 if not question and args.question_file and os.path.isfile(args.question_file):      # :345-347
@@ -541,11 +590,14 @@ def get_parser():
     p.add_argument("--beam_width", type=int, default=0,
                    help="ASR / Yue_ASR with --decode_type greedy (extension): N in 1..8 decodes with beam search over N hypotheses on the "
                         "device (the reference's generate_asr_beam_search rule, which its own --decode_type beamsearch cannot run).  "
-                        "Default 0 = off")
+                        "With --batch_size N the utterances are decoded N at a time, their beams side by side in one frame: N * W <= 64, "
+                        "same results.  Default 0 = off")
     p.add_argument("--length_penalty", type=float, default=0.6,
                    help="--beam_width: exponent of the length normalisation ((5 + length) / 6) ** length_penalty (the reference's default 0.6)")
     p.add_argument("--batch_size", type=int, default=1,
-                   help="utterances decoded together per GPU (extension; TTS / Yue_TTS with --text_file; 1 = one by one as the reference)")
+                   help="utterances decoded together per GPU (extension; 1 = one by one as the reference).  TTS / Yue_TTS with --text_file: "
+                        "continuous batching.  ASR / Yue_ASR with --beam_width W: chunks of N utterances per beam-search frame, N * W <= 64; "
+                        "the K/V plan then holds 2 * N * W sequences (128 sequences at 2048 positions: about 35 GB at the released sizes)")
     return p
 
 
