@@ -150,6 +150,31 @@ typedef struct ua2_kv_geom {
                          the attention window plus the positions written per launch; ua2_attn needs window > 0 with it. */
 } ua2_kv_geom;
 
+/* [v10, addition] Greedy sampling tail of the depth decoder folded into the launch that consumes it (B = 1 frames of the executor,
+ * ua2_linear_args.fold).  Step i of the depth decoder ends in audio_head's per-16-column arg-max partials; with the plan's per-id tables
+ * everything step i + 1 reads of the sampled id is a table row (projected embedding y, layer 0's q | k | v at position i + 1).  Instead of a
+ * one-block launch that reduces the partials and copies those rows into buffers only the next launch reads, layer 0's O-projection
+ * (UA2_PRO_LOCAL_ATTN, UA2_EPI_RESIDUAL, M == 1) reduces them itself, after an ordinary kernel boundary — no flags, counters or fences:
+ *   id  = arg-max over (part_max, part_idx)[0 .. n_part) under "larger value, then lower index" (the all-NaN fallback and the clamp into
+ *         [0, limit) of the stand-alone tails included), every workgroup for itself;   row = id + row_off;
+ *   q   = tab_q[row], K / V of position `pos` = tab_k / tab_v[row], positions < pos from the sequence's cache page as always;
+ *   y   = tab_y[row] + attention (.) W^T   (the residual comes from the table; `x` and `resid` are not read);
+ *   workgroup 0 also stores id to *out_token and the K / V row into the cache page at position `pos` (later launches read them there).
+ * part_max == NULL: off.  Same bits as the arg-max launch followed by the plain launch. */
+typedef struct ua2_argmax_fold {
+  const float* part_max;    /* [n_part] */
+  const int32_t* part_idx;  /* [n_part] */
+  int32_t n_part, limit;
+  int32_t* out_token;
+  int64_t row_off;
+  int32_t pos;              /* 1 .. 7: position of this step's row (== row_pos[0]) */
+  int32_t reserved;
+  const float* tab_y;       /* [rows, N] fp32 */
+  const float* tab_q;       /* [rows, K] fp32 */
+  const void* tab_k;        /* [rows, n_kv * head_size] of the launch dtype */
+  const void* tab_v;
+} ua2_argmax_fold;
+
 typedef struct ua2_linear_args {
   int32_t dtype, prologue, epilogue;
   int32_t M, N, K;        /* rows, out features, in features */
@@ -246,6 +271,7 @@ typedef struct ua2_linear_args {
      (profiles/r6_range_split.txt: 15.3 + 5.9 us against 20.4), so the frame executor leaves it NULL unless UA2_RANGE_SPLIT=1. */
   float* range_ws;
   size_t range_ws_bytes;
+  ua2_argmax_fold fold;   /* [v10, addition] UA2_PRO_LOCAL_ATTN only; fold.part_max == NULL: off */
 } ua2_linear_args;
 
 int ua2_linear(const ua2_linear_args* a, void* stream);
@@ -281,7 +307,7 @@ int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
  * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
- * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches); -1 for an unknown
+ * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
  * call getenv on every launch); a process that changes one of them afterwards (the tests do) calls this to have them read again. */

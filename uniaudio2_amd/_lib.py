@@ -34,6 +34,12 @@ class KvGeom(C.Structure):
                 ("n_head", i32), ("head_size", i32), ("ring_pages", i32)]
 
 
+class ArgmaxFold(C.Structure):
+    """ua2_argmax_fold: the previous step's greedy tail, folded into a PRO_LOCAL_ATTN launch (include/ua2hip.h)."""
+    _fields_ = [("part_max", vp), ("part_idx", vp), ("n_part", i32), ("limit", i32), ("out_token", vp), ("row_off", i64),
+                ("pos", i32), ("reserved", i32), ("tab_y", vp), ("tab_q", vp), ("tab_k", vp), ("tab_v", vp)]
+
+
 class LinearArgs(C.Structure):
     _fields_ = [("dtype", i32), ("prologue", i32), ("epilogue", i32), ("M", i32), ("N", i32), ("K", i32),
                 ("x", vp), ("ldx", i32), ("norm_w", vp), ("eps", f32),
@@ -46,7 +52,7 @@ class LinearArgs(C.Structure):
                 ("y_norm_w", vp), ("y_h", vp), ("ldh", i32), ("y_ssq", vp), ("x_h", vp), ("x_ssq", vp),
                 ("split_ws", vp), ("split_ws_bytes", C.c_size_t), ("sum_order", i32),
                 ("y_ln_w", vp), ("y_ln_b", vp), ("y_ln_eps", f32),
-                ("range_ws", vp), ("range_ws_bytes", C.c_size_t)]
+                ("range_ws", vp), ("range_ws_bytes", C.c_size_t), ("fold", ArgmaxFold)]
 
 
 class AttnArgs(C.Structure):

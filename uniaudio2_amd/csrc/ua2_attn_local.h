@@ -55,6 +55,56 @@ struct LocalAttn {
       }
     }
   }
+  // The same loads where the row of position `pos` is not in the cache yet but a row of the per-id tables (ua2_argmax_fold), in two
+  // halves: the positions below `pos` do not depend on the id and go out first (slots from `pos` up re-read position 0: never used) ...
+  __device__ __forceinline__ void issue_older(const ua2_kv_geom& kv, int page, int h, int d, int pos) {
+    const int G = kv.n_head / kv.n_kv;
+    const size_t base = (((size_t)page * kv.n_kv + h / G) * UA2_PAGE) * HS + d;
+#pragma unroll
+    for (int j = 0; j < kLocalCtx; ++j) {
+      const size_t off = base + (size_t)(j < pos ? j : 0) * HS;
+      if constexpr (DT == UA2_BF16) {
+        const unsigned kr = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(kv.k_pool) + off);
+        const unsigned vr = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(kv.v_pool) + off);
+        k[j] = make_float2(__uint_as_float(kr << 16), __uint_as_float(kr & 0xffff0000u));
+        v[j] = make_float2(__uint_as_float(vr << 16), __uint_as_float(vr & 0xffff0000u));
+      } else {
+        k[j] = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(kv.k_pool) + off);
+        v[j] = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(kv.v_pool) + off);
+      }
+    }
+  }
+  // ... then q and the K / V row of position `pos` from the table rows (q_row [n_head * HS] fp32, k_row / v_row [n_kv * HS] of DT).
+  // publish: the first query head of each kv group also stores the two elements it loaded into the cache page at position `pos`
+  __device__ __forceinline__ void issue_row(const ua2_kv_geom& kv, const float* __restrict__ q_row, const void* k_row, const void* v_row,
+                                            int h, int d, int pos, bool publish, int page) {
+    const int G = kv.n_head / kv.n_kv;
+    q = *reinterpret_cast<const float2*>(q_row + (size_t)h * HS + d);
+    const size_t off = (size_t)(h / G) * HS + d;
+    const size_t dst = (((size_t)page * kv.n_kv + h / G) * UA2_PAGE + pos) * HS + d;
+    const bool put = publish && h % G == 0;
+    float2 tk, tv;
+    if constexpr (DT == UA2_BF16) {
+      const unsigned kr = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(k_row) + off);
+      const unsigned vr = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(v_row) + off);
+      tk = make_float2(__uint_as_float(kr << 16), __uint_as_float(kr & 0xffff0000u));
+      tv = make_float2(__uint_as_float(vr << 16), __uint_as_float(vr & 0xffff0000u));
+      if (put) {
+        *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(kv.k_pool) + dst) = kr;
+        *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(kv.v_pool) + dst) = vr;
+      }
+    } else {
+      tk = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(k_row) + off);
+      tv = *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(v_row) + off);
+      if (put) {
+        *reinterpret_cast<float2*>(reinterpret_cast<float*>(kv.k_pool) + dst) = tk;
+        *reinterpret_cast<float2*>(reinterpret_cast<float*>(kv.v_pool) + dst) = tv;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kLocalCtx; ++j)
+      if (j == pos) { k[j] = tk; v[j] = tv; }
+  }
   // softmax(q k^T / sqrt(HS)) v over positions 0..pos; returns this lane's two output dims
   __device__ __forceinline__ float2 finish(int pos) const {
     const float scale = 1.0f / sqrtf((float)HS);

@@ -193,7 +193,7 @@ inline void ua2_allow_big_lds() {
 }
 
 // ---- test hooks (ua2hip.h ABI v9): launch counters per kernel family, and UA2_* environment variables read once -------------
-enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_SKINNY2_W8 = 7, UA2_CNT_N = 8 };
+enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_SKINNY2_W8 = 7, UA2_CNT_ARGMAX = 8, UA2_CNT_N = 9 };
 extern std::atomic<int64_t> g_ua2_launches[UA2_CNT_N];
 extern std::atomic<int> g_ua2_env_gen;              // bumped by ua2_debug_refresh_env
 inline void ua2_count_launch(int family) { g_ua2_launches[family].fetch_add(1, std::memory_order_relaxed); }
@@ -229,6 +229,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 =
 int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_attn_local_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_gemv_rows_per_tile(int dtype, int K);   // rows one decode-kernel workgroup holds in LDS (ua2_gemv.hip)
+int ua2_gemv_fold_ok(int dtype, int N, int K);   // does the decode kernel's geometry for an (N, K) O-projection have a ua2_argmax_fold form?
 int ua2_gemv_rows_preferred(int dtype, int K);  // rows up to which the launchers prefer the decode kernel (<= rows_per_tile; a cost choice)
 extern "C" int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
                                const int32_t* forbid, uint64_t seed, const int32_t* counter, int32_t stream_id,

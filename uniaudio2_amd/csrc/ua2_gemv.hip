@@ -49,6 +49,76 @@ __device__ __forceinline__ void local_attn_prologue(const ua2_linear_args& a, ch
   if (!streamed) burst();
 }
 
+// The same prologue with the previous step's greedy tail folded in (ua2_argmax_fold, include/ua2hip.h): the workgroup reduces the
+// arg-max partials itself — the 16 waves share them, one barrier, the candidates, order and tie / all-NaN rules of ua2_row_token — and
+// takes q and the K / V row of this step's position from the per-id tables; older positions come from the cache page and do not depend
+// on the id, so they are requested first.  on_id(row) runs once the table row is known, in front of the weight burst (the epilogue's
+// residual is a table row too).  Workgroup 0 (`writer`) publishes what later launches read: the id, and the K / V row of the cache page
+// (stored by the lanes that load it for the attention: every kv head is some query head's).
+// `red`: 3 * kMaxWaves words of LDS nobody else uses before the MFMA phase.
+template <int DT, int HS, typename Burst, typename OnId>
+__device__ __forceinline__ void local_attn_fold_prologue(const ua2_linear_args& a, char* a_lds, float* red, int wave, int nw, int lane, bool writer,
+                                                         Burst&& burst, OnId&& on_id) {
+  using LA = LocalAttn<DT, HS>;
+  constexpr int BYTES = Elem<DT>::BYTES;
+  const ua2_argmax_fold& f = a.fold;
+  const int pos = f.pos, tid = wave * 64 + lane;
+  float bv = -INFINITY;
+  int bi = UA2_TOK_NONE, lo = UA2_TOK_NONE;
+  for (int p = tid; p < f.n_part; p += nw * 64) {
+    const float v = f.part_max[p];
+    const int i = f.part_idx[p];
+    if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    lo = min(lo, i);
+  }
+  const int page = a.kv.page_table[(size_t)kv_table_row(a, 0) * a.kv.max_pages];
+  LA la;
+  const int hl = lane / LA::LPH, d = (lane % LA::LPH) * 2;
+  const bool mine = wave * LA::HPW < a.kv.n_head;             // wave-uniform: this wave has a first pass
+  if (mine) la.issue_older(a.kv, page, wave * LA::HPW + hl, d, pos);
+  bool streamed = false;
+#ifdef UA2_FOLD_BURST_FIRST   // measurement build (profiles/b1_latency_chain.md): the weights go out before the id is known and the id-dependent
+  burst();                    // loads land behind them: 9.80 us per launch against 9.01 us in the default order (burst once the id is known)
+  streamed = true;
+#endif
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(bv, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    lo = min(lo, __shfl_xor(lo, o));
+  }
+  int* redi = reinterpret_cast<int*>(red);
+  if (lane == 0) { red[wave] = bv; redi[kMaxWaves + wave] = bi; redi[2 * kMaxWaves + wave] = lo; }
+  __syncthreads();
+  bv = red[0]; bi = redi[kMaxWaves]; lo = redi[2 * kMaxWaves];
+  for (int w = 1; w < nw; ++w) {
+    const float ov = red[w];
+    const int oi = redi[kMaxWaves + w];
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    lo = min(lo, redi[2 * kMaxWaves + w]);
+  }
+  const int tok = min(max(bi == UA2_TOK_NONE ? lo : bi, 0), f.limit - 1);   // nobody won (all NaN): the lowest candidate id
+  const size_t row = (size_t)((long long)tok + f.row_off);
+  const size_t kvw = (size_t)a.kv.n_kv * HS;                   // elements of a K (V) table row
+  const float* q_row = f.tab_q + row * a.K;
+  const char* k_row = reinterpret_cast<const char*>(f.tab_k) + row * kvw * BYTES;
+  const char* v_row = reinterpret_cast<const char*>(f.tab_v) + row * kvw * BYTES;
+  on_id(row);
+  for (int h0 = wave * LA::HPW; h0 < a.kv.n_head; h0 += nw * LA::HPW) {
+    const int h = h0 + hl;
+    if (h0 != wave * LA::HPW) la.issue_older(a.kv, page, h, d, pos);
+    la.issue_row(a.kv, q_row, k_row, v_row, h, d, pos, writer, page);     // the writer's lanes also put the K / V row into the cache page
+    if (!streamed) { burst(); streamed = true; }
+    const float2 o = la.finish(pos);
+    char* dst = a_lds + ((size_t)h * HS + d) * BYTES;
+    if constexpr (DT == UA2_BF16) *reinterpret_cast<unsigned*>(dst) = (unsigned)f2bf(o.x) | ((unsigned)f2bf(o.y) << 16);
+    else *reinterpret_cast<float2*>(dst) = o;
+  }
+  if (!streamed) burst();
+  if (writer && tid == 0) *f.out_token = tok;
+}
+
 // fp8 weights (W8 != 0; include/ua2hip.h ua2_pack_linear_w8).  One 16-byte lane load of the fp8 image carries the lane's B fragments of
 // TWO chunks (2j: bytes 0-7, 2j + 1: bytes 8-15), so a wave streams half the bytes of the bf16 launch in half as many 1 KiB bursts.
 // Eight OCP e4m3fn codes -> the bf16 B fragment of one chunk, exactly (an e4m3 value has 4 significant bits and sits inside the bf16
@@ -70,7 +140,9 @@ __device__ __forceinline__ int burst_index(int cb, int u, int last) {
 // chunks (every shape of the released model): CPW / 2 loads per round; 2 = fp8 image, any range of up to CPW chunks (odd starts,
 // single-chunk ranges: small K): one load per chunk, the half picked by the chunk's parity.  The geometry, the chunk order inside a
 // wave's chain and the order of the cross-wave sum are those of W8 = 0, whatever the form.
-template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0>
+// FOLD (UA2_PRO_LOCAL_ATTN, W8 = 0): the launch carries a ua2_argmax_fold; an instantiation of its own, so that the plain launches keep
+// their registers (the CPW = 16 forms sit at the 128-register limit of a 16-wave workgroup).
+template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0, bool FOLD = false>
 __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, const int a_stride, const int red_off, const int rt,
                                           const int bx, const int by, const Ua2W8* w8 = nullptr) {
   constexpr int KC = Elem<DT>::KC, EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
@@ -140,7 +212,9 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     }
   }
   EpiPre pre;
-  if (tid < 256) epilogue_prefetch_a<DT, EPI>(a, tile[0], tid >> 4, tid & 15, pre, m0);
+  static_assert(!FOLD || (PRO == UA2_PRO_LOCAL_ATTN && EPI == UA2_EPI_RESIDUAL && W8 == 0), "ua2_argmax_fold: the O-projection of the local attention");
+  // (FOLD: the residual is a table row, known once the prologue has the id)
+  if (tid < 256 && !FOLD) epilogue_prefetch_a<DT, EPI>(a, tile[0], tid >> 4, tid & 15, pre, m0);
   float ssqv[16];                                        // UA2_PRO_SCALED: the row's sum-of-squares partials, requested before the burst
   if constexpr (PRO == UA2_PRO_SCALED) {
     if (tid < 256) scaled_ssq_request(a, m0 + min(tid >> 4, rows - 1), tid & 15, ssqv);
@@ -163,6 +237,18 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(c0, u, last) * 64);
   };
   if constexpr (PRO == UA2_PRO_LOCAL_ATTN) {
+    if constexpr (FOLD) {
+      auto on_id = [&](size_t row) {
+        const int n = tile[0] * 16 + (tid & 15);
+        if (tid < 16 && n < a.N) pre.resid = a.fold.tab_y[row * a.N + n];       // epilogue row 0 (M == 1)
+      };
+      const bool writer = bx == 0 && by == 0;
+      switch (a.kv.head_size) {
+        case 32: local_attn_fold_prologue<DT, 32>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+        case 64: local_attn_fold_prologue<DT, 64>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+        default: local_attn_fold_prologue<DT, 128>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+      }
+    } else
     switch (a.kv.head_size) {
       case 32: local_attn_prologue<DT, 32>(a, a_lds, m0, wave, nw, lane, burst); break;
       case 64: local_attn_prologue<DT, 64>(a, a_lds, m0, wave, nw, lane, burst); break;
@@ -386,11 +472,11 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   linear_epilogue<DT, EPI, NT>(a, v, tile, row, col, pre, m0, rows);
 }
 
-template <int DT, int PRO, int EPI, int CPW, bool MR>
+template <int DT, int PRO, int EPI, int CPW, bool MR, bool FOLD = false>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_kernel(const ua2_linear_args a, const int a_stride,
                                                               const int red_off, const int rt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<DT, PRO, EPI, CPW, MR>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y);
+  gemv_body<DT, PRO, EPI, CPW, MR, 0, FOLD>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y);
 }
 
 // the same launch on the fp8 image of its weight(s): bf16 activations in LDS, bf16 MFMA, half the weight bytes
@@ -544,9 +630,9 @@ Geometry pick_geometry(int nchunks, int blocks, int nt) {
   return Geometry{w, c};
 }
 
-template <int DT, int PRO, int EPI, int CPW, bool MR>
+template <int DT, int PRO, int EPI, int CPW, bool MR, bool FOLD = false>
 void launch_one(const ua2_linear_args& a, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
-  constexpr auto kern = gemv_kernel<DT, PRO, EPI, CPW, MR>;
+  constexpr auto kern = gemv_kernel<DT, PRO, EPI, CPW, MR, FOLD>;
   ua2_allow_big_lds<kern>();
   hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt);
   ua2_count_launch(UA2_CNT_GEMV);
@@ -612,6 +698,20 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullpt
   } else {
     if (w8) return 1;
   }
+  if constexpr (PRO == UA2_PRO_LOCAL_ATTN && EPI == UA2_EPI_RESIDUAL) {
+    if (a.fold.part_max) {     // ua2_argmax_fold: the geometries of attention-wide K (rounds of 4 or 8 chunks); fp8 twins are refused above
+      if (a.M != 1 || geo.cpw > 8) return 1;
+      if (mr) {
+        if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, true, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one<DT, PRO, EPI, 8, true, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else {
+        if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, false, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one<DT, PRO, EPI, 8, false, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      }
+      UA2_LAUNCH_CHECK();
+      return 0;
+    }
+  }
   if (mr) {
     if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
     else launch_one<DT, PRO, EPI, 8, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
@@ -641,7 +741,7 @@ bool w8_pair(int pro, int epi) {
 template <int DT>
 int launch_dt(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr) {
   if (w8) {       // fp8 weights: only the pairs above (each instantiation below is compiled for exactly those)
-    if (DT != UA2_BF16 || !w8_pair(a.prologue, a.epilogue)) return 1;
+    if (DT != UA2_BF16 || !w8_pair(a.prologue, a.epilogue) || a.fold.part_max) return 1;
     if (a.prologue == UA2_PRO_NORM) {
       if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s, w8);
       if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s, w8);
@@ -736,6 +836,11 @@ int ua2_gemv_launch_with_rider(const ua2_linear_args& a, const ua2_linear_args& 
   ua2_count_launch(UA2_CNT_GEMV);
   UA2_LAUNCH_CHECK();
   return 0;
+}
+
+int ua2_gemv_fold_ok(int dtype, int N, int K) {
+  const int kc = dtype == UA2_BF16 ? 32 : 16;
+  return pick_geometry(ua2_ceil_div(K, kc), ua2_ceil_div(N, 16), 1).cpw <= 8 ? 1 : 0;
 }
 
 ua2_gemv_geometry ua2_pick_gemv_geometry(int dtype, int N, int K, int nt) {

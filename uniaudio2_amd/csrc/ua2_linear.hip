@@ -140,8 +140,15 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
                   a.kv.n_head % (128 / a.kv.head_size) == 0 && a.K == a.kv.n_head * a.kv.head_size && a.K % kc == 0,
               "ua2_linear: bad LOCAL_ATTN arguments");
     UA2_CHECK(a.resid != nullptr && a.y != nullptr, "ua2_linear: RESIDUAL needs resid, y");
+    if (a.fold.part_max) {   // ua2_argmax_fold
+      const ua2_argmax_fold& f = a.fold;
+      UA2_CHECK(f.part_idx && f.n_part > 0 && f.limit > 0 && f.out_token && f.tab_y && f.tab_q && f.tab_k && f.tab_v && f.row_off >= 0,
+                "ua2_linear: argmax fold: missing partials / tables / out_token");
+      UA2_CHECK(f.pos >= 1 && f.pos < 8 && !a.out_scale && a.kv.ring_pages == 0 && !w8,
+                "ua2_linear: argmax fold needs 1 <= pos < 8, a linear cache, no out_scale and no fp8 twin");
+    }
     const int rc = ua2_gemv_try_launch(a, s, w8);
-    UA2_CHECK(rc <= 0, "ua2_linear: LOCAL_ATTN problem outside the decode kernel's range");
+    UA2_CHECK(rc <= 0, "ua2_linear: LOCAL_ATTN problem outside the decode kernel's range%s", a.fold.part_max ? " (argmax fold: rounds of 4 or 8 chunks per wave)" : "");
     return rc;
   }
   if (a.y_norm_w) {   // producer half of the scaled-norm hand-over

@@ -22,7 +22,7 @@ extern "C" int ua2_version(void) { return UA2_VERSION; }
 std::atomic<int64_t> g_ua2_launches[UA2_CNT_N];
 std::atomic<int> g_ua2_env_gen{0};
 extern "C" int64_t ua2_debug_kernel_launches(const char* family) {
-  static const char* const names[UA2_CNT_N] = {"gemm2", "gemm", "skinny2", "gemv", "rsplit", "gemv_w8", "text_flush", "skinny2_w8"};
+  static const char* const names[UA2_CNT_N] = {"gemm2", "gemm", "skinny2", "gemv", "rsplit", "gemv_w8", "text_flush", "skinny2_w8", "argmax"};
   if (!family) return -1;
   for (int i = 0; i < UA2_CNT_N; ++i)
     if (!strcmp(family, names[i])) return g_ua2_launches[i].load(std::memory_order_relaxed);
@@ -392,6 +392,7 @@ int ua2_argmax_embed_launch(int dtype, int32_t M, int32_t n_part, int32_t limit,
                             int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, hipStream_t s) {
   UA2_CHECK(M > 0 && n_part > 0 && limit > 0 && part_max && part_idx && out_tokens, "ua2_argmax_embed: bad arguments");
   UA2_CHECK(!emb || next_h, "ua2_argmax_embed: next_h is NULL");
+  ua2_count_launch(UA2_CNT_ARGMAX);
   if (dtype == UA2_BF16)
     hipLaunchKernelGGL((argmax_embed_kernel<UA2_BF16>), dim3(M), dim3(256), 0, s, n_part, limit, part_max, part_idx, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
   else if (dtype == UA2_F32)
@@ -446,6 +447,7 @@ int ua2_argmax_gather(int32_t M, int32_t n_part, int32_t limit, const float* par
     UA2_CHECK(tab_h && tab_ssq && ho->ssq && (ho->h || ho->packed) && (!ho->h || ho->ldh % 4 == 0), "ua2_argmax_gather: hand-over tables / outputs missing");
     h = *ho;
   }
+  ua2_count_launch(UA2_CNT_ARGMAX);
   hipLaunchKernelGGL(argmax_gather_kernel, dim3(M), dim3(256), 0, s, n_part, limit, part_max, part_idx, out_tokens, out_ld, out_col, tab_y,
                      reinterpret_cast<const unsigned short*>(tab_h), tab_ssq, (long long)row_off, Cd, next_x, h, q);
   UA2_LAUNCH_CHECK();

@@ -59,6 +59,12 @@ struct ua2_stage3 {
   float* split_ws = nullptr;   // K-slab scratch of the order-free GEMM (ua2_linear_args.split_ws): handed to launches under UA2_SUM_ORDER_FREE only
   size_t split_ws_bytes = 0;
   bool scaled = false;
+  // B = 1 greedy frames with both per-id tables: no arg-max launches inside the depth decoder.  The arg-max + table gather after steps
+  // 0 .. n_cb - 2 is done by the launch that consumes it, layer 0's O-projection of the next step (ua2_argmax_fold); the arg-max of the
+  // LAST step runs inside feedback_kernel's one block (its embedding gather has no reader: there is no further step).  Each consumer
+  // redoes a tiny reduction after an ordinary kernel boundary: no flags, no counters, nothing to spin on.  UA2_NO_ARGMAX_FOLD=1, read
+  // when the plan is created: off (A/B; one process can hold both plans)
+  bool argmax_fold = false;
   int32_t npart_t, npart_a;
   int32_t topk = 1;            // 1 = greedy (fused arg-max partials); > 1 = ua2_sample_topk
   float temperature = 1.f;
@@ -235,7 +241,7 @@ struct RiderPlan {
 // rp: the launches of this GPT that can (RiderPlan::ok) carry their share of the rider's column tiles.
 int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const int32_t* row_pos,
             const int32_t* row_seq, hipStream_t s, bool local = false, bool grouped = false, const float* final_norm_w = nullptr,
-            bool scaled = false, RiderPlan* rp = nullptr, bool qkv0_given = false) {
+            bool scaled = false, RiderPlan* rp = nullptr, bool qkv0_given = false, const ua2_argmax_fold* fold0 = nullptr) {
   auto launch = [&](const ua2_linear_args& a, int kind) -> int {
     if (rp && rp->ok[kind]) {
       int t0, t1;
@@ -294,6 +300,10 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     a.M = R; a.N = C; a.K = qn; a.x = fuse_attn ? h->q : h->yattn; a.ldx = qn;
     a.w0 = h->ptrs[gi][1][l]; a.y = x; a.ldy = C; a.resid = x; a.ldr = C;
     if (fuse_attn) { a.row_pos = row_pos; a.row_seq = row_seq; a.kv = kv; }
+    if (fold0 && l == 0) {            // the previous step's arg-max and table gathers happen inside this launch (ua2_argmax_fold)
+      UA2_CHECK(fuse_attn && qkv0_given, "ua2_stage3: the arg-max fold needs the fused local attention and the q | k | v table");
+      a.fold = *fold0;
+    }
     if (pack_o && !fuse_attn) a.x_packed = h->gemm_ws;
     if (scaled) ho.produce(a, h->norms[gi][1][l]);              // x after attention -> norm_2 + fc_1 / fc_2
     a.sum_order = order; free_scratch(a);
@@ -326,10 +336,32 @@ __global__ void bump_kernel(int32_t* c) { c[0] += 1; }
 __global__ void feedback_kernel(int R, int ncb, int mode, int reason_eos, int reason_card, int log_frames,
                                 int max_rows, int32_t* __restrict__ tokens, uint8_t* __restrict__ mask,
                                 int32_t* __restrict__ row_pos, int32_t* __restrict__ forbid,
-                                const int32_t* __restrict__ out, int32_t* __restrict__ log, int32_t* counters, int no_text,
-                                const float* __restrict__ hfin, float* __restrict__ stash, int C, int cap_frames) {
-  const int frame = counters[0];
+                                int32_t* out, int32_t* __restrict__ log, int32_t* counters, int no_text,
+                                const float* __restrict__ hfin, float* __restrict__ stash, int C, int cap_frames,
+                                int am_npart, int am_limit, const float* __restrict__ am_pmax, const int32_t* __restrict__ am_pidx) {
   const int w = ncb + 1;
+  // am_npart > 0 (R == 1, greedy, heads_impl left the launch out): the last codebook step's arg-max over audio_head's partials, as
+  // argmax_embed_kernel takes it — the same 256 threads, candidates, order and tie / all-NaN rules (ua2_row_token) — into out[ncb]
+  if (am_npart > 0) {
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    __shared__ int tok_s;
+    float bv = -INFINITY;
+    int bi = UA2_TOK_NONE;
+    for (int p = threadIdx.x; p < am_npart; p += blockDim.x) {
+      const float v = am_pmax[p];
+      const int i = am_pidx[p];
+      if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    }
+    const int tok = ua2_row_token(bv, bi, am_limit, sv, si, &tok_s, [&] {
+      int lo = UA2_TOK_NONE;
+      for (int p = threadIdx.x; p < am_npart; p += blockDim.x) lo = min(lo, am_pidx[p]);
+      return lo;
+    });
+    if (threadIdx.x == 0) out[ncb] = tok;
+    __syncthreads();                  // the row loop below reads it
+  }
+  const int frame = counters[0];
   // UA2_FRAME_DEFER_TEXT_HEAD, frames of a few rows: this frame's h_final rows go into slot frame % cap_frames of the stash ring (the
   // slot is a device value — the frame is a replayed graph).  cap_frames * R rows fit the ring (checked by the launcher); C % 4 == 0.
   if (stash && frame >= 0) {
@@ -462,6 +494,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
   h->scaled = d->dtype == UA2_BF16 && getenv("UA2_NO_SCALED") == nullptr && d->backbone.n_embd % 32 == 0 && d->decoder.n_embd % 32 == 0 &&
               d->max_batch <= 64;
   h->npart_t = (d->vt + 15) / 16; h->npart_a = (d->va + 15) / 16;
+  h->argmax_fold = getenv("UA2_NO_ARGMAX_FOLD") == nullptr;
   if (c.ptab_rows) {
     // The table is what the frame's own projection launches would write: same entry point, same arguments, rows in groups of up to 64
     // (decode kernel / weights-stationary kernel: a row's bits do not depend on its group).  Null stream, once per plan.
@@ -691,7 +724,8 @@ extern "C" int ua2_stage3_trunk(ua2_stage3* h, int32_t R, void* stream) {
 // to a list nobody reads (:259), so the frame's audio ids do not depend on it: skipping lm_head + its arg-max (788 MB of weights
 // at 3072 x 128256 bf16 = 117 us of the 3.1 ms B = 1 frame, 220 us at 64 rows) leaves (reason, semantic) bit-identical
 // (model_new.py:617 computes it every frame).  generate_frame's (B, 9) API never sets it.
-static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bool skip_text = false, bool beam = false) {
+// fold_last != NULL: the caller runs feedback_kernel next and can take the last step's arg-max (set to true when it must)
+static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bool skip_text = false, bool beam = false, bool* fold_last = nullptr) {
   UA2_CHECK(h && R > 0 && R <= h->d.max_batch, "ua2_stage3_heads: R=%d out of range", R);
   hipStream_t s = (hipStream_t)stream;
   const ua2_stage3_desc& d = h->d;
@@ -759,6 +793,8 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   // steps 1 .. n_cb - 1 take their projected input (and its hand-over) from the table, gathered by the previous step's arg-max
   // (under the order-free opt-in as well: the table rows are the row-invariant kernels' sums, one of the orders that contract allows)
   const bool tab = h->ptab_y && h->topk == 1 && (!scaled || h->ptab_ho || h->ptab_q);
+  ua2_argmax_fold fg{};
+  bool fold_next = false;             // step i left its arg-max + table gather to layer 0's O-projection of step i + 1
   for (int i = 0; i < (text_only ? 0 : d.n_cb); ++i) {             // model_new.py:630-641
     const Handover hod(h, R, Cd);
     if (!(tab && i > 0)) {
@@ -770,7 +806,9 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
       if (int rc = lin(h, a, s)) return rc;
     }
     if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, d.n_cb <= 8, false,
-                         scaled ? d.decoder.ln_f : nullptr, scaled, ride ? &rp : nullptr, tab && i > 0 && h->ptab_q)) return rc;
+                         scaled ? d.decoder.ln_f : nullptr, scaled, ride ? &rp : nullptr, tab && i > 0 && h->ptab_q,
+                         fold_next ? &fg : nullptr)) return rc;
+    fold_next = false;
     fresh_args(h, a);
     a.dtype = d.dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_STORE;
     a.M = R; a.N = d.va; a.K = Cd; a.x = h->xd; a.ldx = Cd; a.norm_w = d.decoder.ln_f; a.eps = d.decoder.eps;
@@ -782,7 +820,16 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     if (cfg)   // model_new.py:634-637
       if (int rc = ua2_cfg_mix(h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->cfg_scale, d.forbid, h->pmax_a,
                                h->pidx_a, R / 2, s)) return rc;
-    if (tab && i + 1 < d.n_cb) {
+    // R == 1 with layer 0's q | k | v in the table and the attention fused into the O-projection: that launch of step i + 1 takes the tail
+    const ua2_gpt_desc& gdec = d.decoder;
+    if (tab && i + 1 < d.n_cb && h->argmax_fold && h->ptab_q && R == 1 && !cfg && d.n_cb <= 8 && !no_local_fuse() && gdec.n_layer > 0 && h->w8.empty() &&
+        ua2_gemv_fold_ok(d.dtype, gdec.n_embd, gdec.n_head * gdec.head_size)) {          // (fp8 plans keep the arg-max launches: the fold has no fp8 form)
+      fg = ua2_argmax_fold{};
+      fg.part_max = h->pmax_a; fg.part_idx = h->pidx_a; fg.n_part = h->npart_a; fg.limit = d.va;
+      fg.out_token = d.out_tokens + 1 + i; fg.row_off = (int64_t)i * d.va; fg.pos = i + 1;
+      fg.tab_y = h->ptab_y; fg.tab_q = h->ptab_q; fg.tab_k = h->ptab_k; fg.tab_v = h->ptab_v;
+      fold_next = true;
+    } else if (tab && i + 1 < d.n_cb) {
       const ua2_handover g = hod.rowwise(nullptr);
       ua2_qkv_gather qg{};
       if (h->ptab_q) {
@@ -795,6 +842,8 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
       // with layer 0's q | k | v in hand nothing reads the hand-over of the projected row (its only consumer was that launch)
       if (int rc = ua2_argmax_gather(R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, h->ptab_y, h->ptab_h, h->ptab_ssq,
                                      (int64_t)i * d.va, Cd, h->xd, (scaled && !h->ptab_q) ? &g : nullptr, h->ptab_q ? &qg : nullptr, s)) return rc;
+    } else if (h->topk == 1 && fold_last && h->argmax_fold && tab && R == 1 && i + 1 == d.n_cb) {
+      *fold_last = true;              // nothing reads this step's embedding (tab: steps >= 1 read the table), and the id is feedback_kernel's
     } else if (h->topk == 1) {
       if (int rc = ua2_argmax_embed_launch(d.dtype, R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, d.audio_emb,
                                     i * d.va, C, h->curr_h, s)) return rc;
@@ -821,7 +870,8 @@ extern "C" int ua2_stage3_heads(ua2_stage3* h, int32_t R, void* stream) { return
 // defer_frames > 0 (UA2_FRAME_DEFER_TEXT_HEAD): the frame's h_final rows go into the stash ring of that many frame slots.  Up to 4 rows the
 // copy (48 KB at C = 3072) is part of feedback_kernel's one block — no launch is added to the B = 1 frame; more rows take a launch of
 // one block per row in front of it (one block would copy 390 KB at 32 rows: longer than the 3.5 us of a launch).
-static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card, void* stream, int no_text, int defer_frames = 0) {
+static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card, void* stream, int no_text, int defer_frames = 0,
+                         bool fold_argmax = false) {
   UA2_CHECK(h && R > 0 && R <= h->d.max_rows && mode >= 0 && mode <= 2, "ua2_stage3_feedback: bad arguments");
   const ua2_stage3_desc& d = h->d;
   if (mode == 1 && h->ngram_n > 1) {   // asr_task.py:371-375: the filtered id is what the log records and the next frame consumes
@@ -842,7 +892,8 @@ static int feedback_impl(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_
   }
   hipLaunchKernelGGL(feedback_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, R, d.n_cb, mode, reason_eos,
                      reason_card, d.log_frames, d.max_rows, d.tokens, d.mask, d.row_pos, d.forbid, d.out_tokens,
-                     d.frame_log, d.counters, no_text, h->hfin, fold ? h->defer_stash : nullptr, C, fold ? defer_frames : 1);
+                     d.frame_log, d.counters, no_text, h->hfin, fold ? h->defer_stash : nullptr, C, fold ? defer_frames : 1,
+                     fold_argmax ? h->npart_a : 0, d.va, h->pmax_a, h->pidx_a);
   UA2_LAUNCH_CHECK();
   return 0;
 }
@@ -881,7 +932,8 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   }
   auto body = [&](hipStream_t st) -> int {
     if (int rc = trunk_impl(h, R, true, st, skip_experts)) return rc;
-    if (int rc = heads_impl(h, R, mode == 1 || beam, st, skip_text, beam)) return rc;
+    bool fold_last = false;
+    if (int rc = heads_impl(h, R, mode == 1 || beam, st, skip_text, beam, (mode == 0 && R == 1) ? &fold_last : nullptr)) return rc;
     if (mode < 0) return 0;
     if (beam) {
       const ua2_stage3_desc& d = h->d;
@@ -890,7 +942,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
       if (int rc = ua2_beam_reorder_groups(h->beam_W, h->beam_G, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
       return feedback_impl(h, R, 1, reason_eos, reason_card, st, 0);   // out_tokens' text column holds the step's ids: the text feedback as it is
     }
-    return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0, defer_frames);
+    return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0, defer_frames, fold_last);
   };
   if (!use_graph) return body(s);
   int tbits, cbits;

@@ -121,7 +121,7 @@ def linear(*, dtype, M, N, K, w0, prologue=PRO_CAST, epilogue=EPI_STORE, x=None,
            w1=None, y=None, ldy=None, resid=None, ldr=None, part_max=None, part_idx=None,
            forbid=None, row_pos=None, row_seq=None, rope_cos=None, rope_sin=None, q_out=None, kv=None, launch=True,
            norm_b=None, norm_kind=0, out_scale=None, rope_mode=0, workspace=None, bias=None, bias1=None, act_kind=0,
-           y_packed=None, x_packed=None, y_norm_w=None, y_h=None, ldh=0, y_ssq=None, x_h=None, x_ssq=None, split_ws=None, sum_order=0, y_ln=None, range_ws=None):
+           y_packed=None, x_packed=None, y_norm_w=None, y_h=None, ldh=0, y_ssq=None, x_h=None, x_ssq=None, split_ws=None, sum_order=0, y_ln=None, range_ws=None, fold=None):
     a = LinearArgs()
     a.dtype, a.prologue, a.epilogue = dtype_code(dtype), prologue, epilogue
     a.M, a.N, a.K = M, N, K
@@ -149,6 +149,11 @@ def linear(*, dtype, M, N, K, w0, prologue=PRO_CAST, epilogue=EPI_STORE, x=None,
         a.y_ln_w, a.y_ln_b, a.y_ln_eps = ptr(y_ln[0]), ptr(y_ln[1]), float(y_ln[2])
     if kv is not None:
         a.kv = kv
+    if fold is not None:                 # ua2_argmax_fold (PRO_LOCAL_ATTN): dict of its fields, tensors for the pointers
+        f = a.fold
+        f.part_max, f.part_idx, f.out_token = ptr(fold["part_max"]), ptr(fold["part_idx"]), ptr(fold["out_token"])
+        f.n_part, f.limit, f.row_off, f.pos = fold["n_part"], fold["limit"], fold["row_off"], fold["pos"]
+        f.tab_y, f.tab_q, f.tab_k, f.tab_v = ptr(fold["tab_y"]), ptr(fold["tab_q"]), ptr(fold["tab_k"]), ptr(fold["tab_v"])
     if not launch:
         return a
     check(lib.ua2_linear(C.byref(a), stream()), "ua2_linear")
