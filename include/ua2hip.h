@@ -131,6 +131,32 @@ size_t ua2_packed_bytes_w8(int64_t N, int64_t K);
 int ua2_pack_linear_w8(const void* src, int src_dtype, int transposed, int64_t N, int64_t K, void* out_q, int8_t* out_exp,
                        void* out_bf16, int rope_head_size, void* stream);
 
+/* ---- [v10, addition] lossless 13-bit image of a packed bf16 weight; UA2_BF16 launches of the decode kernel only ----------------------
+ * A bf16 weight is s | E[7:0] | m[6:0]; its sign and mantissa are close to uniform, its exponent is not: inside a 16-column tile nearly
+ * every weight lies within 30 binades of the largest.  The image stores, for every element of ua2_pack_linear's bf16 form
+ * [N/16][K/32][64 lanes][8 elements] (same lane <-> (column, k) map, K % 128 == 0):
+ *   low byte  E[0] | m, raw;
+ *   code q    4 bits: q = 0 means E[7:1] == 0 (exact +-0 and the lowest pair of binades), q = 1 .. 15 means E[7:1] == base + q;
+ *   sign      1 bit;
+ * and per tile one byte base = max(largest E[7:1] of the tile - 15, 0), in a side array [N/16] (packed tile order).  A weight with
+ * 0 < E[7:1] <= base cannot be written: an ESCAPE.  ua2_pack_linear_l13 counts them; an image with escapes != 0 must not be used (its
+ * escaped weights hold q = 0) and the weight stays on its bf16 form — there are no per-tile fallbacks.  With escapes == 0 the decode
+ * s | (q ? base + q : 0) | low byte gives back every bf16 bit pattern (NaN payloads and infinities included), so a launch on the image
+ * computes with the very B fragments of the bf16 launch: every sum, id and cache entry is unchanged.
+ * Layout: per tile, K / 128 groups of 4 chunks, 3328 B each (13/16 of the bf16 form), four dense planes so that every wave load is
+ * contiguous and every lane load aligned:
+ *   [0, 2048)     low bytes: pair p of chunks (2p, 2p + 1) = [64 lanes][16 B]: the lane's 8 low bytes of chunk 2p, then of chunk 2p + 1;
+ *   [2048, 3072)  codes: [64 lanes][4 chunks] dwords; byte b of a dword = q(element b) | q(element b + 4) << 4;
+ *   [3072, 3328)  signs: [64 lanes] dwords; bit 8 b + 2 c + h = sign of element 4 h + b of chunk c of the group.
+ * ua2_packed_bytes_l13 returns 0 for shapes without an image (K % 128 != 0).  ua2_pack_linear_l13 reads the PACKED bf16 form (device),
+ * writes the image, the base bytes [ceil(N / 16)] and *escapes (one int32 on the device), stream-ordered. */
+typedef struct {
+  const void* image;     /* 13-bit image */
+  const uint8_t* base;   /* per-tile base bytes */
+} ua2_l13_ref;
+size_t ua2_packed_bytes_l13(int64_t N, int64_t K);
+int ua2_pack_linear_l13(const void* packed_bf16, int64_t N, int64_t K, void* out_image, uint8_t* out_base, int32_t* escapes, void* stream);
+
 /* Geometry of the paged KV cache shared by the QKV epilogue and the attention kernel.
  * Pool layout (per layer): [n_pages][n_kv][UA2_PAGE][head_size] of `dtype`, K and V separate.
  * page_table[seq*max_pages + p] = page id holding positions [p*UA2_PAGE, (p+1)*UA2_PAGE). */
@@ -281,6 +307,12 @@ int ua2_linear(const ua2_linear_args* a, void* stream);
  * LOCAL_ATTN with RESIDUAL.  Anything else is an error (never a silent launch on the bf16 form).  Same grid, waves, chunk ranges and
  * summation order as the bf16 launch of that (N, K): bit-identical outputs.  Counted as "gemv_w8" by ua2_debug_kernel_launches. */
 int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream);
+/* [v10, addition] ua2_linear on the 13-bit images of a->w0 (and a->w1 for SWIGLU; both must be escape-free): the launches ua2_linear_w8
+ * serves (UA2_BF16, up to ua2_gemv_rows_preferred rows, a prologue / epilogue pair of the decode frame, no x_packed, no argmax fold) with
+ * K % 128 == 0; anything else is refused with a message.  Same grid, waves, chunk ranges and summation order as the bf16 launch and the
+ * same B fragments: bit-identical outputs.  Counted as "gemv_l13" (and, a decode-kernel launch on bf16 weights, as "gemv") by
+ * ua2_debug_kernel_launches. */
+int ua2_linear_l13(const ua2_linear_args* a, const ua2_l13_ref* w0, const ua2_l13_ref* w1, void* stream);
 /* [v10, addition] The many-row counterpart: one launch on the fp8 twins through the weights-stationary kernel (csrc/ua2_skinny.hip,
  * skinny2_kernel with W8 = true) — the batched decode frame, 6 .. UA2_SKINNY_W8_MAX_ROWS rows (default 64; 0 / "off" = never).  Served: UA2_BF16,
  * K % 64 == 0, more rows than the launchers give the decode kernel, a workspace (or x_packed), a Linear geometry of the released widths
@@ -306,18 +338,25 @@ size_t ua2_linear_workspace_bytes(int dtype, int64_t M, int64_t K);
 int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
- * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "rsplit" ([v10] the range split
+ * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "gemv_l13" (the decode kernel on 13-bit images of its bf16 weights: such a launch counts under "gemv" as well), "rsplit" ([v10] the range split
  * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
  * call getenv on every launch); a process that changes one of them afterwards (the tests do) calls this to have them read again. */
 int64_t ua2_debug_kernel_launches(const char* family);
+/* [v10, addition] Test hook: the decode kernel's launch geometry for an [N, K] weight of `dtype` and nt matrices per launch (2 = SWIGLU) —
+ * workgroup waves and chunks per wave per round; *multi_round = 1 when a wave walks its range in several double-buffered rounds. */
+int ua2_debug_gemv_geometry(int dtype, int32_t N, int32_t K, int32_t nt, int32_t* waves, int32_t* cpw, int32_t* multi_round);
 void ua2_debug_refresh_env(void);
 
 /* Measurement helper (bench.py roofline leg): launches args[0..n) back to back `iters` times on
  * `stream`, bracketed by hipEvents recorded on that same stream, waits for the stop event and
  * returns the elapsed milliseconds in *ms_out.  No other work is enqueued in between. */
 int ua2_linear_chain_timed(const ua2_linear_args* args, int32_t n, int32_t iters, void* stream, float* ms_out);
+/* [v10, addition] The same chain through ua2_linear_l13: launch i on the images w0[i] (and w1[i]; w1 may be NULL when no launch is a
+ * SWIGLU one) — the image side of ua2_linear_chain_timed for tools/ubench/gemv_shapes.py. */
+int ua2_linear_l13_chain_timed(const ua2_linear_args* args, const ua2_l13_ref* w0, const ua2_l13_ref* w1, int32_t n, int32_t iters, void* stream,
+                               float* ms_out);
 /* [v10, addition] The same chain through ua2_linear_w8_many: launch i on the fp8 twins w0[i] (and w1[i]; w1 may be NULL when no launch is a
  * SWIGLU one).  Same host path and the same events as ua2_linear_chain_timed, so the two figures of one shape can be compared
  * (tools/ubench/skinny_shapes.py --w8). */
@@ -849,6 +888,29 @@ typedef struct {
   const int8_t* exp;
 } ua2_w8_entry;
 int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32_t n);
+/* [v10, addition] Lossless 13-bit weight images (ua2_pack_linear_l13 above).  ua2_stage3_create packs, for a UA2_BF16 plan, an image of
+ * every Linear weight a decode frame streams — the layers of the three trunk GPTs and of the depth decoder, projection, the audio heads;
+ * not lm_head — and keeps those without an escape; the handle owns them (about 13/16 of the plan's weight bytes in extra device memory).
+ * The frame's few-row launches that the decode kernel serves (up to ua2_gemv_rows_preferred rows; not the argmax-fold launch, not launches
+ * that carry riders, not the one form the image makes longer — a 16-chunk single burst on fewer than 160 workgroups, the depth decoder's
+ * down-projection at the released sizes —) then stream the image of a weight that has one: the same bits as the bf16 form, fewer bytes.  Everything else — prefill,
+ * larger batches, the plan's tables, UA2_F32 plans — reads the bf16 form.  fp8 twins (ua2_stage3_set_w8), when attached, take precedence.
+ * On by default; UA2_NO_LOSSLESS=1 in the environment when the plan is created packs nothing.  ua2_stage3_set_lossless switches a plan that
+ * has images and drops the captured frame graphs.  ua2_stage3_lossless_stats reports what creation found: how many matrices compress
+ * depends on the weights (the escape count of each) and is measured, never assumed. */
+typedef struct {
+  int32_t on;                     /* images in use by the frame's launches */
+  int32_t with_image;             /* matrices with an escape-free image */
+  int32_t without_image;          /* matrices on bf16 alone: K % 128 != 0, an escape, or no memory for the images */
+  int32_t with_escapes;           /* ... of those, the ones with at least one escape */
+  int64_t bf16_bytes_per_frame;   /* weight bytes one B = 1 frame streams from these matrices in bf16 (depth decoder: once per codebook) */
+  int64_t image_bytes_per_frame;  /* ... and with every image in use */
+  int64_t extra_device_bytes;     /* device memory the images take */
+  float build_ms;                 /* host time of packing them */
+  int32_t reserved;
+} ua2_lossless_info;
+int ua2_stage3_set_lossless(ua2_stage3* h, int32_t on);
+int ua2_stage3_lossless_stats(const ua2_stage3* h, ua2_lossless_info* out);
 /* n-gram repeat filter of the text-feedback frames: with n >= 2 every feedback of mode 1 (ua2_stage3_frame with or without
  * UA2_FRAME_SKIP_AUDIO_EXPERTS, and the standalone feedback) first runs the n-gram filter above over the text ids of its R rows,
  * so the frame log and the fed-back text id carry the filtered id.  hist [max_batch, cap] / hist_len [max_batch] int32 are

@@ -86,6 +86,17 @@ class W8Entry(C.Structure):
     _fields_ = [("w", vp), ("q", vp), ("exp", vp)]
 
 
+class L13Ref(C.Structure):
+    """ua2_l13_ref: lossless 13-bit image + per-tile base bytes of one packed bf16 weight (ua2_pack_linear_l13)."""
+    _fields_ = [("image", vp), ("base", vp)]
+
+
+class LosslessInfo(C.Structure):
+    """ua2_lossless_info: what ua2_stage3_create found when it packed the plan's 13-bit weight images."""
+    _fields_ = [("on", i32), ("with_image", i32), ("without_image", i32), ("with_escapes", i32), ("bf16_bytes_per_frame", i64),
+                ("image_bytes_per_frame", i64), ("extra_device_bytes", i64), ("build_ms", f32), ("reserved", i32)]
+
+
 class BeamState(C.Structure):
     """ua2_beam_state: the caller-owned device buffers of a beam search (include/ua2hip.h)."""
     _fields_ = [("score", vp), ("fin", vp), ("len", vp), ("parent", vp), ("ctrl", vp), ("cand_logp", vp), ("cand_id", vp),
@@ -130,10 +141,17 @@ _EXPORTS = {
     "ua2_linear_w8": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), vp]),
     "ua2_linear_w8_many": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(W8Ref), C.POINTER(W8Ref), vp]),
     "ua2_stage3_set_w8": (C.c_int, [vp, C.POINTER(W8Entry), i32]),
+    "ua2_packed_bytes_l13": (C.c_size_t, [i64, i64]),
+    "ua2_pack_linear_l13": (C.c_int, [vp, i64, i64, vp, vp, vp, vp]),
+    "ua2_linear_l13": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(L13Ref), C.POINTER(L13Ref), vp]),
+    "ua2_linear_l13_chain_timed": (C.c_int, [C.POINTER(LinearArgs), C.POINTER(L13Ref), C.POINTER(L13Ref), i32, i32, vp, C.POINTER(C.c_float)]),
+    "ua2_stage3_set_lossless": (C.c_int, [vp, i32]),
+    "ua2_stage3_lossless_stats": (C.c_int, [vp, C.POINTER(LosslessInfo)]),
     "ua2_linear_order_free_accepts": (C.c_int, [C.POINTER(LinearArgs)]),
     "ua2_debug_force_general_linear": (C.c_int, [C.c_int]),
     "ua2_debug_kernel_launches": (i64, [C.c_char_p]),
     "ua2_debug_refresh_env": (None, []),
+    "ua2_debug_gemv_geometry": (C.c_int, [C.c_int, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "ua2_struct_size": (C.c_size_t, [C.c_int]),
     "ua2_dwconv1d": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "ua2_cfg_mix": (C.c_int, [vp, i32, i32, C.c_float, vp, vp, vp, i32, vp]),

@@ -193,7 +193,7 @@ inline void ua2_allow_big_lds() {
 }
 
 // ---- test hooks (ua2hip.h ABI v9): launch counters per kernel family, and UA2_* environment variables read once -------------
-enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_SKINNY2_W8 = 7, UA2_CNT_ARGMAX = 8, UA2_CNT_N = 9 };
+enum { UA2_CNT_GEMM2 = 0, UA2_CNT_GEMM = 1, UA2_CNT_SKINNY2 = 2, UA2_CNT_GEMV = 3, UA2_CNT_RSPLIT = 4, UA2_CNT_GEMV_W8 = 5, UA2_CNT_TEXT_FLUSH = 6, UA2_CNT_SKINNY2_W8 = 7, UA2_CNT_ARGMAX = 8, UA2_CNT_GEMV_L13 = 9, UA2_CNT_N = 10 };
 extern std::atomic<int64_t> g_ua2_launches[UA2_CNT_N];
 extern std::atomic<int> g_ua2_env_gen;              // bumped by ua2_debug_refresh_env
 inline void ua2_count_launch(int family) { g_ua2_launches[family].fetch_add(1, std::memory_order_relaxed); }
@@ -221,6 +221,9 @@ struct Ua2W8 {
   const void *q0 = nullptr, *q1 = nullptr;
   const int8_t *e0 = nullptr, *e1 = nullptr;
   bool strict = false, many = false;
+  // l13: q0 / q1 are lossless 13-bit images of a.w0 / a.w1 (ua2_pack_linear_l13) and e0 / e1 their per-tile base bytes: the decode kernel
+  // alone streams them (ua2_linear_l13; the executor's images), every other kernel reads a.w0 / a.w1 — the very same weights
+  bool l13 = false;
 };
 // internal launchers used by both the op-level ABI and the frame executor
 // w8 != NULL: launches that the decode kernel or the weights-stationary kernel (6 .. UA2_SKINNY_W8_MAX_ROWS rows) serves stream the fp8
@@ -259,6 +262,9 @@ int ua2_kv_rows_extract(const void* k_pool, const void* v_pool, const int32_t* p
 int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
 // does the decode kernel have an fp8-weight form for this launch (bf16, K % 64 == 0, a (prologue, epilogue) pair of the decode frame, a geometry it tiles)?
 bool ua2_gemv_w8_ok(const ua2_linear_args& a);
+// ... and a form on the lossless 13-bit image (bf16, K % 128 == 0, the same pairs, a geometry whose wave ranges are whole groups of 4 chunks or
+// the small-K fall-back)?
+bool ua2_gemv_l13_ok(const ua2_linear_args& a);
 // riders (ua2_gemv.hip gemv_rider_kernel): column tiles [tile0, tile1) of the one-row-tile GEMV `r` on the idle CUs of host launch `a`
 bool ua2_gemv_rider_ok(const ua2_linear_args& a, const ua2_linear_args& r);
 int ua2_gemv_launch_with_rider(const ua2_linear_args& a, const ua2_linear_args& r, int tile0, int tile1, hipStream_t s);

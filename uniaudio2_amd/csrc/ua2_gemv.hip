@@ -126,6 +126,34 @@ __device__ __forceinline__ void local_attn_fold_prologue(const ua2_linear_args& 
 // but once on the reduced tile (a power of two commutes with every fp32 rounding of the chain and of the cross-wave sum).
 // (dequant_e4m3x8: ua2_linear_common.h — the weights-stationary kernel of ua2_skinny.hip reads the same image.)
 
+// ---- lossless 13-bit image (W8 = 3 / 4; include/ua2hip.h ua2_pack_linear_l13) ------------------------------------------------------
+// Per 16-column tile and group of 4 chunks, 3328 B in dense planes: 2 x 1 KiB of low bytes (E[0] | mantissa; the fp8 image's shape: a lane's
+// 16 bytes are its 8 of chunk 2p and its 8 of chunk 2p + 1), 1 KiB of codes (a lane's dword per chunk: byte b = q of element b | q of element
+// b + 4 << 4) and 256 B of signs (a lane's dword per group: bit 8 b + 2 c + h = sign of element 4 h + b of chunk c).  Decoding is SWAR on
+// four high bytes at a time — s | (q ? base + q : 0) — and one v_perm_b32 per two weights interleaves them with the low bytes: the B
+// fragment the bf16 image holds, bit for bit.  Counted in the ISA of gemv_l13_kernel<SCALED, SWIGLU, 4, true, 3>: 23 VALU per chunk
+// of 8 weights (2 nibble masks + a shift, 2 x (add, and, shift, sub, add, and) for the exponent bytes, 2 x (shift, and-or) for the signs,
+// 4 perms), 2.9 per weight.
+constexpr int kL13Group = 208;                                 // u32x4 per group: 64 + 64 low, 64 codes, 16 of signs
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+struct L13Group { u32x4 lo0, lo1, code; unsigned sign; };      // W8 = 3: a lane's share of a whole group, 13 dwords for 4 chunks
+struct L13Chunk { u32x2 lo; unsigned code, sign; };            // W8 = 4: of one chunk (the group's sign dword whole)
+template <int W8> struct WFrag { using type = u32x4; };
+template <> struct WFrag<3> { using type = L13Group; };
+template <> struct WFrag<4> { using type = L13Chunk; };
+
+// chunk `cg` of its group: low bytes of elements 0-3 / 4-7, the chunk's code dword, the group's sign dword; base4 = the tile's base in every byte
+__device__ __forceinline__ u32x4 l13_decode(unsigned lo_a, unsigned lo_b, unsigned code, unsigned sign, int cg, unsigned base4) {
+  auto high = [&](unsigned qb, int bit) {
+    const unsigned nz = (qb + 0x7f7f7f7fu) & 0x80808080u;      // bit 7 of a byte: q != 0 (q <= 15: no carry)
+    const unsigned keep = nz - (nz >> 7);                      // 0x7f where q != 0: E[7:1] has seven bits (base + q <= 127)
+    return ((sign << (7 - bit)) & 0x80808080u) | ((qb + base4) & keep);
+  };
+  const unsigned h_a = high(code & 0x0f0f0f0fu, 2 * cg), h_b = high((code >> 4) & 0x0f0f0f0fu, 2 * cg + 1);
+  return u32x4{__builtin_amdgcn_perm(h_a, lo_a, 0x05010400u), __builtin_amdgcn_perm(h_a, lo_a, 0x07030602u),
+               __builtin_amdgcn_perm(h_b, lo_b, 0x05010400u), __builtin_amdgcn_perm(h_b, lo_b, 0x07030602u)};
+}
+
 // 1 KiB burst of the weight image that load `u` of the round starting at chunk `cb` fetches (`last` = the wave's last chunk: clamped, never predicated)
 template <int W8>
 __device__ __forceinline__ int burst_index(int cb, int u, int last) {
@@ -134,12 +162,39 @@ __device__ __forceinline__ int burst_index(int cb, int u, int last) {
   else return min(cb + u, last);
 }
 
+// load `u` of the round starting at chunk `cb`: a 1 KiB burst (W8 <= 2; wp carries the lane), a group's four planes (3), a chunk's share of them (4)
+template <int W8>
+__device__ __forceinline__ typename WFrag<W8>::type weight_load(const u32x4* wp, int lane, int cb, int u, int last) {
+  if constexpr (W8 == 3) {
+    const u32x4* p = wp + (size_t)min((cb >> 2) + u, last >> 2) * kL13Group;
+    L13Group f;
+    f.sign = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p + 192) + lane);
+    f.code = __builtin_nontemporal_load(p + 128 + lane);
+    f.lo0 = __builtin_nontemporal_load(p + lane);
+    f.lo1 = __builtin_nontemporal_load(p + 64 + lane);
+    return f;
+  } else if constexpr (W8 == 4) {
+    const int c = min(cb + u, last);
+    const u32x4* p = wp + (size_t)(c >> 2) * kL13Group;
+    L13Chunk f;
+    f.sign = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p + 192) + lane);
+    f.code = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(p + 128 + lane) + (c & 3));
+    f.lo = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + ((c >> 1) & 1) * 64 + lane) + (c & 1));
+    return f;
+  } else {
+    return __builtin_nontemporal_load(wp + (size_t)burst_index<W8>(cb, u, last) * 64);
+  }
+}
+
 // MR = multi-round: <= 8 waves per workgroup, several rounds of CPW chunks per wave, next round's
 // weights prefetched (double buffer); !MR = single burst: up to 16 waves, everything up front.
 // W8: 0 = the weights of a.w0 / a.w1 in the launch dtype; 1 = fp8 image, the wave's chunk range is a whole number of rounds of CPW
 // chunks (every shape of the released model): CPW / 2 loads per round; 2 = fp8 image, any range of up to CPW chunks (odd starts,
 // single-chunk ranges: small K): one load per chunk, the half picked by the chunk's parity.  The geometry, the chunk order inside a
 // wave's chain and the order of the cross-wave sum are those of W8 = 0, whatever the form.
+// 3 / 4 = the lossless 13-bit image of the same bf16 weights (l13_decode above), shaped like 1 / 2: 3 = whole rounds, one load set per group of 4
+// chunks (a wave's range starts on a group: CPW >= 4), decoded chunk by chunk as the planes land (the round in flight behind it in the
+// multi-round forms); 4 = any range of up to CPW chunks, a load set per chunk.  No scale: the decoded fragment IS the bf16 one.
 // FOLD (UA2_PRO_LOCAL_ATTN, W8 = 0): the launch carries a ua2_argmax_fold; an instantiation of its own, so that the plain launches keep
 // their registers (the CPW = 16 forms sit at the 128-register limit of a 16-wave workgroup).
 template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0, bool FOLD = false>
@@ -147,8 +202,10 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
                                           const int bx, const int by, const Ua2W8* w8 = nullptr) {
   constexpr int KC = Elem<DT>::KC, EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
   constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
-  static_assert(W8 == 0 || DT == UA2_BF16, "fp8 weights are a bf16-plan option");
-  constexpr int NL = (W8 == 1) ? CPW / 2 : CPW;               // weight loads per matrix per round
+  static_assert(W8 == 0 || DT == UA2_BF16, "fp8 weights and 13-bit images are bf16-plan options");
+  constexpr bool FP8 = W8 == 1 || W8 == 2, L13 = W8 == 3 || W8 == 4;
+  constexpr int NL = (W8 == 1) ? CPW / 2 : (W8 == 3) ? CPW / 4 : CPW;     // weight loads (load sets) per matrix per round
+  using WF = typename WFrag<W8>::type;
   char* a_lds = smem;                                        // [rows][a_stride] of T
   float* red = reinterpret_cast<float*>(smem + red_off);     // [nw][NT][256]
   float* ssq = red + kMaxWaves * NT * 256;                   // [nw][16]
@@ -165,7 +222,11 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   const int nchunks = (a.K + KC - 1) / KC;
   int tile[NT];
   const u32x4* wp[NT];
-  if constexpr (W8 != 0) {                                     // [N/16][K/64][64 lanes][16 B]: nchunks / 2 bursts per tile (K % 64 == 0)
+  if constexpr (L13) {                                         // [N/16][K/128] groups of kL13Group x 16 B (K % 128 == 0); the lane goes on in weight_load
+    tile[0] = bx;
+    wp[0] = reinterpret_cast<const u32x4*>(w8->q0) + (size_t)bx * (nchunks >> 2) * kL13Group;
+    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(w8->q1) + (size_t)bx * (nchunks >> 2) * kL13Group; }
+  } else if constexpr (W8 != 0) {                              // [N/16][K/64][64 lanes][16 B]: nchunks / 2 bursts per tile (K % 64 == 0)
     tile[0] = bx;
     wp[0] = reinterpret_cast<const u32x4*>(w8->q0) + (size_t)bx * (nchunks >> 1) * 64 + lane;
     if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(w8->q1) + (size_t)bx * (nchunks >> 1) * 64 + lane; }
@@ -224,17 +285,25 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   int wexp[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) wexp[t] = 0;
-  if constexpr (W8 != 0) {
+  if constexpr (FP8) {
     wexp[0] = w8->e0[bx * 16 + (tid & 15)];
     if constexpr (NT == 2) wexp[1] = w8->e1[bx * 16 + (tid & 15)];
   }
+  // 13-bit image: the tile's base byte (workgroup-uniform, needed at decode time only), spread to the four bytes of a dword
+  unsigned base4[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) base4[t] = 0u;
+  if constexpr (L13) {
+    base4[0] = (unsigned)reinterpret_cast<const unsigned char*>(w8->e0)[bx] * 0x01010101u;
+    if constexpr (NT == 2) base4[1] = (unsigned)reinterpret_cast<const unsigned char*>(w8->e1)[bx] * 0x01010101u;
+  }
 
-  u32x4 wf[NT][NL];
+  WF wf[NT][NL];
   auto burst = [&]() {
 #pragma unroll
     for (int u = 0; u < NL; ++u)
 #pragma unroll
-      for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(c0, u, last) * 64);
+      for (int t = 0; t < NT; ++t) wf[t][u] = weight_load<W8>(wp[t], lane, c0, u, last);
   };
   if constexpr (PRO == UA2_PRO_LOCAL_ATTN) {
     if constexpr (FOLD) {
@@ -409,13 +478,13 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   const char* abase = a_lds + ((size_t)i * a_stride + g * EPL) * BYTES;
   for (int cb = c0; cb < c1; cb += CPW) {
     // multi-round geometries: the next round's weights go out before this round's MFMAs
-    u32x4 wn[NT][MR ? NL : 1];
+    WF wn[NT][MR ? NL : 1];
     const bool more = MR && (cb + CPW < c1);
     if constexpr (MR) if (more) {
 #pragma unroll
       for (int u = 0; u < NL; ++u)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) wn[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(cb + CPW, u, last) * 64);
+        for (int t = 0; t < NT; ++t) wn[t][u] = weight_load<W8>(wp[t], lane, cb + CPW, u, last);
     }
 #pragma unroll
     for (int u = 0; u < CPW; ++u) {
@@ -433,6 +502,13 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
           const u32x4 w = wf[t][u];
           const bool odd = (min(c, last) & 1) != 0;
           af.mma(dequant_e4m3x8(odd ? w[2] : w[0], odd ? w[3] : w[1]), acc[t]);
+        } else if constexpr (W8 == 3) {                    // chunk cb + u: chunk u % 4 of load set u / 4 (cb is a multiple of 4)
+          const L13Group& w = wf[t][u >> 2];
+          const u32x4& lo = (u & 2) ? w.lo1 : w.lo0;
+          af.mma(l13_decode(lo[(u & 1) * 2], lo[(u & 1) * 2 + 1], w.code[u & 3], w.sign, u & 3, base4[t]), acc[t]);
+        } else if constexpr (W8 == 4) {                    // chunk c: its own load set (a clamped chunk meets a zero A fragment)
+          const L13Chunk& w = wf[t][u];
+          af.mma(l13_decode(w.lo[0], w.lo[1], w.code, w.sign, min(c, last) & 3, base4[t]), acc[t]);
         } else {
           af.mma(wf[t][u], acc[t]);
         }
@@ -449,7 +525,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
 #pragma unroll
       for (int u = 0; u < NL; ++u)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) wf[t][u] = __builtin_nontemporal_load(wp[t] + (size_t)burst_index<W8>(cb + CPW, u, last) * 64);
+        for (int t = 0; t < NT; ++t) wf[t][u] = weight_load<W8>(wp[t], lane, cb + CPW, u, last);
     }
   }
 
@@ -467,7 +543,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     for (int w = 0; w < nw; ++w) s += red[(w * NT + t) * 256 + src];
     v[t] = s;
     // fp8 weights: the column's scale 2^e, once, on the reduced sum (exact: e in [-117, 120] keeps 2^e a normal float)
-    if constexpr (W8 != 0) v[t] = __fmul_rn(s, __uint_as_float((unsigned)(wexp[t] + 127) << 23));
+    if constexpr (FP8) v[t] = __fmul_rn(s, __uint_as_float((unsigned)(wexp[t] + 127) << 23));
   }
   linear_epilogue<DT, EPI, NT>(a, v, tile, row, col, pre, m0, rows);
 }
@@ -483,6 +559,15 @@ __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_kernel(const u
 template <int PRO, int EPI, int CPW, bool MR, int W8>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_w8_kernel(const ua2_linear_args a, const int a_stride,
                                                                  const int red_off, const int rt, const Ua2W8 w8) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
+}
+
+// ... and on the lossless 13-bit image of the bf16 weights themselves (W8 = 3 / 4): 13/16 of the bytes, the same bits
+template <int PRO, int EPI, int CPW, bool MR, int W8>
+__global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_l13_kernel(const ua2_linear_args a, const int a_stride,
+                                                                  const int red_off, const int rt, const Ua2W8 w8) {
+  static_assert(W8 == 3 || W8 == 4, "the 13-bit forms");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
 }
@@ -646,10 +731,29 @@ void launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, dim3 grid, int wav
   ua2_count_launch(UA2_CNT_GEMV_W8);
 }
 
+template <int PRO, int EPI, int CPW, bool MR, int W8>
+void launch_one_l13(const ua2_linear_args& a, const Ua2W8& w8, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
+  constexpr auto kern = gemv_l13_kernel<PRO, EPI, CPW, MR, W8>;
+  ua2_allow_big_lds<kern>();
+  hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt, w8);
+  ua2_count_launch(UA2_CNT_GEMV);       // bf16 weights through the decode kernel: a "gemv" launch as well (the counter's readers count launches of the frame)
+  ua2_count_launch(UA2_CNT_GEMV_L13);
+}
+
 // Which fp8 form serves a geometry: 1 = every wave's range is whole rounds of cpw chunks; 2 = ranges of up to 4 chunks in one
 // single-burst round of 4 (the small-K fall-back geometries); 0 = none (the launch stays on the bf16 twin).
 int w8_form(int nchunks, const Geometry& geo) {
   if (nchunks % 2) return 0;
+  if (nchunks % geo.waves == 0 && (nchunks / geo.waves) % geo.cpw == 0) return 1;
+  const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
+  if (!mr && geo.cpw == 4 && ua2_ceil_div(nchunks, geo.waves) <= 4) return 2;
+  return 0;
+}
+
+// ... and which 13-bit form: 1 = whole rounds (a wave's range then starts on a group of 4 chunks: cpw >= 4), 2 = the small-K fall-back
+// geometries, a load set per chunk
+int l13_form(int nchunks, const Geometry& geo) {
+  if (nchunks % 4) return 0;
   if (nchunks % geo.waves == 0 && (nchunks / geo.waves) % geo.cpw == 0) return 1;
   const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
   if (!mr && geo.cpw == 4 && ua2_ceil_div(nchunks, geo.waves) <= 4) return 2;
@@ -678,6 +782,23 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullpt
   const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
   if constexpr (DT == UA2_BF16 && (EPI == UA2_EPI_QKV_ROPE || EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_STORE || EPI == UA2_EPI_RESIDUAL) &&
                 !(PRO == UA2_PRO_CAST && (EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_QKV_ROPE))) {
+    if (w8 && w8->l13) {
+      const int form = l13_form(nchunks, geo);
+      if (form == 2) {
+        launch_one_l13<PRO, EPI, 4, false, 4>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else if (form == 1 && mr) {
+        if (geo.cpw == 4) launch_one_l13<PRO, EPI, 4, true, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one_l13<PRO, EPI, 8, true, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else if (form == 1) {
+        if (geo.cpw == 4) launch_one_l13<PRO, EPI, 4, false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else if (geo.cpw == 8 || NT == 2) launch_one_l13<PRO, EPI, 8, false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+        else launch_one_l13<PRO, EPI, (NT == 1 ? 16 : 8), false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
+      } else {
+        return 1;
+      }
+      UA2_LAUNCH_CHECK();
+      return 0;
+    }
     if (w8) {     // the same grid, waves, LDS carve and chunk ranges: only the weight stream differs
       const int form = w8_form(nchunks, geo);
       if (form == 2) {
@@ -849,6 +970,14 @@ ua2_gemv_geometry ua2_pick_gemv_geometry(int dtype, int N, int K, int nt) {
   return ua2_gemv_geometry{g.waves, g.cpw};
 }
 
+extern "C" int ua2_debug_gemv_geometry(int dtype, int32_t N, int32_t K, int32_t nt, int32_t* waves, int32_t* cpw, int32_t* multi_round) {
+  UA2_CHECK(waves && cpw && multi_round && N > 0 && K > 0 && (nt == 1 || nt == 2), "ua2_debug_gemv_geometry: bad arguments");
+  const int nchunks = ua2_ceil_div(K, dtype == UA2_BF16 ? 32 : 16);
+  const Geometry g = pick_geometry(nchunks, ua2_ceil_div(N, 16), nt);
+  *waves = g.waves; *cpw = g.cpw; *multi_round = (g.waves <= 8 && g.waves * g.cpw < nchunks) ? 1 : 0;
+  return 0;
+}
+
 // Returns 0 if launched, 1 if this problem is outside the decode regime (caller uses the general
 // kernel), negative on error.
 bool ua2_gemv_w8_ok(const ua2_linear_args& a) {
@@ -857,8 +986,19 @@ bool ua2_gemv_w8_ok(const ua2_linear_args& a) {
   return w8_form(a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
 }
 
+bool ua2_gemv_l13_ok(const ua2_linear_args& a) {
+  if (a.dtype != UA2_BF16 || a.K % 128 || a.N <= 0 || !w8_pair(a.prologue, a.epilogue) || a.fold.part_max || rows_per_tile(a.dtype, a.K) < 1) return false;
+  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
+  return l13_form(a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
+}
+
 int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
   if (rows_per_tile(a.dtype, a.K) < 1) return 1;   // a single row does not fit the LDS budget
+  if (w8 && w8->l13) {                             // images of a.w0 / a.w1: where the decode kernel has no form for them the launch reads the weights themselves
+    if (w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && ua2_gemv_l13_ok(a)) return launch_dt<UA2_BF16>(a, s, w8);
+    if (w8->strict) return 1;
+    w8 = nullptr;
+  }
   if (w8 && w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && ua2_gemv_w8_ok(a)) return launch_dt<UA2_BF16>(a, s, w8);
   if (w8 && w8->strict) return 1;                  // asked for by name: never the bf16 twin in its place
   if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s);

@@ -112,13 +112,75 @@ __global__ void w8_pack_kernel(const void* __restrict__ src, const int8_t* __res
   }
 }
 
+// ---- lossless 13-bit image of a packed bf16 weight: include/ua2hip.h ua2_pack_linear_l13 ------------------------------------------
+// one workgroup per 16-column tile: the largest E[7:1] of the tile -> its base byte, then the weights below the window -> the escape count
+__global__ __launch_bounds__(256) void l13_base_kernel(const unsigned short* __restrict__ w, uint8_t* __restrict__ out_base, int32_t* __restrict__ escapes,
+                                                       int64_t tile_elems) {
+  __shared__ int red[4];
+  const unsigned short* t = w + (size_t)blockIdx.x * tile_elems;
+  int mx = 0;
+  for (int64_t i = threadIdx.x; i < tile_elems; i += 256) mx = max(mx, (t[i] >> 8) & 0x7f);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  const int base = max(max(max(red[0], red[1]), max(red[2], red[3])) - 15, 0);
+  int esc = 0;
+  for (int64_t i = threadIdx.x; i < tile_elems; i += 256) {
+    const int e7 = (t[i] >> 8) & 0x7f;
+    esc += (e7 != 0 && e7 <= base) ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) esc += __shfl_xor(esc, o);
+  if ((threadIdx.x & 63) == 0 && esc) atomicAdd(escapes, esc);
+  if (threadIdx.x == 0) out_base[blockIdx.x] = (uint8_t)base;
+}
+
+// one thread per (tile, group of 4 chunks, lane): its 4 x 16 B of the bf16 image -> its share of the group's four planes
+__global__ __launch_bounds__(256) void l13_pack_kernel(const u32x4* __restrict__ w, const uint8_t* __restrict__ bases, u32x4* __restrict__ out,
+                                                       int64_t groups_per_tile, int64_t total) {
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int lane = (int)(idx & 63);
+    const int64_t grp = idx >> 6, tile = grp / groups_per_tile;
+    const int base = bases[tile];
+    unsigned lo[8], code[4], sign = 0u;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const u32x4 v = w[(grp * 4 + c) * 64 + lane];
+      unsigned la = 0u, lb = 0u, cd = 0u;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const unsigned b = (v[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
+        const int e7 = (int)((b >> 8) & 0x7fu);
+        const unsigned q = (unsigned)min(max(e7 - base, 0), 15);          // 0: E[7:1] == 0 (an escape lands here too: such an image is never used)
+        const int by = e & 3, h = e >> 2;
+        if (h == 0) la |= (b & 0xffu) << (8 * by); else lb |= (b & 0xffu) << (8 * by);
+        cd |= q << (8 * by + 4 * h);
+        sign |= (b >> 15) << (8 * by + 2 * c + h);
+      }
+      lo[2 * c] = la; lo[2 * c + 1] = lb; code[c] = cd;
+    }
+    u32x4* g = out + grp * 208;
+    g[lane] = u32x4{lo[0], lo[1], lo[2], lo[3]};
+    g[64 + lane] = u32x4{lo[4], lo[5], lo[6], lo[7]};
+    g[128 + lane] = u32x4{code[0], code[1], code[2], code[3]};
+    reinterpret_cast<unsigned*>(g + 192)[lane] = sign;
+  }
+}
+
 }  // namespace
 
 static int g_force_general = 0;
 
 int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
   const bool w8_many = w8 && w8->strict && w8->many;
-  const bool w8_strict = w8 && w8->strict && !w8->many;
+  const bool l13 = w8 && w8->l13;                                     // images of a.w0 / a.w1 for the decode kernel alone
+  const bool w8_strict = w8 && w8->strict && !w8->many && !l13;
+  const Ua2W8* const w8_gemm = l13 ? nullptr : w8;                    // what the many-row kernels may stream
+  if (l13 && w8->strict)
+    UA2_CHECK(a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_l13_ok(a),
+              "ua2_linear_l13: not a launch the decode kernel serves on a 13-bit image (UA2_BF16, K %% 128 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed, no argmax fold)",
+              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
   if (w8_many)
     UA2_CHECK(ua2_gemm_w8_serves(a, *w8),
               "ua2_linear_w8_many: not a launch the fp8 weights-stationary kernel serves (UA2_BF16, K %% 64 == 0, %d to %d rows [UA2_SKINNY_W8_MAX_ROWS], "
@@ -172,7 +234,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
   if (a.x_packed) {   // operand handed over in fragment order by its producer: only the many-row kernels read it
     UA2_CHECK((a.prologue == UA2_PRO_CAST || a.prologue == UA2_PRO_SCALED) && g_force_general != 2,
               "ua2_linear: x_packed needs PRO_CAST / PRO_SCALED and the many-row kernels");
-    const int rc = ua2_gemm_try_launch(a, s, w8_many ? 0 : (g_force_general >= 4 ? g_force_general : 3), w8);
+    const int rc = ua2_gemm_try_launch(a, s, w8_many ? 0 : (g_force_general >= 4 ? g_force_general : 3), w8_gemm);
     UA2_CHECK(rc <= 0, "%s: x_packed launch not applicable", w8_many ? "ua2_linear_w8_many" : "ua2_linear");
     return rc;
   }
@@ -220,8 +282,8 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
     UA2_CHECK(rc <= 0, "ua2_linear_w8_many: the fp8 weights-stationary kernel did not take the launch");
     return rc;
   }
-  if (g_force_general != 2 && !w8_strict) {
-    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8);  // many rows: packed operand, 128-row tiles
+  if (g_force_general != 2 && !w8_strict && !(l13 && w8->strict)) {
+    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8_gemm);  // many rows: packed operand, 128-row tiles
     if (rc <= 0) return rc;
   }
   const int rc = ua2_gemv_try_launch(a, s, w8);  // decode regime: LDS-staged activations, all loads up front
@@ -325,6 +387,57 @@ extern "C" int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, con
   if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
   w8.strict = true;
   return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
+}
+
+extern "C" size_t ua2_packed_bytes_l13(int64_t N, int64_t K) {
+  if (N <= 0 || K <= 0 || K % 128) return 0;
+  return (size_t)((N + 15) / 16) * (size_t)(K / 128) * 3328;
+}
+
+extern "C" int ua2_pack_linear_l13(const void* packed_bf16, int64_t N, int64_t K, void* out_image, uint8_t* out_base, int32_t* escapes, void* stream) {
+  UA2_CHECK(packed_bf16 && out_image && out_base && escapes && N > 0 && K > 0, "ua2_pack_linear_l13: bad arguments");
+  UA2_CHECK(K % 128 == 0, "ua2_pack_linear_l13: K=%lld must be a multiple of 128 (groups of four 32-wide chunks)", (long long)K);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t tiles = (N + 15) / 16, groups = K / 128, total = tiles * groups * 64;
+  UA2_HIP(hipMemsetAsync(escapes, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(l13_base_kernel, dim3((unsigned)tiles), dim3(256), 0, s, (const unsigned short*)packed_bf16, out_base, escapes, 16 * K);
+  hipLaunchKernelGGL(l13_pack_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535 * 16)), dim3(256), 0, s, (const u32x4*)packed_bf16,
+                     out_base, (u32x4*)out_image, groups, total);
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_linear_l13(const ua2_linear_args* a, const ua2_l13_ref* w0, const ua2_l13_ref* w1, void* stream) {
+  UA2_CHECK(a != nullptr && w0 != nullptr && w0->image && w0->base, "ua2_linear_l13: NULL args or image of w0");
+  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->image && w1->base), "ua2_linear_l13: SWIGLU needs the image of w1");
+  Ua2W8 w8;
+  w8.q0 = w0->image; w8.e0 = reinterpret_cast<const int8_t*>(w0->base);
+  if (w1) { w8.q1 = w1->image; w8.e1 = reinterpret_cast<const int8_t*>(w1->base); }
+  w8.strict = w8.l13 = true;
+  return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
+}
+
+extern "C" int ua2_linear_l13_chain_timed(const ua2_linear_args* args, const ua2_l13_ref* w0, const ua2_l13_ref* w1, int32_t n, int32_t iters,
+                                          void* stream, float* ms_out) {
+  UA2_CHECK(args && w0 && n > 0 && iters > 0 && ms_out, "ua2_linear_l13_chain_timed: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipEvent_t e0, e1;
+  UA2_HIP(hipEventCreate(&e0));
+  UA2_HIP(hipEventCreate(&e1));
+  UA2_HIP(hipEventRecord(e0, s));
+  for (int it = 0; it < iters; ++it)
+    for (int i = 0; i < n; ++i)
+      if (int rc = ua2_linear_l13(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s)) {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return rc;
+      }
+  UA2_HIP(hipEventRecord(e1, s));
+  UA2_HIP(hipEventSynchronize(e1));
+  UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return 0;
 }
 
 static int linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, hipStream_t s) {

@@ -7,6 +7,7 @@
 // device memory, so the launch sequence is identical from frame to frame and is captured once
 // into a hipGraph and replayed: no host round trip between the 350-odd kernels of a frame and
 // none between frames (the reference synchronises twice per frame, tts_task.py:261,263).
+#include <chrono>
 #include <map>
 #include <stdlib.h>
 #include <string.h>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "ua2_common.h"
+#include "ua2_linear_common.h"
 
 struct ua2_stage3 {
   ua2_stage3_desc d;
@@ -85,6 +87,15 @@ struct ua2_stage3 {
   // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
   struct W8Twin { const void* q; const int8_t* exp; };
   std::map<const void*, W8Twin> w8;
+  // Lossless 13-bit images (include/ua2hip.h ua2_pack_linear_l13) of the Linear weights a decode frame streams, packed when a bf16 plan is
+  // created: packed bf16 pointer -> (image, base bytes), escape-free matrices only.  One allocation, owned by the handle.  The few-row
+  // launches the decode kernel serves stream the image instead of the bf16 form — the same bits, 13/16 of the bytes; fp8 twins, when
+  // attached, take precedence.  ua2_stage3_set_lossless / UA2_NO_LOSSLESS=1 (read at creation: no images are packed)
+  struct L13Img { const void* image; const uint8_t* base; };
+  std::map<const void*, L13Img> l13;
+  void* l13_mem = nullptr;
+  bool lossless = false;
+  ua2_lossless_info l13_info{};
   std::map<std::tuple<int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
 };
 
@@ -165,8 +176,32 @@ void fresh_args(const ua2_stage3* h, ua2_linear_args& a) {
 // which streams them where the decode kernel serves the launch (up to 5 rows) or the weights-stationary kernel does (6 ..
 // UA2_SKINNY_W8_MAX_ROWS rows of a released Linear shape: decode frames, and prefill chunks that small) and reads a.w0 / a.w1 — the bf16
 // forms of W' — everywhere else.  Same bits either way.
+// The one launch form of the frame that the image makes clearly LONGER (kernel trace, profiles/lossless_weights.md): a single 16-chunk burst
+// per wave on a grid well under the CU count — the depth decoder's down-projection, 8192 -> 2048 on 128 workgroups, 9.6 -> 10.4 us, 32
+// times per frame.  Its time is one workgroup's latency chain, which the decode lengthens, not the stream.  It keeps bf16 (the same bits);
+// the trunk's down-projection (192 workgroups) gains and keeps its image.  UA2_L13_ALL=1: every served launch (A/B).
+bool l13_pays(const ua2_linear_args& a) {
+  static Ua2EnvInt all{"UA2_L13_ALL", 0};
+  if (all.get()) return true;
+  const ua2_gemv_geometry g = ua2_pick_gemv_geometry(a.dtype, a.N, a.K, a.epilogue == UA2_EPI_SWIGLU ? 2 : 1);
+  return !(g.cpw == 16 && ua2_ceil_div(a.N, 16) < 160);
+}
+
 int lin(const ua2_stage3* h, const ua2_linear_args& a, hipStream_t s) {
-  if (h->w8.empty()) return ua2_linear_launch(a, s);
+  if (h->w8.empty()) {
+    if (h->lossless && !a.x_packed && !a.fold.part_max && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_l13_ok(a) && l13_pays(a)) {
+      const auto i0 = h->l13.find(a.w0);
+      const auto i1 = a.epilogue == UA2_EPI_SWIGLU ? h->l13.find(a.w1) : i0;
+      if (i0 != h->l13.end() && i1 != h->l13.end()) {
+        Ua2W8 w;
+        w.l13 = true;
+        w.q0 = i0->second.image; w.e0 = reinterpret_cast<const int8_t*>(i0->second.base);
+        if (a.epilogue == UA2_EPI_SWIGLU) { w.q1 = i1->second.image; w.e1 = reinterpret_cast<const int8_t*>(i1->second.base); }
+        return ua2_linear_launch(a, s, &w);
+      }
+    }
+    return ua2_linear_launch(a, s);
+  }
   const auto t0 = h->w8.find(a.w0);
   if (t0 == h->w8.end()) return ua2_linear_launch(a, s);
   Ua2W8 w;
@@ -446,6 +481,77 @@ __global__ void emb_rows_f32_kernel(const void* __restrict__ emb, long long row0
     out[i] = load_elem<DT>(emb, (size_t)row0 * C + i);
 }
 
+// Images of every Linear weight a decode frame streams (the three trunk GPTs, the depth decoder, projection, the audio heads; not lm_head:
+// the flush's many-row kernel reads it).  Null stream, once per plan; the escape counts come back in one copy.  A plan that cannot get the
+// memory runs without images (the stats say so): the same bits either way.
+int build_l13(ua2_stage3* h) {
+  const ua2_stage3_desc& d = h->d;
+  struct Mat { const void* w; int64_t N, K; int64_t per_frame; size_t img_off, base_off; };
+  std::vector<Mat> mats;
+  std::map<const void*, int> seen;
+  auto add = [&](const void* w, int64_t N, int64_t K, int64_t per_frame) {
+    if (!w || N <= 0 || K <= 0) return;
+    const auto it = seen.find(w);
+    if (it != seen.end()) { mats[it->second].per_frame += per_frame; return; }
+    seen[w] = (int)mats.size();
+    mats.push_back(Mat{w, N, K, per_frame, 0, 0});
+  };
+  const ua2_gpt_desc* gs[4] = {&d.und, &d.backbone, &d.gen, &d.decoder};
+  for (int gi = 0; gi < 4; ++gi) {
+    const ua2_gpt_desc& g = *gs[gi];
+    const int64_t C = g.n_embd, qn = (int64_t)g.n_head * g.head_size, nqkv = (int64_t)(g.n_head + 2 * g.n_kv) * g.head_size;
+    const int64_t pf = gi == 3 ? std::max(d.n_cb, 1) : 1;          // the depth decoder runs once per codebook
+    for (int l = 0; l < g.n_layer; ++l) {
+      add(h->ptrs[gi][0][l], nqkv, C, pf); add(h->ptrs[gi][1][l], C, qn, pf);
+      add(h->ptrs[gi][2][l], g.inter, C, pf); add(h->ptrs[gi][3][l], g.inter, C, pf); add(h->ptrs[gi][4][l], C, g.inter, pf);
+    }
+  }
+  add(d.projection, d.decoder.n_embd, d.backbone.n_embd, 1);
+  for (const void* p : h->audio_head) add(p, d.va, d.decoder.n_embd, 1);
+  ua2_lossless_info& info = h->l13_info;
+  info = ua2_lossless_info{};
+  size_t off = 0;
+  auto take = [&](size_t n) { const size_t o = off; off += (n + 255) & ~(size_t)255; return o; };
+  for (Mat& m : mats) {
+    const size_t ib = ua2_packed_bytes_l13(m.N, m.K);
+    if (!ib) continue;
+    m.img_off = take(ib); m.base_off = take((size_t)((m.N + 15) / 16));
+  }
+  const size_t esc_off = take(mats.size() * sizeof(int32_t));
+  const auto t0 = std::chrono::steady_clock::now();
+  bool have = !mats.empty() && hipMalloc(&h->l13_mem, off) == hipSuccess;
+  if (!have) { (void)hipGetLastError(); h->l13_mem = nullptr; }
+  std::vector<int32_t> esc(mats.size(), 0);
+  if (have) {
+    char* base = static_cast<char*>(h->l13_mem);
+    for (size_t i = 0; i < mats.size(); ++i) {
+      const Mat& m = mats[i];
+      if (!ua2_packed_bytes_l13(m.N, m.K)) continue;
+      if (int rc = ua2_pack_linear_l13(m.w, m.N, m.K, base + m.img_off, reinterpret_cast<uint8_t*>(base + m.base_off),
+                                       reinterpret_cast<int32_t*>(base + esc_off) + i, nullptr)) return rc;
+    }
+    UA2_HIP(hipMemcpy(esc.data(), base + esc_off, esc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    info.extra_device_bytes = (int64_t)off;
+  }
+  for (size_t i = 0; i < mats.size(); ++i) {
+    const Mat& m = mats[i];
+    const int64_t bf = (int64_t)ua2_packed_elems(UA2_BF16, m.N, m.K) * 2, ib = (int64_t)ua2_packed_bytes_l13(m.N, m.K);
+    const bool ok = have && ib && esc[i] == 0;
+    info.bf16_bytes_per_frame += bf * m.per_frame;
+    info.image_bytes_per_frame += (ok ? ib + (m.N + 15) / 16 : bf) * m.per_frame;
+    if (ok) {
+      ++info.with_image;
+      h->l13[m.w] = ua2_stage3::L13Img{static_cast<char*>(h->l13_mem) + m.img_off, reinterpret_cast<const uint8_t*>(static_cast<char*>(h->l13_mem) + m.base_off)};
+    } else {
+      ++info.without_image;
+      if (have && ib) ++info.with_escapes;
+    }
+  }
+  info.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->lossless = !h->l13.empty();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t ua2_stage3_scratch_floats(const ua2_stage3_desc* d) { return d ? carve(*d).total : 0; }
@@ -551,6 +657,8 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
     if (tmp_k) { (void)hipFree(tmp_k); (void)hipFree(tmp_v); (void)hipFree(tmp_i); }
     if (e != hipSuccess) { ua2_set_error("ua2_stage3_create: building the projected-embedding table failed: %s", hipGetErrorString(e)); delete h; return -1; }
   }
+  if (d->dtype == UA2_BF16 && getenv("UA2_NO_LOSSLESS") == nullptr)
+    if (int rc = build_l13(h)) { ua2_stage3_destroy(h); return rc; }
   *out = h;
   return 0;
 }
@@ -559,6 +667,7 @@ extern "C" void ua2_stage3_destroy(ua2_stage3* h) {
   if (!h) return;
   for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+  if (h->l13_mem) (void)hipFree(h->l13_mem);
   delete h;
 }
 
@@ -652,6 +761,24 @@ extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32
   for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);     // recorded frames bake the kernels and the weight pointers: drop them
   h->graphs.clear();
   h->w8.swap(m);
+  return 0;
+}
+
+extern "C" int ua2_stage3_set_lossless(ua2_stage3* h, int32_t on) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_lossless: NULL handle");
+  const bool want = on != 0 && !h->l13.empty();
+  if (want != h->lossless) {                          // recorded frames bake the kernels and the weight pointers: drop them
+    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
+    h->graphs.clear();
+  }
+  h->lossless = want;
+  return 0;
+}
+
+extern "C" int ua2_stage3_lossless_stats(const ua2_stage3* h, ua2_lossless_info* out) {
+  UA2_CHECK(h != nullptr && out != nullptr, "ua2_stage3_lossless_stats: NULL argument");
+  *out = h->l13_info;
+  out->on = h->lossless ? 1 : 0;
   return 0;
 }
 

@@ -221,6 +221,20 @@ class Model_stage3(nn.Module):
         check(lib.ua2_stage3_set_w8(self._h, tab, len(w8)), "ua2_stage3_set_w8")
         self._w8_on = True
 
+    def set_lossless(self, on: bool = True):
+        """Switch the plan's lossless 13-bit weight images (bf16 plans; on by default) on or off: the same ids and logits bit for bit
+        either way; the captured frame graphs are dropped (include/ua2hip.h ua2_stage3_set_lossless)."""
+        self._need()
+        check(lib.ua2_stage3_set_lossless(self._h, int(bool(on))), "ua2_stage3_set_lossless")
+
+    def lossless_stats(self):
+        """ua2_stage3_lossless_stats as a dict: matrices with / without an image, bytes per frame, extra device memory, build time."""
+        from .._lib import LosslessInfo
+        self._need()
+        info = LosslessInfo()
+        check(lib.ua2_stage3_lossless_stats(self._h, C.byref(info)), "ua2_stage3_lossless_stats")
+        return {k: getattr(info, k) for k, _ in LosslessInfo._fields_ if k != "reserved"}
+
     def _destroy(self):
         if self._h is not None:
             lib.ua2_stage3_destroy(self._h)

@@ -108,6 +108,29 @@ def linear_w8_many(args, w0, w1=None):
     check(lib.ua2_linear_w8_many(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8_many")
 
 
+def pack_linear_l13(packed, N, K):
+    """Packed bf16 weight (pack_linear(..., torch.bfloat16)) of an [N, K] Linear, K % 128 == 0 -> (image, base, escapes): the lossless
+    13-bit image (uint8), the per-tile base bytes (uint8 [ceil(N / 16)]) and the escape count (int32 [1], on the device)
+    (ua2_pack_linear_l13).  An image with escapes != 0 must not be handed to linear_l13."""
+    assert packed.is_cuda and packed.dtype == torch.bfloat16 and packed.numel() == packed_elems(torch.bfloat16, N, K)
+    nbytes = lib.ua2_packed_bytes_l13(N, K)
+    if nbytes == 0:
+        raise ValueError(f"no 13-bit image for K={K} (K % 128 != 0)")
+    image = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    base = torch.empty((N + 15) // 16, dtype=torch.uint8, device=packed.device)
+    esc = torch.zeros(1, dtype=torch.int32, device=packed.device)
+    check(lib.ua2_pack_linear_l13(ptr(packed), N, K, ptr(image), ptr(base), ptr(esc), stream()), "ua2_pack_linear_l13")
+    return image, base, esc
+
+
+def linear_l13(args, w0, w1=None):
+    """ua2_linear_l13: the launch `args` (ops.linear(..., launch=False); w0 / w1 = the packed bf16 weights) on their 13-bit images
+    w0, w1 = (image, base)."""
+    r0 = _lib.L13Ref(ptr(w0[0]), ptr(w0[1]))
+    r1 = _lib.L13Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
+    check(lib.ua2_linear_l13(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_l13")
+
+
 def kv_geom(k_pool, v_pool, page_table, n_head, n_kv, head_size, ring_pages=0):
     g = KvGeom()
     g.ring_pages = ring_pages
@@ -171,6 +194,19 @@ def linear_chain_timed(args_list, iters):
     ms = C.c_float(0.0)
     check(lib.ua2_linear_chain_timed(arr, len(args_list), iters, stream(), C.byref(ms)), "ua2_linear_chain_timed")
     return ms.value / (len(args_list) * iters)
+
+
+def linear_l13_chain_timed(args_list, images, iters):
+    """Average milliseconds per launch of the given launches through ua2_linear_l13, back to back, HIP-event timed: the image side of
+    linear_chain_timed (same host path).  images[i] = ((image, base) of w0, (image, base) of w1 or None)."""
+    n = len(args_list)
+    arr = (LinearArgs * n)(*args_list)
+    r0 = (_lib.L13Ref * n)(*[_lib.L13Ref(ptr(t[0][0]), ptr(t[0][1])) for t in images])
+    has1 = any(t[1] is not None for t in images)
+    r1 = (_lib.L13Ref * n)(*[_lib.L13Ref(ptr(t[1][0]), ptr(t[1][1])) if t[1] is not None else _lib.L13Ref() for t in images]) if has1 else None
+    ms = C.c_float(0.0)
+    check(lib.ua2_linear_l13_chain_timed(arr, r0, r1, n, iters, stream(), C.byref(ms)), "ua2_linear_l13_chain_timed")
+    return ms.value / (n * iters)
 
 
 def linear_w8_many_chain_timed(args_list, twins, iters):
