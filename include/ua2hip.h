@@ -283,8 +283,9 @@ typedef struct ua2_linear_args {
      takes it as x_packed with UA2_PRO_CAST).  Where the launch runs as K slabs the combine forms it in the same pass (one launch
      instead of combine + prep); otherwise a row pass follows the GEMM.  Only the order-free kernel implements it (N % 4 == 0,
      N <= 2048): ua2_linear_order_free_accepts() tells a caller beforehand whether a launch will be taken; a launch that carries
-     y_ln_w and is not is an error.  The statistics are summed in this kernel's own order (fp32): same value as the prep launch's to
-     rounding, not to the bit — the order-free contract. */
+     y_ln_w and is not is an error.  The statistics are the prep launch's two-pass form (centred variance, the mean carried in two
+     parts) summed in this kernel's own order (fp32): same value as the prep launch's to rounding, not to the bit — the order-free
+     contract. */
   const float* y_ln_w;
   const float* y_ln_b;
   float y_ln_eps;

@@ -244,6 +244,77 @@ def half_ulp_bf16(v):
     return 0.5 * _bf16_quantum(v.to(F64))
 
 
+# ---- hand-overs of the order-free kernel (include/ua2hip.h y_ln_w, y_norm_w / UA2_PRO_SCALED) -----------------------------------
+
+def ln_handover_ref(y, w, b, eps, dt=F64):
+    """The LayerNorm hand-over before its rounding to bf16: (y - mean) rstd w + b over the columns of y, the two-pass centred form
+    (kr.layernorm_ref) in `dt`."""
+    return kr.layernorm_ref(y, w, b, eps, dt)
+
+
+def ln_handover_naive32(y, w, b, eps):
+    """The formula the hand-over must NOT use, replayed in fp32: var = mean(y^2) - mean^2, which loses the variance's digits once
+    |mean| >> std.  For checking that the hand-over condition notices it."""
+    y, w = y.float(), w.float()
+    n = y.shape[-1]
+    mean = y.sum(-1, keepdim=True) / n
+    var = ((y * y).sum(-1, keepdim=True) / n - mean * mean).clamp_min(0.0)
+    out = (y - mean) * (1.0 / torch.sqrt(var + torch.tensor(eps, dtype=torch.float32))) * w
+    return out if b is None else out + b.float()
+
+
+def ln_handover_excess(got, y, w, b, eps):
+    """The hand-over's pass condition on `got` [M, N] (the bf16 values a launch wrote, or any candidate): per element
+    |got - ref| <= half_ulp_bf16(ref) + B, ref = the float64 LayerNorm of y (the launch's OWN fp32 y), B = kr.bar(E_ref) scale,
+    scale = max(1, max |ref|), E_ref = error of the fp32 replay of the same two-pass formula / scale.
+    Returns (worst, e_ref, bar): worst = max over the elements of (|got - ref| - half_ulp_bf16(ref)) / scale, to be <= bar."""
+    ref = ln_handover_ref(y, w, b, eps, F64)
+    ref32 = ln_handover_ref(y, w, b, eps, torch.float32).to(F64)
+    scale = max(1.0, float(ref.abs().max()))
+    e_ref = float((ref32 - ref).abs().max()) / scale
+    d = (got.to(F64) - ref).abs() - half_ulp_bf16(ref)
+    return float(d.max()) / scale, e_ref, kr.bar(e_ref)
+
+
+def hostile_rows(N, seed):
+    """The four hostile rows of the LayerNorm cases [4, N] fp32: unit scale, mean 1e3 with std 1, the constant 2.5, scale 1e-3."""
+    g = torch.Generator().manual_seed(seed)
+    r = torch.randn(4, N, generator=g)
+    r[1] += 1e3
+    r[2] = 2.5
+    r[3] *= 1e-3
+    return r
+
+
+def scaled_rstd_ref(ssq, K, eps, dt=F64):
+    """UA2_PRO_SCALED: the row scale rsqrt(sum_j ssq[m][j] / K + eps) from the producer's per-16-column sums of squares."""
+    return torch.rsqrt(ssq.to(dt).sum(-1, keepdim=True) / K + eps)
+
+
+def scaled_linear_ref(op, ssq, W, *, eps, epi=EPI_STORE, W1=None, bias=None, bias1=None, act_kind=0, qkv=None, dt=F64):
+    """A UA2_PRO_SCALED launch: y = epilogue(rstd[m] (op W^T)), op [M, K] = the bf16 operand the producer wrote (taken as it is:
+    the reference is built from the producer's bits), rstd from its ssq [M, K / 16]."""
+    a = op.to(dt)
+    rs = scaled_rstd_ref(ssq, a.shape[1], eps, dt)
+    s = rs * ksum_ref(a, weights_ref(W, torch.bfloat16, dt), torch.bfloat16, dt)
+    if epi == EPI_STORE:
+        return store_ref(s, bias, dt)
+    if epi == EPI_SWIGLU:
+        return swiglu_ref(s, rs * ksum_ref(a, weights_ref(W1, torch.bfloat16, dt), torch.bfloat16, dt), bias, bias1, act_kind, dt)
+    assert epi == EPI_QKV_ROPE
+    return qkv_rope_ref(s, qkv["pos"], qkv["n_head"], qkv["n_kv"], qkv["hs"], qkv["rope_mode"], qkv.get("cos"), qkv.get("sin"), bias, dt)
+
+
+def sample_rows(M, block=256):
+    """Three rows of every `block`-row tile of an M-row launch — first, last and one inside — sorted, without repeats: rows are
+    independent, so a reference over these rows and all columns reaches every tile of the grid."""
+    rows = set()
+    for r0 in range(0, M, block):
+        r1 = min(r0 + block, M) - 1
+        rows.update((r0, r1, r0 + (r1 - r0) * 5 // 13))
+    return sorted(rows)
+
+
 # ---- pack layout ------------------------------------------------------------------------------------------------------------
 
 def rope_rows(n, hs):
@@ -303,14 +374,16 @@ def linear_ref(x, W, dtype, *, pro=PRO_CAST, epi=EPI_STORE, norm_kind=0, norm_w=
 
 # ---- the inputs of the UA2_PRO_NORM cases -----------------------------------------------------------------------------------
 
-NORM_KS = (72, 144, 1056, 2048, 3072, 4104, 6144, 8192)     # every K at which tests/test_gpu_linear_parity.py runs UA2_PRO_NORM
+NORM_KS = (72, 144, 1056, 1536, 2048, 3072, 4104, 6144, 8192)     # every K at which the GPU parity modules run UA2_PRO_NORM
 ROW_SCALES = (1.0, 1e-3, 1e3)
 _norm_cache = {}
 
 
 def norm_rows(K, norm_kind):
-    """Rows of the NORM input at width K: one more than the bf16 row tile (300 for RMS_LIT at K = 2048: the many-row cases)."""
-    return 300 if (K == 2048 and norm_kind == NORM_RMS_LIT) else rows_per_tile(torch.bfloat16, K) + 1
+    """Rows of the NORM input at width K: one more than the bf16 row tile (300 for RMS_LIT at K = 2048 and LayerNorm at K = 1536:
+    the many-row cases)."""
+    many = (K == 2048 and norm_kind == NORM_RMS_LIT) or (K == 1536 and norm_kind == NORM_LAYERNORM)
+    return 300 if many else rows_per_tile(torch.bfloat16, K) + 1
 
 
 def norm_inputs(K, norm_kind, eps=1e-5):

@@ -6,7 +6,11 @@ instead of the decode kernel's wave ranges) — so fp32 outputs agree to fp32 su
 unit-scale sums, the bar of the K-split test), bf16 outputs (packed operand hand-offs, K/V pages) to one bf16 rounding of that
 noise, and the launch is deterministic (same bits every time: the race screen of the two-group phase structure).  The invariant
 kernels themselves are pinned on the decode kernel, which is pinned on the oracle (tests/test_gpu_invariance.py,
-tests/test_gpu_lm.py)."""
+tests/test_gpu_lm.py).
+
+This module compares two kernels of the library with each other.  The family's float64 anchor — every form here against
+tests/linear_refs.py under the bar of tests/test_gpu_linear_parity.py, at the small and ragged shapes this module does not reach —
+is tests/test_gpu_gemm2_parity.py."""
 import os
 
 import pytest

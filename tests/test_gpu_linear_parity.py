@@ -350,10 +350,11 @@ def _run_qkv(tag, dtype, nh, nkv, hs, K, *, rope_mode, pro, norm_kind, bias, per
         vp = torch.full_like(kp, SENT)
         q = torch.full((M_run, nh * hs), SENT, device=dev)
         seq_run = None if seq is None else seq[:M_run].contiguous()
+        table_d = table.cuda()                                      # kv_geom keeps the pointer only: the tensor must outlive the launch
         ops.linear(dtype=dtype, M=M_run, N=N, K=K, w0=p0, prologue=pro, epilogue=lr.EPI_QKV_ROPE, x=xd, norm_w=cu(nw), norm_b=cu(nb),
                    norm_kind=norm_kind, eps=EPS, bias=cu(b0), row_pos=pos[:M_run].cuda(), row_seq=cu(seq_run),
                    rope_cos=cos.cuda(), rope_sin=sin.cuda(), q_out=q, rope_mode=rope_mode,
-                   kv=ops.kv_geom(kp, vp, table.cuda(), nh, nkv, hs, ring_pages=ring_pages))
+                   kv=ops.kv_geom(kp, vp, table_d, nh, nkv, hs, ring_pages=ring_pages))
         torch.cuda.synchronize()
         case = f"{tag} {_dn(dtype)} {nh}/{nkv}/{hs} K={K} M={M_run}"
         qc, kc_, vc = q.cpu().to(F64).view(M_run, nh, hs), kp.cpu(), vp.cpu()

@@ -177,3 +177,94 @@ def test_flip_free_builder_moves_a_planted_candidate():
     y, rec = lr.flip_free_inputs(x, lr.NORM_RMS_LIT, w, None, 1e-5)
     assert int(lr.flip_candidates(y, lr.PRO_NORM, lr.NORM_RMS_LIT, w, None, 1e-5, rec["delta"]).sum()) == 0
     assert 1 <= rec["rounds"] <= lr.MAX_ROUNDS and rec["nudged"] >= 1 and float(y[1, 7]) != float(x[1, 7])
+
+
+# ---- references and judge of tests/test_gpu_gemm2_parity.py -------------------------------------------------------------------
+
+GEMM2_KS = tuple(32 * c for c in (1, 2, 5, 7, 33, 48, 64))         # the K list of tests/test_gpu_gemm2_parity.py (restated there as CHUNKS)
+LN_NS = (64, 1536, 2048)
+
+
+def _ln_case(N):
+    """y = the hostile rows (unit scale, mean 1e3 with std 1, the constant 2.5, scale 1e-3) and the issue's w = 1 + 0.2 randn,
+    b = 0.2 randn, eps = 1e-6."""
+    g = _g(N)
+    return lr.hostile_rows(N, N), 1.0 + 0.2 * torch.randn(N, generator=g), 0.2 * torch.randn(N, generator=g), 1e-6
+
+
+@pytest.mark.parametrize("N", LN_NS)
+def test_ln_handover_ref_vs_torch(N):
+    y, w, b, eps = _ln_case(N)
+    _close(lr.ln_handover_ref(y, w, b, eps), F.layer_norm(y.to(F64), (N,), w.to(F64), b.to(F64), eps))
+    assert torch.equal(lr.ln_handover_ref(y, w, b, eps)[2], b.to(F64))              # the constant row: exactly b
+    assert lr.ln_handover_ref(y, w, b, eps, F32).dtype == F32
+    assert torch.equal(y[2], torch.full((N,), 2.5)) and abs(float(y[1].mean()) - 1e3) < 1.0 and float(y[3].abs().max()) < 1e-2
+
+
+def test_scaled_linear_ref_vs_torch():
+    g = _g(3)
+    M, K, N = 6, 64, 48
+    op = torch.randn(M, K, generator=g).to(BF16)
+    ssq = torch.rand(M, K // 16, generator=g) * 16
+    W, W1, bias = torch.randn(N, K, generator=g) * K ** -0.5, torch.randn(N, K, generator=g) * K ** -0.5, torch.randn(N, generator=g)
+    rs = torch.rsqrt(ssq.to(F64).sum(-1, keepdim=True) / K + 1e-5)
+    _close(lr.scaled_rstd_ref(ssq, K, 1e-5), rs)
+    lin, lin1 = rs * F.linear(op.to(F64), W.to(BF16).to(F64)), rs * F.linear(op.to(F64), W1.to(BF16).to(F64))
+    _close(lr.scaled_linear_ref(op, ssq, W, eps=1e-5, bias=bias), lin + bias.to(F64))
+    _close(lr.scaled_linear_ref(op, ssq, W, eps=1e-5, epi=lr.EPI_SWIGLU, W1=W1), F.silu(lin) * lin1)
+    pos = torch.arange(M)
+    ang = torch.rand(M, 8, generator=g, dtype=F64)
+    qkv = dict(pos=pos, n_head=1, n_kv=1, hs=16, rope_mode=lr.ROPE_HALF_SPLIT, cos=ang.cos(), sin=ang.sin())
+    got = lr.scaled_linear_ref(op, ssq, W, eps=1e-5, epi=lr.EPI_QKV_ROPE, qkv=qkv)
+    want = lr.qkv_rope_ref(lin, pos, 1, 1, 16, lr.ROPE_HALF_SPLIT, ang.cos(), ang.sin())
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+    y32 = lr.scaled_linear_ref(op, ssq, W, eps=1e-5, bias=bias, dt=F32)
+    assert y32.dtype == F32 and float((y32.to(F64) - lin - bias.to(F64)).abs().max()) < 1e-5
+
+
+def test_sample_rows():
+    assert lr.sample_rows(4352, 256)[:4] == [0, 98, 255, 256] and len(lr.sample_rows(4352, 256)) == 51
+    for M, block in ((4352, 256), (257, 256), (300, 128), (1, 256)):
+        rows = lr.sample_rows(M, block)
+        assert rows == sorted(set(rows)) and 0 <= rows[0] and rows[-1] == M - 1
+        for r0 in range(0, M, block):                                # first, last and (where the block has three rows) one inside
+            r1 = min(r0 + block, M) - 1
+            inside = [r for r in rows if r0 < r < r1]
+            assert r0 in rows and r1 in rows and (len(inside) == 1 or r1 - r0 < 2)
+
+
+def _parity_judge(got, ref, ref32):
+    """err, bar of tests/test_gpu_gemm2_parity.py's _judge (the rule of test_gpu_linear_parity.py)."""
+    scale = max(1.0, float(ref.abs().max()))
+    return float((got.to(F64) - ref).abs().max()) / scale, kr.bar(float((ref32.to(F64) - ref).abs().max()) / scale)
+
+
+@pytest.mark.parametrize("K", GEMM2_KS)
+def test_the_judge_rejects_a_dropped_chunk(K):
+    """A kernel that loses the last chunk of its ring (the fault a wrong wait count or a wrong partial turn produces) is over the bar
+    at every K of the GPU module's list, on that module's RESIDUAL shapes; the fp32 replay itself is under it."""
+    g = _g(K)
+    M, N = 300, 320
+    x, W, resid = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * K ** -0.5, torch.randn(M, N, generator=g)
+    kw = dict(epi=lr.EPI_RESIDUAL, resid=resid)
+    ref, ref32 = lr.linear_ref(x, W, BF16, dt=F64, **kw), lr.linear_ref(x, W, BF16, dt=F32, **kw)
+    err, bar = _parity_judge(lr.linear_ref(x, W, BF16, dt=F32, drop_last_chunk=True, **kw), ref, ref32)
+    assert err > bar, (K, err, bar)
+    err, bar = _parity_judge(ref32, ref, ref32)
+    assert err <= bar
+
+
+@pytest.mark.parametrize("N", LN_NS)
+def test_the_handover_condition_rejects_the_uncentred_variance(N):
+    """var = mean(y^2) - mean^2 in fp32 on the hostile rows is over the LayerNorm hand-over condition (half a bf16 ulp of the value +
+    the bar); the centred two-pass replay, rounded to bf16 as the kernel rounds, is under it."""
+    y, w, b, eps = _ln_case(N)
+    naive = kr.bf16_round(lr.ln_handover_naive32(y, w, b, eps))
+    worst, e_ref, bar = lr.ln_handover_excess(naive, y, w, b, eps)
+    print(f"HANDOVER N={N}: uncentred excess {worst:.3e} E_ref {e_ref:.3e} bar {bar:.3e}")
+    assert worst > bar, (N, worst, bar)
+    centred = kr.bf16_round(lr.ln_handover_ref(y, w, b, eps, F32))
+    worst, _, bar = lr.ln_handover_excess(centred, y, w, b, eps)
+    print(f"HANDOVER N={N}: centred excess {worst:.3e} bar {bar:.3e}")
+    assert worst <= bar, (N, worst, bar)
+    assert torch.equal(centred[2], kr.bf16_round(b))

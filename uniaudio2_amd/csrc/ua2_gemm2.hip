@@ -604,11 +604,12 @@ __global__ __launch_bounds__(256) void gemm2_tail_combine_kernel(const ua2_linea
 // out_scale (.) (sum of the slabs in index order + bias), stored, and RNE_bf16(LayerNorm(y) * w + b) written in fragment order (the
 // DiT's o-projection / FF2: the prep launch of FF1 / the next block's q|k|v disappears).  slabs == 0: y is already complete (no K split,
 // or a tail split): the LayerNorm pass alone.  A WORKGROUP per row — one 4-column piece per thread, N / 4 threads rounded up to whole
-// waves, statistics through LDS; norm_stat / norm_apply's formulas.  (A wave per row, six pieces per lane, was measured first: 14 us
+// waves, statistics through LDS; norm_stat_centred / norm_apply's formulas (the two-pass centred variance: the row piece stays in
+// registers, so the second pass costs a reduction and no memory traffic).  (A wave per row, six pieces per lane, was measured first: 14 us
 // for 1000 rows against ~5.5 — each of a row's steps is a memory round trip (the slabs were written by other XCDs' workgroups: every
 // load misses this XCD's L2) and with one wave per SIMD nothing overlapped them: DiT step 5.17 vs 4.89 ms, profiles/r6_notes.md §6.)
 __global__ __launch_bounds__(512) void gemm2_combine_ln_row_kernel(const ua2_linear_args a, const int slabs) {
-  __shared__ float red_s[2][8];
+  __shared__ float red_s[3][8];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const int n = 4 * tid;
   const bool live = n < a.N;
@@ -645,21 +646,33 @@ __global__ __launch_bounds__(512) void gemm2_combine_ln_row_kernel(const ua2_lin
   const float4 w = *reinterpret_cast<const float4*>(a.y_ln_w + nc);
   float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
   if (a.y_ln_b) b = *reinterpret_cast<const float4*>(a.y_ln_b + nc);
-  float sm = sum4(0.f, t), ss = sumsq4(0.f, t);
+  // two passes over the row piece in registers (ua2_linear_common.h norm_stat_centred): the sum gives the mean; the second pass gives
+  // the CENTRED sum of squares and sum(t - mean), the fp32 sum's rounding error in the mean, carried as mean_lo.  mean(y^2) - mean^2
+  // loses the variance once |mean| >> std: a row of mean 1e3, std 1 came out wrong by 7e-2 of its scale at N = 1536.
+  float sm = sum4(0.f, t);
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { sm += __shfl_xor(sm, o); ss += __shfl_xor(ss, o); }
-  if (lane == 0) { red_s[0][wave] = sm; red_s[1][wave] = ss; }
+  for (int o = 32; o >= 1; o >>= 1) sm += __shfl_xor(sm, o);
+  if (lane == 0) red_s[0][wave] = sm;
   __syncthreads();
-  sm = 0.f; ss = 0.f;
-  for (int i = 0; i < nw; ++i) { sm += red_s[0][i]; ss += red_s[1][i]; }       // every thread, wave order
+  sm = 0.f;
+  for (int i = 0; i < nw; ++i) sm += red_s[0][i];                               // every thread, wave order
   const float mean = sm / (float)a.N;
-  const float rstd = 1.0f / sqrtf(fmaxf(__fsub_rn(ss / (float)a.N, __fmul_rn(mean, mean)), 0.f) + a.y_ln_eps);
+  float cs = 0.f, sd = 0.f;
+  if (live) centred4(cs, sd, t, mean);                                          // (a dead lane holds t = 0: its t - mean is not part of the row)
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
+  if (lane == 0) { red_s[1][wave] = cs; red_s[2][wave] = sd; }
+  __syncthreads();
+  cs = 0.f; sd = 0.f;
+  for (int i = 0; i < nw; ++i) { cs += red_s[1][i]; sd += red_s[2][i]; }
+  const float mean_lo = sd / (float)a.N;
+  const float rstd = 1.0f / sqrtf(fmaxf(__fsub_rn(cs / (float)a.N, __fmul_rn(mean_lo, mean_lo)), 0.f) + a.y_ln_eps);
   if (!live) return;
   float4 o4;
-  o4.x = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(t.x, mean), rstd), w.x), b.x);
-  o4.y = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(t.y, mean), rstd), w.y), b.y);
-  o4.z = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(t.z, mean), rstd), w.z), b.z);
-  o4.w = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(t.w, mean), rstd), w.w), b.w);
+  o4.x = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fsub_rn(t.x, mean), mean_lo), rstd), w.x), b.x);
+  o4.y = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fsub_rn(t.y, mean), mean_lo), rstd), w.y), b.y);
+  o4.z = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fsub_rn(t.z, mean), mean_lo), rstd), w.z), b.z);
+  o4.w = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(__fsub_rn(t.w, mean), mean_lo), rstd), w.w), b.w);
   store_packed4<UA2_BF16>(a.y_packed, m, n, a.N / 32, o4);
 }
 
