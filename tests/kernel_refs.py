@@ -1,10 +1,13 @@
-"""Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py and tests/test_gpu_rowwise.py.
+"""Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py, tests/test_gpu_attn_flash_parity.py and
+tests/test_gpu_rowwise.py.
 
 Every helper takes `dt`: torch.float64 is the reference a kernel is compared with; torch.float32 evaluates the SAME formula in
 plain fp32 on the host, whose error against the float64 result (`E_ref`) sizes the bar of a tolerance test:
 bar = max(4 * E_ref, 8 * 2^-24 * scale) (two legal fp32 summation orders differ by about twice the single-order error, and the
 kernels' exp / tanh / rsqrt are good to 1-2 ulp; the floor because E_ref can be exactly 0 on short rows).
 tests/test_kernel_refs.py pins each helper to the torch library function it restates (CPU, float64, rtol 1e-12).
+attn_flash_model is no reference but a host model of the MFMA flash form's arithmetic contract (16-bit or bf16 q and weights,
+blocked online softmax): its error against attn_ref sizes the flash bars, which a plain fp32 evaluation would set ~10x too tight.
 All helpers are vectorised over rows and heads."""
 import math
 
@@ -218,6 +221,175 @@ def dwconv_ref(x, w, bias=None, *, stride=1, dilation=1, pad_left=0, Tout=None, 
     return y
 
 
+# ---- the flash (prefill / dense) form: a host model of its arithmetic contract, hostile inputs, the packed layout ---------------
+
 def bf16_round(x):
     """RNE to bf16 of an fp32 tensor, as fp32."""
     return x.float().to(torch.bfloat16).float()
+
+
+def bf16_once(x):
+    """RNE to bf16, returned in the dtype it came in."""
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def split16_round(x):
+    """hi = bf16(x), lo = bf16(x - hi); the value used is hi + lo (16 significant bits)."""
+    hi = bf16_once(x)
+    return hi + bf16_once(x - hi)
+
+
+ROUNDERS = {"split": split16_round, "bf16": bf16_once, "fp32": lambda x: x}
+
+
+def causal_visible(key, pos):
+    return key <= pos
+
+
+def attn_flash_model(q, K, V, pos, seq, n_head, n_kv, mode, keys_per_step=64, score_dt=torch.float32, dt=torch.float32,
+                     visible=causal_visible):
+    """The arithmetic contract of attn_flash_kernel (header comment in csrc/ua2_attn.hip), nothing of its lane layout:
+    q * log2(e) / sqrt(hs) in fp32, rounded by `mode` ("split": 16 significant bits as bf16 hi + lo; "bf16": one bf16; "fp32":
+    left alone); scores accumulated in `score_dt` and handed on in `dt`; keys visited in steps of `keys_per_step` with the running
+    max / alpha / l recurrence on exp2; masked keys contribute exact zeros; l sums the unrounded weights; the weights entering
+    P V are rounded by `mode`; O accumulates in `dt`.  dt = score_dt = float64 with mode "fp32" is attn_ref in another order.
+    mode may be a pair (q rounder, p rounder) of names or callables, and `visible(key, pos)` another mask: the hooks with which
+    tests/test_kernel_refs.py builds deliberately wrong models."""
+    rq, rp = (mode, mode) if isinstance(mode, str) else mode
+    rq, rp = ROUNDERS.get(rq, rq) if isinstance(rq, str) else rq, ROUNDERS.get(rp, rp) if isinstance(rp, str) else rp
+    q = torch.as_tensor(q).to(dt)
+    pos, seq = np.asarray(pos, dtype=np.int64), np.asarray(seq, dtype=np.int64)
+    R, G = q.shape[0], n_head // n_kv
+    hs = q.shape[1] // n_head
+    sc = torch.tensor(1.44269504088896340736, dtype=dt) / torch.sqrt(torch.tensor(float(hs), dtype=dt))
+    qs = rq(q * sc)
+    ninf = float("-inf")
+    out = torch.zeros(R, n_head * hs, dtype=dt)
+    for b in np.unique(seq):
+        rows = np.nonzero(seq == b)[0]
+        p = torch.from_numpy(pos[rows])
+        n = int(p.max()) + 1
+        Kb, Vb = K[b][:n], V[b][:n]
+        Vb = torch.where(torch.isnan(Vb), torch.zeros_like(Vb), Vb).to(dt)
+        qb = qs[rows].view(len(rows), n_kv, G, hs)
+        s_all = torch.einsum("rkgd,lkd->rkgl", qb.to(score_dt), Kb.to(score_dt)).to(dt)
+        vis = visible(torch.arange(n)[None, :], p[:, None])                               # [r, n]
+        assert not bool(torch.isnan(torch.where(vis[:, None, None, :], s_all, torch.zeros_like(s_all))).any()), "a visible key is not stored"
+        s_all = s_all.masked_fill(~vis[:, None, None, :], ninf)
+        m = torch.full(s_all.shape[:3], ninf, dtype=dt)
+        l = torch.zeros_like(m)
+        o = torch.zeros(*m.shape, hs, dtype=dt)
+        for k0 in range(0, n, keys_per_step):
+            s = s_all[..., k0:k0 + keys_per_step]
+            m_new = torch.maximum(m, s.amax(-1))
+            dead = m_new == ninf
+            alpha = torch.where(dead, torch.ones_like(m), torch.exp2(m - torch.where(dead, torch.zeros_like(m), m_new)))
+            pv = torch.where(s == ninf, torch.zeros_like(s), torch.exp2(s - torch.where(dead, torch.zeros_like(m), m_new)[..., None]))
+            l = l * alpha + pv.sum(-1)
+            o = o * alpha[..., None] + torch.einsum("rkgl,lkd->rkgd", rp(pv), Vb[k0:k0 + keys_per_step])
+            m = m_new
+        out[rows] = (o * (1.0 / l)[..., None]).reshape(len(rows), n_head * hs)
+    return out
+
+
+def rel_row_err(y, ref):
+    """max |y - ref| relative to each row's max magnitude; an unwritten (NaN) or non-finite element is an error of inf."""
+    y = y.detach().cpu().to(F64)
+    if not bool(torch.isfinite(y).all()):
+        return float("inf")
+    scale = ref.abs().amax(dim=1, keepdim=True).clamp_min(1e-30)
+    return float(((y - ref).abs() / scale).max())
+
+
+def abs_err(y, ref):
+    y = y.detach().cpu().to(F64)
+    return float((y - ref).abs().max()) if bool(torch.isfinite(y).all()) else float("inf")
+
+
+HOSTILE_LENS = [3, 40, 130, 300]
+HOSTILE_KINDS = ["peaked_q", "dominant_key-k128", "dominant_key-k63", "dominant_key-k64", "dominant_key-last", "wide_v", "equal_keys",
+                 "rising_max", "falling_max"]
+RAMP = 140.0          # span of the rising / falling score ramp in natural units (202 in log2 units: past the underflow of exp2)
+
+
+def all_rows(lens, seed=None, dense=False):
+    """(pos, seq) int32: one query row per position of every sequence (dense: every row at the last position), shuffled by `seed`."""
+    pos = np.concatenate([np.full(L, L - 1) if dense else np.arange(L) for L in lens]).astype(np.int32)
+    seq = np.concatenate([np.full(L, b) for b, L in enumerate(lens)]).astype(np.int32)
+    if seed is not None:
+        perm = np.random.default_rng(seed).permutation(len(pos))
+        pos, seq = pos[perm], seq[perm]
+    return pos, seq
+
+
+def hostile_inputs(kind, n_head, n_kv, hs, lens=HOSTILE_LENS, seed=13):
+    """Hostile but finite inputs (K, V per sequence as drawn, q, pos, seq), every position a query row.  peaked_q: q x 8 (scores of
+    +-100); dominant_key-<where>: one key x 10 at position 128 (slot 0 of a block and of a pair of blocks), 63, 64 (each clamped
+    to the sequence) or the last position; wide_v: V entries of +-1e4 next to 1e-4; equal_keys: runs of four identical keys (ties
+    in the running max); rising_max / falling_max: a common direction d added to q and d * linspace(0, c, L) (reversed: c .. 0) to
+    the keys, c = RAMP / sqrt(hs): the block maximum rises at every step and rescales everything accumulated so far towards
+    zero / the maximum sits in block 0 and the later weights run down past the underflow of exp2."""
+    g = torch.Generator().manual_seed(seed)
+    K = [torch.randn(L, n_kv, hs, generator=g) for L in lens]
+    V = [torch.randn(L, n_kv, hs, generator=g) for L in lens]
+    pos, seq = all_rows(lens, seed=4)
+    q = torch.randn(len(pos), n_head * hs, generator=g)
+    if kind == "peaked_q":
+        q = q * 8.0
+    elif kind.startswith("dominant_key"):
+        where = kind.split("-")[1]
+        for k in K:
+            k[len(k) - 1 if where == "last" else min(int(where[1:]), len(k) - 1)] *= 10.0
+    elif kind == "wide_v":
+        for v in V:
+            mag = torch.where(torch.rand(v.shape, generator=g) < 0.5, torch.tensor(1e4), torch.tensor(1e-4))
+            v.copy_(torch.sign(v) * mag)
+    elif kind == "equal_keys":
+        for k in K:
+            k[1:] = k[1:][(torch.arange(len(k) - 1) // 4) * 4 % max(len(k) - 1, 1)]
+    elif kind in ("rising_max", "falling_max"):
+        d = torch.where(torch.rand(hs, generator=g) < 0.5, -1.0, 1.0)
+        q = (q.view(-1, n_head, hs) + d).reshape(-1, n_head * hs)
+        for k in K:
+            t = torch.linspace(0.0, RAMP / math.sqrt(hs), len(k))
+            k += (t.flip(0) if kind == "falling_max" else t)[:, None, None] * d
+    else:
+        raise ValueError(kind)
+    return K, V, q, pos, seq
+
+
+def packed_index(m, k, K, dtype):
+    """Element (row m, column k) of an [M, K] operand in ua2_linear's operand order [ceil(M/16)][K / KC][64 lanes][EPL]
+    (csrc/ua2_common.h store_packed_operand): k = c * KC + g * EPL + e lies at (((m >> 4) * (K / KC) + c) * 64 + g * 16 + (m & 15)) * EPL + e."""
+    KC, EPL = (32, 8) if dtype == torch.bfloat16 else (16, 4)
+    c, r = k // KC, k % KC
+    g, e = r // EPL, r % EPL
+    return (((m >> 4) * (K // KC) + c) * 64 + g * 16 + (m & 15)) * EPL + e
+
+
+def decode_packed(pk, R, K, dtype):
+    """The first R rows [R, K] of a packed operand (the same layout as packed_index, written as a view)."""
+    KC, EPL = (32, 8) if dtype == torch.bfloat16 else (16, 4)
+    t = pk.view(-1, K // KC, KC // EPL, 16, EPL)                      # [tile, c, g, m & 15, e]
+    return t.permute(0, 3, 1, 2, 4).reshape(-1, K)[:R]
+
+
+def encode_packed(y, dtype, fill, index=packed_index):
+    """Host image of a packed operand: the rows of y [R, K] rounded to `dtype` at index(m, k, K, dtype), `fill` elsewhere."""
+    R, K = y.shape
+    pk = torch.full(((R + 15) // 16 * 16 * K,), fill, dtype=dtype)
+    m, k = torch.meshgrid(torch.arange(R), torch.arange(K), indexing="ij")
+    pk[index(m, k, K, dtype).reshape(-1)] = y.to(dtype).reshape(-1)
+    return pk
+
+
+def packed_mismatch(pk, y, R, K, dtype, fill):
+    """Why a packed buffer is not (the R rows of y rounded RNE to `dtype`, bit for bit, then rows of `fill`); None if it is."""
+    bits = lambda t: t.contiguous().view(torch.int16 if dtype == torch.bfloat16 else torch.int32)
+    pk, y = pk.detach().cpu(), y.detach().cpu()
+    full = decode_packed(pk, (R + 15) // 16 * 16, K, dtype)
+    if not torch.equal(bits(full[:R]), bits(y.to(dtype))):
+        return "a live element differs from the row-major output"
+    if not torch.equal(bits(full[R:]), bits(torch.full_like(full[R:], fill))):
+        return "a row beyond R was written"
+    return None

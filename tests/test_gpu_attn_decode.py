@@ -195,12 +195,7 @@ def test_row_bits_do_not_depend_on_the_launch(dtype, nh, nkv, hs):
     assert _abs_err(y_all, dev.ref(q, pos, seq)) < BAR
 
 
-def _decode_packed(pk, R, K, dtype):
-    """ua2_linear's operand order [ceil(R/16)][K / KC][64 lanes][EPL]: element (m, k), k = c * KC + g * EPL + e, lies at
-    (((m >> 4) * (K / KC) + c) * 64 + g * 16 + (m & 15)) * EPL + e (csrc/ua2_common.h store_packed_operand)."""
-    KC, EPL = (32, 8) if dtype == torch.bfloat16 else (16, 4)
-    t = pk.view((R + 15) // 16, K // KC, KC // EPL, 16, EPL)          # [tile, c, g, m & 15, e]
-    return t.permute(0, 3, 1, 2, 4).reshape(-1, K)[:R]
+_decode_packed = kr.decode_packed          # one layout formula for this file and tests/test_gpu_attn_flash_parity.py
 
 
 @pytest.mark.parametrize("nh,nkv,hs", [(24, 8, 128), (4, 2, 32), (32, 8, 64)])

@@ -172,7 +172,7 @@ def test_large_m_qkv_rope_cache_write_identical(dtype, nh, nkv, hs, C, linear_mo
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("nh,nkv,hs", [(32, 8, 64), (4, 2, 32), (8, 4, 128)])
+@pytest.mark.parametrize("nh,nkv,hs", [(32, 8, 64), (4, 2, 32), (8, 4, 128), (24, 8, 128), (40, 8, 64)])   # the last two: a second, partial head pass
 def test_local_attention_and_its_fusion_into_the_o_projection(dtype, nh, nkv, hs):
     """ua2_attn_local against a torch fp32 softmax(q k^T / sqrt(hs)) v on the cache contents, and the decode
     kernel's UA2_PRO_LOCAL_ATTN prologue (M = 1) against ua2_attn_local + UA2_PRO_CAST: same bits, so a sequence

@@ -1,4 +1,7 @@
-"""The float64 references of tests/kernel_refs.py against the torch library functions they restate (CPU, float64, rtol 1e-12)."""
+"""The float64 references of tests/kernel_refs.py against the torch library functions they restate (CPU, float64, rtol 1e-12); the
+host model of the flash attention contract against attn_ref; the conditions every hostile input generator must meet; and a dry
+run in which deliberately wrong host models stand in for the device result of tests/test_gpu_attn_flash_parity.py and must
+fail its assertions."""
 import numpy as np
 import pytest
 import torch
@@ -138,3 +141,147 @@ def test_argmax_partials_and_fp32_replays():
     assert got.dtype == np.float32
     np.testing.assert_array_equal(got, np.float32(l1.numpy()) + (np.float32(l0.numpy()) - np.float32(l1.numpy())) * np.float32(3.0))
     assert kr.bar(0.0) == 8 * 2.0 ** -24 and kr.bar(1e-3) == 4e-3
+
+
+# ---- the host model of the flash contract (kernel_refs.attn_flash_model) ----------------------------------------------------------
+
+FLASH_BAR, FLASH_BAR_QP, FLOOR = 2e-4, 1e-2, 8.0 * 2.0 ** -24          # the bars of tests/test_gpu_attn_flash_parity.py
+
+
+def _stored(lens, nkv, hs, K=None, V=None, seed=2):
+    c = kr.PagedCache(lens, nkv, hs, torch.bfloat16, seed=seed, K=K, V=V, fill=3.0e4, extra_pages=2)
+    KV = [c.stored_seq(b) for b in range(len(lens))]
+    return [k for k, _ in KV], [v for _, v in KV]
+
+
+_RANDN = {}
+
+
+def _randn_case(nh, nkv, hs):
+    """300 causal rows over 300 keys (+ a short sequence): inputs, float64 reference, and the model error per (mode, keys per step)."""
+    if (nh, nkv, hs) not in _RANDN:
+        lens = [300, 70]
+        K, V = _stored(lens, nkv, hs)
+        pos, seq = kr.all_rows(lens, seed=1)
+        q = torch.randn(len(pos), nh * hs, generator=torch.Generator().manual_seed(hs))
+        ref = kr.attn_ref(q, K, V, pos, seq, nh, nkv)
+        out = {(m, kps): kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, m, kps) for m in ("fp32", "split", "bf16") for kps in (64, 128)}
+        _RANDN[(nh, nkv, hs)] = (q, K, V, pos, seq, ref, out)
+    return _RANDN[(nh, nkv, hs)]
+
+
+@pytest.mark.parametrize("nh,nkv,hs", [(4, 4, 32), (8, 2, 64), (6, 2, 128)])
+def test_flash_model_vs_attn_ref(nh, nkv, hs):
+    q, K, V, pos, seq, ref, out = _randn_case(nh, nkv, hs)
+    # fp32 end to end: fp32 noise, sized by the plain fp32 evaluation of the reference formula
+    e_ref = kr.rel_row_err(kr.attn_ref(q, K, V, pos, seq, nh, nkv, dt=torch.float32), ref)
+    E = {key: kr.rel_row_err(y, ref) for key, y in out.items()}
+    assert E[("fp32", 64)] <= kr.bar(e_ref) and E[("fp32", 128)] <= kr.bar(e_ref)
+    # float64 end to end: the reference itself in another order, whatever the step
+    for kps in (7, 64, 128):
+        _close(kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, "fp32", kps, F64, dt=F64), ref)
+    # the three grades are ordered, and both step sizes stay inside the bar the device test applies to that grade
+    for kps in (64, 128):
+        assert E[("fp32", kps)] < E[("split", kps)] < E[("bf16", kps)]
+        assert kr.abs_err(out[("split", kps)], ref) < FLASH_BAR and kr.abs_err(out[("bf16", kps)], ref) < FLASH_BAR_QP
+        assert kr.abs_err(out[("fp32", kps)], ref) < FLASH_BAR
+
+
+@pytest.mark.parametrize("kind", kr.HOSTILE_KINDS)
+@pytest.mark.parametrize("nh,nkv,hs", [(24, 8, 128), (8, 2, 64), (4, 4, 32), (24, 24, 64)])
+def test_hostile_inputs_are_finite_and_keep_the_bar_narrow(nh, nkv, hs, kind):
+    """A condition on the inputs: the float64 reference is finite, and the bar 4 * E_model(split) never grows past 1e-3."""
+    K, V, q, pos, seq = kr.hostile_inputs(kind, nh, nkv, hs)
+    assert len(pos) == sum(kr.HOSTILE_LENS) and all(bool(torch.isfinite(t).all()) for t in K + V + [q])
+    K, V = _stored(kr.HOSTILE_LENS, nkv, hs, K, V)
+    ref = kr.attn_ref(q, K, V, pos, seq, nh, nkv)
+    assert bool(torch.isfinite(ref).all())
+    for kps in (64, 128):
+        e = kr.rel_row_err(kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, "split", kps), ref)
+        assert 4.0 * e <= 1e-3, (kps, e)
+
+
+def test_ramp_kinds_drive_the_online_softmax_hard():
+    """rising_max: the running max of the last row rises at every 64-key step, by more than 16 bits at a full step (alpha < 2^-16:
+    what was accumulated so far drops below the 16 significant bits of the weights);
+    falling_max: it is set in step 0 and the weights of the last step are below the underflow of exp2."""
+    nh, nkv, hs = 4, 4, 32
+    for kind in ("rising_max", "falling_max"):
+        K, V, q, pos, seq = kr.hostile_inputs(kind, nh, nkv, hs)
+        K, V = _stored(kr.HOSTILE_LENS, nkv, hs, K, V)
+        r = int(np.nonzero((seq == 3) & (pos == 299))[0][0])
+        s = torch.einsum("hd,lhd->hl", q[r].view(nh, hs).to(F64), K[3]) * (1.4426950408889634 / hs ** 0.5)          # log2 units
+        step_max = torch.stack([s[:, k0:k0 + 64].max(1).values for k0 in range(0, 300, 64)], 1)                      # [head, step]
+        if kind == "rising_max":
+            rise = step_max[:, 1:] - step_max[:, :-1]
+            assert bool((rise[:, :3] > 16).all()) and bool((rise[:, 3] > 8).all())          # the last step holds 44 keys
+        else:
+            assert bool((step_max.argmax(1) == 0).all()) and bool((s[:, 256:].min(1).values - step_max[:, 0] < -126).all())
+
+
+def test_wrong_models_fail_the_flash_assertions():
+    """Dry run of tests/test_gpu_attn_flash_parity.py on the host: the model stands in for the device and passes; a mask off by one
+    key at a block edge and a q whose lo half is dropped in one 32-dim chunk fail the unit-scale bar and the hostile bar; against
+    the bf16 forms the wrong mask fails assertion (a) and the several times narrower (b)."""
+    nh, nkv, hs = 8, 2, 64
+    q, K, V, pos, seq, ref, out = _randn_case(nh, nkv, hs)
+
+    def edge_mask(key, p):                               # the row at the first slot of a key block does not see that slot
+        return (key <= p) & ~((key == p) & (p % 64 == 0) & (p > 0))
+
+    def drop_lo_chunk(x):                                # dims 32 .. 63 of every head: hi only
+        x = kr.split16_round(x).view(-1, nh, hs).clone()
+        x[..., 32:64] = kr.bf16_once(x[..., 32:64])
+        return x.view(-1, nh * hs)
+
+    wrong = {"mask": dict(mode="split", visible=edge_mask), "lo": dict(mode=(drop_lo_chunk, "split"))}
+    assert kr.abs_err(out[("split", 64)], ref) < FLASH_BAR
+    for name, kw in wrong.items():
+        y = kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, kw["mode"], visible=kw.get("visible", kr.causal_visible))
+        assert not kr.abs_err(y, ref) < FLASH_BAR, name
+    # NaN left in an unwritten element fails too
+    y = out[("split", 64)].clone()
+    y[5, 3] = float("nan")
+    assert not kr.abs_err(y, ref) < FLASH_BAR and not kr.rel_row_err(y, ref) <= 1.0
+    # the hostile bar
+    Kh, Vh, qh, ph, sh = kr.hostile_inputs("rising_max", nh, nkv, hs)
+    Kh, Vh = _stored(kr.HOSTILE_LENS, nkv, hs, Kh, Vh)
+    refh = kr.attn_ref(qh, Kh, Vh, ph, sh, nh, nkv)
+    bar = max(4.0 * kr.rel_row_err(kr.attn_flash_model(qh, Kh, Vh, ph, sh, nh, nkv, "split"), refh), FLOOR)
+    assert kr.rel_row_err(kr.attn_flash_model(qh, Kh, Vh, ph, sh, nh, nkv, "split", 128), refh) <= bar
+    for name, kw in wrong.items():
+        y = kr.attn_flash_model(qh, Kh, Vh, ph, sh, nh, nkv, kw["mode"], visible=kw.get("visible", kr.causal_visible))
+        assert not kr.rel_row_err(y, refh) <= bar, name
+    # the bf16 forms: (a) against float64, (b) against the model
+    m32, m64 = out[("bf16", 64)].to(F64), kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, "bf16", 64, F64).to(F64)
+    bar_a, bar_b = 4.0 * kr.rel_row_err(m32, ref), max(4.0 * kr.rel_row_err(m32, m64), FLOOR)
+    assert bar_b < bar_a / 4
+    y = kr.attn_flash_model(q, K, V, pos, seq, nh, nkv, "bf16", visible=edge_mask)
+    assert not kr.rel_row_err(y, ref) <= bar_a and not kr.rel_row_err(y, m32) <= bar_b
+    assert kr.rel_row_err(m64, ref) <= bar_a and kr.rel_row_err(m64, m32) <= bar_b
+    assert not kr.rel_row_err(out[("bf16", 128)], m32) <= FLOOR            # the two step sizes give different bits
+
+
+def test_wrong_packed_index_fails_the_packed_assertion():
+    """packed_index (index arithmetic) and decode_packed (a view) state one layout; an image written with two index factors swapped,
+    or one that writes a row beyond R, is refused."""
+    fill = 12352.0
+    for dtype, K in ((torch.bfloat16, 256), (torch.float32, 48)):
+        R = 37
+        y = torch.randn(R, K, generator=torch.Generator().manual_seed(K))
+        good = kr.encode_packed(y, dtype, fill)
+        assert kr.packed_mismatch(good, y, R, K, dtype, fill) is None
+        assert torch.equal(kr.decode_packed(good, R, K, dtype), y.to(dtype))
+
+        def swapped(m, k, K, dtype):
+            KC, EPL = (32, 8) if dtype == torch.bfloat16 else (16, 4)
+            c, r = k // KC, k % KC
+            return (((m >> 4) * (K // KC) + c) * 64 + (m & 15) * (KC // EPL) + r // EPL) * EPL + r % EPL
+
+        assert kr.packed_mismatch(kr.encode_packed(y, dtype, fill, index=swapped), y, R, K, dtype, fill) is not None
+        beyond = good.clone()
+        beyond[kr.packed_index(torch.tensor(R), torch.tensor(3), K, dtype)] = 1.0
+        assert kr.packed_mismatch(beyond, y, R, K, dtype, fill) == "a row beyond R was written"
+        if dtype == torch.bfloat16:                      # not rounded to nearest: truncated
+            trunc = kr.encode_packed((y.view(torch.int32) & -65536).view(torch.float32), dtype, fill)
+            assert kr.packed_mismatch(trunc, y, R, K, dtype, fill) is not None
