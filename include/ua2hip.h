@@ -340,7 +340,7 @@ int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
  * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "gemv_l13" (the decode kernel on 13-bit images of its bf16 weights: such a launch counts under "gemv" as well), "rsplit" ([v10] the range split
- * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather); -1 for an unknown
+ * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather), "score" (calls of ua2_stage3_score that issued their launches); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
  * call getenv on every launch); a process that changes one of them afterwards (the tests do) calls this to have them read again. */
@@ -442,6 +442,22 @@ int ua2_rmsnorm_blend(int32_t M, int32_t C, const float* x, const float* w, floa
 int ua2_argmax_embed(int dtype, int32_t M, int32_t n_part, const float* part_max, const int32_t* part_idx,
                      int32_t* out_tokens, int32_t out_ld, int32_t out_col,
                      const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, void* stream);
+
+/* [v10, addition] Cross-entropy tail of the teacher-forced pass (model_new.py:402-454 forward, :59-109 CrossEntropyAndAccuracy_*),
+ * over the raw fp32 logits — forbid_prefix, guidance and the arg-max partials are never consulted.  Per row m, with
+ * label = labels[m * label_ld + label_col]:
+ *   nll[m * out_ld + out_col]  = lse(logits[m, :V]) - logits[m, label], the row maximum subtracted before the exponentials; 0 for
+ *                                label == -1 (ignored).  A -inf target gives +inf; a row of -inf, or one that holds a NaN, gives NaN
+ *                                (as F.cross_entropy does);
+ *   pred[m * out_ld + out_col] = the arg-max, lowest index on ties, under the all-NaN rule and the clamp into [0, V) above;
+ *   emb != NULL: emb_out[m, :C] = emb[emb_row0 + label, :] — the gather of ua2_argmax_embed, of the LABEL's row instead of the chosen
+ *                id's (teacher forcing); label == -1 gathers row emb_row0.  The label is clamped into [0, V) before the gather; callers
+ *                reject labels outside [-1, V) on the host.
+ * One workgroup per row and one summation order per row whatever M is: a row's nll bits do not depend on the rows beside it. */
+int ua2_xent_embed(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V,
+                   const int32_t* labels, int32_t label_ld, int32_t label_col,
+                   float* nll, int32_t* pred, int32_t out_ld, int32_t out_col,
+                   const void* emb, int64_t emb_row0, int32_t C, float* emb_out, void* stream);
 
 /* Classifier-free guidance (model_new.py:618-622, 634-637) over `pairs` (conditional, unconditional) pairs of logit rows
  * (rows 2p, 2p + 1 of [2 pairs, ld] fp32; the reference has one pair, batched generation has one per utterance):
@@ -991,6 +1007,18 @@ int32_t ua2_stage3_defer_rows(void);
  * deferred frames, before the ring is written again.  Greedy, unguided plans (top-k = 1, no classifier-free guidance); the logits of a
  * flush are scratch — "text_logits" keeps what the last undeferred frame wrote.  Counted as "text_flush" by ua2_debug_kernel_launches. */
 int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, int32_t n, void* stream);
+/* [v10, addition] Teacher-forced scoring (model_new.py:402-454 forward + the cross-entropies of :59-109) of the R rows the preceding
+ * ua2_stage3_trunk(h, R) ran (R <= max_batch; its h_final is still in the plan's buffer): lm_head into "text_logits" and the text tail,
+ * then per codebook i the projection of the step's input (h_final at i = 0, the embedding of LABEL i - 1 after that), the local decoder
+ * at position i, audio_head[i] into "audio_logits" and ua2_xent_embed on label column i, which gathers audio_emb[i * va + label] for
+ * step i + 1.  These are the launches ua2_stage3_heads issues on its plain path (same prologues, hand-overs and summation orders; no
+ * riders, per-id tables, arg-max fold, graph, guidance or sampler; forbid_prefix ignored), so on the row-invariant plans a
+ * teacher-forced row carries the bits of the decode frame that saw the same ids.  Every row runs the local decoder; rows whose next step
+ * is text pass -1 labels.  labels (device) / nll / pred: [R, n_cb + 1] in the token layout a0 .. a(n_cb-1), text; label -1 = ignored
+ * (nll 0), pred is always written.  Afterwards "text_logits" / "audio_logits" hold the chunk's raw logits.  Touches none of out_tokens,
+ * frame_log, counters, the sampler state, the n-gram history or the beam state; refused while a beam is attached.  Counted as "score" by
+ * ua2_debug_kernel_launches. */
+int ua2_stage3_score(ua2_stage3* h, int32_t R, const int32_t* labels, float* nll, int32_t* pred, void* stream);
 /* Expose intermediate buffers for tests: name in {"h_final","text_logits","audio_logits"}. */
 float* ua2_stage3_buffer(ua2_stage3* h, const char* name);
 

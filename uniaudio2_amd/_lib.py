@@ -213,6 +213,8 @@ _EXPORTS = {
     "ua2_stage3_buffer": (C.POINTER(C.c_float), [vp, C.c_char_p]),
     "ua2_stage3_defer_rows": (i32, []),
     "ua2_stage3_text_flush": (C.c_int, [vp, i32, i32, i32, vp]),
+    "ua2_xent_embed": (C.c_int, [C.c_int, i32, vp, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, i64, i32, vp, vp]),
+    "ua2_stage3_score": (C.c_int, [vp, i32, vp, vp, vp, vp]),
 }
 
 

@@ -1130,6 +1130,60 @@ extern "C" int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, i
   return 0;
 }
 
+// Teacher-forced scoring of the R rows ua2_stage3_trunk has just run (model_new.py:445-453 of forward, with the cross-entropy of
+// :59-109 taken on the device): heads_impl's plain path — no riders, no per-id tables, no arg-max fold, no graph, no guidance, no
+// sampler, forbid_prefix ignored — with ua2_xent_embed as the tail of every head: it scores the label and gathers the LABEL's
+// embedding for the next codebook step.  The launches are built as heads_impl builds them for !tab && !ride (prologues, hand-overs,
+// sum_order), so on the row-invariant plans a teacher-forced row carries the bits of the decode frame that saw the same ids.
+// labels / nll / pred: [R, n_cb + 1] in the token layout (a0 .. a(n_cb-1), text).  Writes none of out_tokens, frame_log, counters, the
+// n-gram history or the beam state.
+extern "C" int ua2_stage3_score(ua2_stage3* h, int32_t R, const int32_t* labels, float* nll, int32_t* pred, void* stream) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_score: NULL handle");
+  UA2_CHECK(R > 0 && R <= h->d.max_batch, "ua2_stage3_score: R=%d out of range (1..max_batch=%d)", R, h->d.max_batch);
+  UA2_CHECK(labels && nll && pred, "ua2_stage3_score: NULL labels / nll / pred");
+  UA2_CHECK(h->beam_W == 0, "ua2_stage3_score: a beam search is attached (ua2_stage3_set_beam); end it first");
+  hipStream_t s = (hipStream_t)stream;
+  const ua2_stage3_desc& d = h->d;
+  const int C = d.backbone.n_embd, Cd = d.decoder.n_embd, w = d.n_cb + 1;
+  const int order = order_free(h, R) ? UA2_SUM_ORDER_FREE : UA2_SUM_ORDER_INVARIANT;
+  const bool scaled = h->scaled || order_free_scaled(h, R);
+  ua2_linear_args a;
+  // text_logits = lm_head(h_final)                                (model_new.py:445)
+  fresh_args(h, a);
+  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
+  a.M = R; a.N = d.vt; a.K = C; a.x = h->hfin; a.ldx = C; a.w0 = d.lm_head; a.y = h->text_logits; a.ldy = d.vt;
+  a.part_max = h->pmax_t; a.part_idx = h->pidx_t; a.sum_order = order;
+  if (int rc = lin(h, a, s)) return rc;
+  if (int rc = ua2_xent_embed(d.dtype, R, h->text_logits, d.vt, d.vt, labels, w, d.n_cb, nll, pred, w, d.n_cb, nullptr, 0, C, nullptr, s)) return rc;
+  const float* curr = h->hfin;
+  for (int i = 0; i < d.n_cb; ++i) {                               // model_new.py:447-453, one codebook position at a time
+    const Handover hod(h, R, Cd);
+    fresh_args(h, a);
+    a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
+    a.M = R; a.N = Cd; a.K = C; a.x = curr; a.ldx = C; a.w0 = d.projection; a.y = h->xd; a.ldy = Cd;
+    if (scaled) hod.produce(a, h->norms[3][0][0]);
+    a.sum_order = order;
+    if (int rc = lin(h, a, s)) return rc;
+    if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, d.n_cb <= 8, false,
+                         scaled ? d.decoder.ln_f : nullptr, scaled)) return rc;
+    fresh_args(h, a);
+    a.dtype = d.dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_STORE;
+    a.M = R; a.N = d.va; a.K = Cd; a.x = h->xd; a.ldx = Cd; a.norm_w = d.decoder.ln_f; a.eps = d.decoder.eps;
+    a.w0 = h->audio_head[i]; a.y = h->audio_logits + (size_t)i * d.va; a.ldy = d.n_cb * d.va;
+    a.part_max = h->pmax_a; a.part_idx = h->pidx_a;
+    if (scaled) hod.consume(a);
+    a.sum_order = order;
+    if (int rc = lin(h, a, s)) return rc;
+    // the last step's gather has no consumer
+    const bool gather = i + 1 < d.n_cb;
+    if (int rc = ua2_xent_embed(d.dtype, R, h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, labels, w, i, nll, pred, w, i,
+                                gather ? d.audio_emb : nullptr, (int64_t)i * d.va, C, gather ? h->curr_h : nullptr, s)) return rc;
+    curr = h->curr_h;
+  }
+  ua2_count_launch(UA2_CNT_SCORE);
+  return 0;
+}
+
 extern "C" float* ua2_stage3_buffer(ua2_stage3* h, const char* name) {
   if (!h || !name) return nullptr;
   if (!strcmp(name, "h_final")) return h->hfin;

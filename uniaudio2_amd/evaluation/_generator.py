@@ -199,6 +199,19 @@ class GeneratorBase:
         return B, L
 
     @torch.inference_mode()
+    def score_continuation(self, tokens, tokens_mask, cont_tokens, cont_mask):
+        """Teacher-forced score of a given continuation under a prompt: tokens / tokens_mask (L, 9) as the prepare_* methods build
+        the prompt, cont_tokens / cont_mask (T, 9) the frames to score (a reference transcript as _text_block lays it out, a
+        reference token file as _audio_block does).  The loss mask covers the continuation only.  Returns Model_stage3.score_sequence's
+        dict for the one sequence: row s of nll / pred (1, L + T - 1, 9) scores frame s + 1, so the continuation's rows are [L - 1:]."""
+        dev = self.device
+        tok = torch.cat([tokens, cont_tokens], dim=0).to(torch.int64).to(dev)
+        msk = torch.cat([tokens_mask, cont_mask], dim=0).bool().to(dev)
+        loss = torch.zeros_like(msk)
+        loss[tokens.shape[0]:] = True
+        return self._model.score_sequence(tok[None], msk[None], loss[None])
+
+    @torch.inference_mode()
     def _generate_audio_tokens(self, tokens, tokens_mask, cfg_tokens=None, cfg_mask=None, topk=1, temperature=1.0,
                                max_audio_frames=500) -> Tuple[torch.Tensor, torch.Tensor]:
         """The loop of generate_tts / generate_audio / generate_LTS (tts_task.py:246-285)."""

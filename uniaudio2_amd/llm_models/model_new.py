@@ -2,7 +2,8 @@
 
 Mirror of the reference's llm_models/model_new.py `Model_stage3` (:334-687) for its inference
 methods: `setup_caches` (:554-565), `reset_caches` (:647-651), `forward_prefix` (:456-507),
-`generate_frame` (:568-645) keep their signatures, the state-dict keys are identical
+`generate_frame` (:568-645) and the teacher-forced `forward` (:402-454, with the cross-entropy helpers of :59-109; `score` is
+the on-device form) keep their signatures, the state-dict keys are identical
 (`backbone.*`, `decoder.*`, `audio_understanding_expert.*`, `audio_generation_expert.*`,
 `audio_embeddings.weight`, `projection.weight`, `audio_head`), so a reference checkpoint loads
 with `load_state_dict`.
@@ -18,6 +19,7 @@ from typing import List, Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import ops
 from .._lib import BeamPool, BeamState, Stage3Desc, W8Entry, check, lib, vp
@@ -83,6 +85,68 @@ def defer_windows(start: int, n_frames: int, R: int, cap_rows: int = DEFER_CAP_R
         stop = min(end, (f // cap_frames + 1) * cap_frames)
         out.append((f, stop - f))
         f = stop
+    return out
+
+
+def CrossEntropyAndAccuracy_text(logits, y, mask, ignore_id=-1):
+    """model_new.py:59-73.  logits (B, T, K), y (B, T), mask (B, T).  Returns (loss, {'acc_text', 'loss_text'}): the per-token
+    cross-entropy (0 where y == ignore_id) and the hits of the arg-max, both summed under `mask` and divided by mask.sum() — a token
+    that is ignored but not masked still counts in the divisor, as in the reference."""
+    y, mask = y.to(logits.device), mask.to(logits.device)
+    K = logits.shape[-1]
+    nll = F.cross_entropy(logits.reshape(-1, K), y.reshape(-1), ignore_index=ignore_id, reduction="none").view(y.shape)
+    n = mask.int().sum()
+    hit = (logits.argmax(-1) == y) & mask.bool()
+    loss = (nll * mask).sum() / n
+    return loss, {"acc_text": hit.int().sum() / n, "loss_text": loss.clone().detach()}
+
+
+def CrossEntropyAndAccuracy_residual(logits, y, loss_mask, loss_weights=[1, 1, 1], ignore_id=None):
+    """model_new.py:75-109.  logits (N, n_cb, K), y (N, n_cb), loss_mask (N, >= n_cb) over the N selected audio steps; one codebook
+    per entry of `loss_weights` (the default scores the first three).  Returns (weighted mean loss, {'acc_i', 'loss_i'}, i from 1).
+    The reference's quirks are kept: the accuracy ignores loss_mask, and both it and the loss divide by N, not by the unmasked count.
+    ignore_id None = no label is ignored (F.cross_entropy's own default id, -100, which no label takes)."""
+    y = y.to(logits.device)
+    ignore = -100 if ignore_id is None else int(ignore_id)
+    N = y.shape[0]
+    acc, losses, total = {}, {}, 0
+    for i, w in enumerate(loss_weights):
+        li, yi = logits[:, i, :], y[:, i]
+        nll = F.cross_entropy(li, yi, ignore_index=ignore, reduction="none") * loss_mask[:, i]
+        acc[f"acc_{i + 1}"] = (li.argmax(1) == yi).int().sum() / N
+        loss_i = nll.sum() / N
+        total = total + loss_i * w
+        losses[f"loss_{i + 1}"] = loss_i.clone().detach()
+    return total / len(loss_weights), {**acc, **losses}
+
+
+def score_stats(nll, pred, lab, step_mask, loss_mask):
+    """Sufficient statistics of the two reference cross-entropy functions over scored rows, float64 on the tensors' device.  nll, pred,
+    lab (..., W) in the token layout (audio streams first, text last), step_mask / loss_mask (..., W) bool: the masks of the steps
+    the rows predict (tokens_mask[:, 1:], loss_mask[:, 1:]).  Per stream: sum_nll (under the loss mask), hits (audio: over every
+    selected row, loss mask ignored — the reference's quirk; text: under the mask), rows (the divisor: audio steps selected by
+    step_mask[..., 0]; text: step_mask & loss_mask of the text stream) and n_tokens (labels that contribute a loss)."""
+    W = nll.shape[-1]
+    n64, hit = nll.double().reshape(-1, W), (pred == lab).reshape(-1, W)
+    tm, lm, lab = step_mask.reshape(-1, W).bool(), loss_mask.reshape(-1, W).bool(), lab.reshape(-1, W)
+    sel = tm[:, :1].expand(-1, W - 1)
+    counted = torch.cat([sel & lm[:, :-1], tm[:, -1:] & lm[:, -1:]], dim=1)            # rows whose loss enters the sum
+    hits_in = torch.cat([sel, counted[:, -1:]], dim=1)
+    rows = torch.cat([sel, counted[:, -1:]], dim=1).sum(0).double()
+    return {"sum_nll": (n64 * counted).sum(0), "hits": (hit & hits_in).sum(0).double(), "rows": rows,
+            "n_tokens": (counted & (lab >= 0)).sum(0).double()}
+
+
+def metrics_from_stats(stats, n_weights=None):
+    """The metric keys of CrossEntropyAndAccuracy_text / _residual (model_new.py:59-109) from score_stats (summed over any number
+    of sequences): acc_text, loss_text, acc_i, loss_i for the first n_weights codebooks (None: all), i from 1."""
+    W = stats["rows"].shape[0]
+    acc, loss = stats["hits"] / stats["rows"], stats["sum_nll"] / stats["rows"]
+    out = {"acc_text": acc[-1], "loss_text": loss[-1]}
+    for i in range(W - 1 if n_weights is None else n_weights):
+        out[f"acc_{i + 1}"] = acc[i]
+    for i in range(W - 1 if n_weights is None else n_weights):
+        out[f"loss_{i + 1}"] = loss[i]
     return out
 
 
@@ -322,6 +386,117 @@ class Model_stage3(nn.Module):
             self._set_groups(ps[s0:s0 + mr], sq[s0:s0 + mr])
             check(lib.ua2_stage3_trunk(self._h, n, ops.stream()), "ua2_stage3_trunk")
         return None
+
+    # ---- teacher-forced scoring (model_new.py:402-454 forward; include/ua2hip.h ua2_stage3_score) ---------------------------------
+    def _teacher_forced(self, tokens, labels, tokens_mask, text_labels, input_pos, sink=None):
+        """The chunk loop shared by score and forward: the B * S rows in time-major order, at most max_batch per chunk, each chunk
+        through ua2_stage3_trunk + ua2_stage3_score.  Returns (nll, pred, lab) as (B, S, W) tensors in the token layout; sink(rows,
+        n), when given, is called after every chunk with the chunk's flat row indices (b * S + s) while the plan's two logits
+        buffers hold that chunk."""
+        self._need()
+        st = self._st
+        if self._beam is not None:
+            raise ValueError("a beam search is running (end_beams): its rows and pages are live in the plan")
+        dev = st["device"]
+        B, S, W = tokens.shape
+        ncb, va, vt = st["ncb"], st["va"], self.backbone.config.padded_vocab_size
+        if W != ncb + 1 or tuple(labels.shape) != (B, S, ncb) or tokens_mask.shape[0] != B or tokens_mask.shape[1] < S + 1:
+            raise ValueError(f"expected tokens (B, S, {ncb + 1}), labels (B, S, {ncb}), tokens_mask (B, S + 1, {ncb + 1}); got "
+                             f"{tuple(tokens.shape)}, {tuple(labels.shape)}, {tuple(tokens_mask.shape)}")
+        if B > st["B"]:
+            raise ValueError(f"setup_caches({st['B']}) is too small for {B} sequences")
+        tokens, labels, tokens_mask = tokens.to(dev), labels.to(dev), tokens_mask.to(dev)
+        if text_labels is None:
+            text_labels = torch.full((B, S), -1, dtype=torch.long, device=dev)
+        text_labels = text_labels.to(dev)
+        if tuple(text_labels.shape) != (B, S):
+            raise ValueError(f"text_labels must be (B, S) = ({B}, {S}), got {tuple(text_labels.shape)}")
+        for name, t, V in (("labels", labels, va), ("text_labels", text_labels, vt)):
+            if t.numel() and (int(t.min().item()) < -1 or int(t.max().item()) >= V):
+                raise ValueError(f"{name} must lie in [-1, {V}) (-1 = ignored); got [{int(t.min().item())}, {int(t.max().item())}]")
+        if input_pos is None:
+            input_pos = torch.arange(S, device=dev).unsqueeze(0).expand(B, S)
+        audio_next = tokens_mask[:, 1:S + 1, 0].bool()                     # rows whose NEXT step is an audio step: the rows the local decoder scores
+        lab = torch.cat([torch.where(audio_next.unsqueeze(-1), labels, torch.full_like(labels, -1)), text_labels.unsqueeze(-1)], dim=-1)
+        seq = torch.arange(B, device=dev).unsqueeze(1).expand(B, S)
+        ps, sq = input_pos.to(dev).reshape(-1), seq.reshape(-1)
+        order = torch.argsort(ps, stable=True)                             # time-major: a chunk only needs K/V of itself and of earlier chunks
+        tk, mk = tokens.reshape(B * S, W)[order], tokens_mask[:, :S].reshape(B * S, W)[order]
+        lb = lab.reshape(B * S, W)[order].to(torch.int32).contiguous()
+        ps, sq = ps[order], sq[order]
+        self._check_positions(int(ps.max().item()))
+        self._check_positions(int(ps.min().item()))
+        R, mb = B * S, st["B"]
+        nll = torch.zeros(R, W, dtype=torch.float32, device=dev)
+        pred = torch.zeros(R, W, dtype=torch.int32, device=dev)
+        s = ops.stream()
+        for s0 in range(0, R, mb):
+            n = self._load_rows(tk[s0:s0 + mb], mk[s0:s0 + mb], ps[s0:s0 + mb], sq[s0:s0 + mb])
+            check(lib.ua2_stage3_trunk(self._h, n, s), "ua2_stage3_trunk")
+            check(lib.ua2_stage3_score(self._h, n, lb[s0:].data_ptr(), nll[s0:].data_ptr(), pred[s0:].data_ptr(), s), "ua2_stage3_score")
+            if sink is not None:
+                sink(order[s0:s0 + n], n)
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(R, device=dev)
+        nll, pred = nll[inv].view(B, S, W), pred[inv].view(B, S, W)
+        nll[..., :ncb] = torch.where(audio_next.unsqueeze(-1), nll[..., :ncb], torch.zeros_like(nll[..., :ncb]))
+        pred[..., :ncb] = torch.where(audio_next.unsqueeze(-1), pred[..., :ncb], torch.full_like(pred[..., :ncb], -1))
+        return nll, pred, lab
+
+    @torch.inference_mode()
+    def score(self, tokens: torch.Tensor, labels: torch.Tensor, tokens_mask: torch.Tensor, loss_mask: torch.Tensor = None,
+              text_labels: torch.Tensor = None, input_pos=None, loss_weights=None):
+        """Teacher-forced scoring on the device: what model_new.py:402-454 `forward` computes, reduced to per-token losses by the
+        cross-entropy tail (ua2_xent_embed) — no logits leave the plan.  Shapes as forward: tokens (B, S, 9), labels (B, S, 8) audio
+        only, tokens_mask and loss_mask (B, S + 1, 9) (loss_mask None: ones); text_labels (B, S), -1 = ignored (default: all -1).
+        Labels outside [-1, V) raise ValueError before any launch.  The B * S rows run time-major in chunks of at most max_batch
+        rows (ua2_stage3_trunk + ua2_stage3_score per chunk), in the decode frame's launch forms, so on the default plans a row's
+        bits depend neither on the batch nor on the chunking.  Needs setup_caches (B <= max_batch_size); overwrites the K/V
+        positions it visits and the decode state's rows, so it must not be called in the middle of a generation.
+        Returns dict(nll (B, S, 9) fp32, pred (B, S, 9) int32, metrics): token layout (audio streams first, text last); the audio
+        streams of rows with tokens_mask[:, 1:, 0] == 0 hold 0 / -1.  metrics: the keys of CrossEntropyAndAccuracy_text (mask =
+        tokens_mask[:, 1:, -1] & loss_mask[:, 1:, -1]) and CrossEntropyAndAccuracy_residual (over the rows tokens_mask[:, 1:, 0]
+        selects, loss_weights = ones(n_cb) unless given), reduced on the device in float64 from nll / pred by the reference's formulas."""
+        nll, pred, lab = self._teacher_forced(tokens, labels, tokens_mask, text_labels, input_pos)
+        S = nll.shape[1]
+        tm = tokens_mask.to(nll.device)[:, 1:S + 1].bool()
+        lm = torch.ones_like(tm) if loss_mask is None else loss_mask.to(nll.device)[:, 1:S + 1].bool()
+        metrics = metrics_from_stats(score_stats(nll, pred, lab, tm, lm), None if loss_weights is None else len(loss_weights))
+        return {"nll": nll, "pred": pred, "metrics": metrics}
+
+    @torch.inference_mode()
+    def score_sequence(self, tokens: torch.Tensor, mask: torch.Tensor, loss_mask: torch.Tensor = None, loss_weights=None):
+        """score of whole sequences: tokens (B, L, 9), mask (B, L, 9), loss_mask (B, L, 9) or None.  Step t predicts step t + 1:
+        tokens[:, :-1] go in, labels = tokens[:, 1:, :-1], text_labels = tokens[:, 1:, -1] where mask[:, 1:, -1], else -1.  The
+        result's row s scores the tokens of step s + 1."""
+        text_labels = torch.where(mask[:, 1:, -1].bool(), tokens[:, 1:, -1], torch.full_like(tokens[:, 1:, -1], -1))
+        return self.score(tokens[:, :-1], tokens[:, 1:, :-1], mask, loss_mask, text_labels=text_labels, loss_weights=loss_weights)
+
+    @torch.inference_mode()
+    def forward(self, tokens: torch.Tensor, labels: torch.Tensor, tokens_mask: torch.Tensor, loss_mask: torch.Tensor,
+                input_pos=None, input_pos_maxp1=None):
+        """model_new.py:402-454: returns (text_logits (B, S, Vt), ci_logits (N, 8, Va), choosed_label, choosed_mask) with the N audio
+        steps in the reference's row order (tokens_mask[:, 1:, 0].bool() indexing).  Assembled chunk by chunk from the plan's two
+        logits buffers behind the launches of `score`.  Departures from the reference: it needs setup_caches; it overwrites the K/V
+        positions it visits (and the decode state's rows), so it must not be called in the middle of a generation; it materialises
+        the logits (B * S * Vt floats), so it is meant for parity checks and small inputs — `score` is the form for corpora.
+        Inference only (no gradients)."""
+        self._need()
+        st = self._st
+        dev = st["device"]
+        B, S, W = tokens.shape
+        ncb, va, vt = st["ncb"], st["va"], self.backbone.config.padded_vocab_size
+        text_all = torch.empty(B * S, vt, dtype=torch.float32, device=dev)
+        audio_all = torch.empty(B * S, ncb, va, dtype=torch.float32, device=dev)
+
+        def sink(rows, n):
+            text_all[rows] = self.buffer("text_logits", n)
+            audio_all[rows] = self.buffer("audio_logits", n)
+
+        self._teacher_forced(tokens, labels, tokens_mask, None, input_pos, sink=sink)
+        sel = tokens_mask.to(dev)[:, 1:S + 1, 0].bool()
+        return (text_all.view(B, S, vt), audio_all.view(B, S, ncb, va)[sel], labels.to(dev)[sel],
+                loss_mask.to(dev)[:, 1:S + 1, :][sel])
 
     @torch.inference_mode()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor,
