@@ -171,6 +171,47 @@ def test_two_calls_back_to_back_equal_one(golden, sd, dtype):
     assert torch.equal(torch.cat([a, b]), one) and int((one[:, :, 0] < 0).sum()) == 0
 
 
+@gpu
+def test_recorded_frames_replay_until_the_environment_is_refreshed(golden, sd):
+    """The executor's graph cache (ua2_stage3.hip FrameKey / drop_graphs).  Captured frames count their launches at capture only, so the
+    rise of a family counter over a call says whether a frame was recorded or replayed: a frame is recorded once per key, replayed
+    after that, and recorded again after ua2_debug_refresh_env (the launch-time knobs are baked into it) — with the ids of the ungraphed
+    path throughout.  The guidance scale is part of the key: another scale records another frame, the first one's stays."""
+    from uniaudio2_amd._lib import lib
+    d, _ = golden
+
+    def frames(m, n, B=1, mode=0, use_graph=True):
+        n0 = lib.ua2_debug_kernel_launches(b"gemv")
+        log = m.generate_frames(n, B, mode, reason_eos=-1, reason_card=RC, use_graph=use_graph, defer_text_head=False).cpu().clone()
+        return log, lib.ua2_debug_kernel_launches(b"gemv") - n0
+
+    _, tokens, mask = _prompt(d, 1)
+    m = build_product_model(sd, torch.bfloat16, batch=1)
+    _start(m, tokens, mask)
+    a, per_frame = frames(m, 2)
+    assert per_frame > 0                                           # recorded once; the call's second frame replayed it
+    b, n = frames(m, 1)
+    assert n == 0                                                  # replayed
+    _refresh()                                                     # the environment itself is unchanged
+    c, n = frames(m, 1)
+    assert n == per_frame                                          # recorded again
+    ref = build_product_model(sd, torch.bfloat16, batch=1)
+    _start(ref, tokens, mask)
+    assert torch.equal(torch.cat([a, b, c]), frames(ref, 4, use_graph=False)[0])
+
+    _, tokens, mask = _prompt(d, 2)
+    m = build_product_model(sd, torch.bfloat16, batch=2)
+    _start(m, tokens, mask, mode=2, cfg=2.0)
+    per_frame = frames(m, 2, 2, 2)[1]
+    assert per_frame > 0
+    m.set_cfg(2.0)
+    assert frames(m, 1, 2, 2)[1] == 0                              # the same scale: the same key
+    m.set_cfg(1.5)
+    assert frames(m, 1, 2, 2)[1] == per_frame                      # another scale: recorded anew
+    m.set_cfg(2.0)
+    assert frames(m, 1, 2, 2)[1] == 0                              # ... and the first frame is still there
+
+
 @pytest.fixture(scope="module")
 def full_model():
     import bench

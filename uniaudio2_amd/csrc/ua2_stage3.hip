@@ -17,6 +17,16 @@
 #include "ua2_common.h"
 #include "ua2_linear_common.h"
 
+namespace {
+// What a recorded frame bakes in beyond the plan's own state (the setters drop the graphs with theirs).  mode: without its flag bits;
+// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only
+struct FrameKey {
+  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits;
+  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits); }
+  bool operator<(const FrameKey& o) const { return tied() < o.tied(); }
+};
+}  // namespace
+
 struct ua2_stage3 {
   ua2_stage3_desc d;
   // deep copies of the per-layer pointer arrays
@@ -96,12 +106,26 @@ struct ua2_stage3 {
   void* l13_mem = nullptr;
   bool lossless = false;
   ua2_lossless_info l13_info{};
-  std::map<std::tuple<int, int, int, int, int, int, int>, hipGraphExec_t> graphs;
+  std::map<FrameKey, hipGraphExec_t> graphs;
+  int env_gen = 0;             // g_ua2_env_gen the graphs were captured under: the launch-time knobs are baked into them (ua2_stage3_frame)
 };
 
 namespace {
 
 size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
+void drop_graphs(ua2_stage3* h) {   // the only code that destroys recorded frames: they bake the kernel choice, the weight pointers and every launch argument
+  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
+  h->graphs.clear();
+}
+// Launch-time knobs (A/B hooks): read once and again after ua2_debug_refresh_env, which also makes ua2_stage3_frame re-capture.
+Ua2EnvInt g_l13_all{"UA2_L13_ALL", 0}, g_of_scaled{"UA2_OF_SCALED", 0}, g_no_scaled{"UA2_NO_SCALED", 0}, g_no_local_fuse{"UA2_NO_LOCAL_FUSE", 0} /* profiles/r1_notes.md */,
+    g_no_packed_handover{"UA2_NO_PACKED_HANDOVER", 0}, g_defer_rows{"UA2_DEFER_ROWS", UA2_DEFER_CAP_ROWS}, g_no_defer{"UA2_NO_DEFER_TEXT_HEAD", 0};
+// Creation-time knobs: read from the environment when a plan is sized and created, so one process can hold plans of both forms.
+struct PlanKnobs { bool range_split, proj_table, qkv_table, scaled, argmax_fold, lossless; };
+PlanKnobs read_plan_knobs() {
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  return {on("UA2_RANGE_SPLIT"), !on("UA2_NO_PROJ_TABLE"), !on("UA2_NO_QKV_TABLE"), !on("UA2_NO_SCALED"), !on("UA2_NO_ARGMAX_FOLD"), !on("UA2_NO_LOSSLESS")};
+}
 
 struct Carve {
   size_t xa, text, xb, hbuf, xg, hfin, q, act, yattn, xd, curr_h, text_logits, audio_logits, pmax_t, pidx_t,
@@ -111,6 +135,7 @@ struct Carve {
 
 Carve carve(const ua2_stage3_desc& d) {
   Carve c;
+  const PlanKnobs knobs = read_plan_knobs();
   const size_t R = d.max_rows;
   const ua2_gpt_desc* gs[4] = {&d.und, &d.backbone, &d.gen, &d.decoder};
   size_t C = d.backbone.n_embd, Cd = d.decoder.n_embd, qmax = 0, actmax = 0;
@@ -138,11 +163,11 @@ Carve carve(const ua2_stage3_desc& d) {
   c.split_floats = (d.dtype == UA2_BF16 && R >= 256) ? (size_t)16 << 20 : 0;
   c.split = take(c.split_floats);
   // range-split scratch: 16 ranges x 64 rows x the widest down-projection output, plans that can hold 33-64-row decode batches
-  c.range_floats = (d.dtype == UA2_BF16 && d.max_batch >= 33 && getenv("UA2_RANGE_SPLIT") != nullptr) ? (size_t)16 * 64 * std::max(C, Cd) : 0;   // opt-in: measured slower in the frame (ua2_skinny.hip rsplit_*)
+  c.range_floats = (d.dtype == UA2_BF16 && d.max_batch >= 33 && knobs.range_split) ? (size_t)16 * 64 * std::max(C, Cd) : 0;   // opt-in: measured slower in the frame (ua2_skinny.hip rsplit_*)
   c.range = take(c.range_floats);
   // projected-embedding table: (n_cb - 1) * va rows of [Cd fp32 | Cd bf16 | Cd / 16 fp32] (the last codebook's sample is never projected);
   // UA2_NO_PROJ_TABLE=1 keeps the per-step projection launch (A/B, and plans that cannot spare ~1.1 GB at the released sizes)
-  c.ptab_rows = (d.n_cb > 1 && d.va > 0 && d.projection && d.audio_emb && Cd % 32 == 0 && getenv("UA2_NO_PROJ_TABLE") == nullptr) ? (size_t)(d.n_cb - 1) * d.va : 0;
+  c.ptab_rows = (d.n_cb > 1 && d.va > 0 && d.projection && d.audio_emb && Cd % 32 == 0 && knobs.proj_table) ? (size_t)(d.n_cb - 1) * d.va : 0;
   c.ptab_y = take(c.ptab_rows * Cd);
   c.ptab_h = take(c.ptab_rows * Cd / 2);
   c.ptab_ssq = take(c.ptab_rows * (Cd / 16));
@@ -150,7 +175,7 @@ Carve carve(const ua2_stage3_desc& d) {
     const ua2_gpt_desc& g = d.decoder;
     const size_t esz = d.dtype == UA2_BF16 ? 2 : 4, kvw = (size_t)g.n_kv * g.head_size;
     c.ptab_qkv = (c.ptab_rows && g.n_layer > 0 && d.n_cb <= UA2_PAGE && (g.n_head * g.head_size) % 4 == 0 && (g.head_size * esz) % 16 == 0 &&
-                  getenv("UA2_NO_QKV_TABLE") == nullptr) ? 1 : 0;
+                  knobs.qkv_table) ? 1 : 0;
     const size_t rows = c.ptab_qkv ? c.ptab_rows : 0;
     c.ptab_q = take(rows * g.n_head * g.head_size);
     c.ptab_k = take((rows * kvw * esz + 3) / 4);
@@ -166,10 +191,17 @@ Carve carve(const ua2_stage3_desc& d) {
 }
 
 // every ua2_linear of the executor may use the large-M kernel (same results, weights read once per 128 rows)
-void fresh_args(const ua2_stage3* h, ua2_linear_args& a) {
+ua2_linear_args fresh_args(const ua2_stage3* h) {
+  ua2_linear_args a;
   memset(&a, 0, sizeof(a));
-  a.workspace = h->gemm_ws;
-  a.workspace_bytes = h->gemm_ws_bytes;
+  a.workspace = h->gemm_ws; a.workspace_bytes = h->gemm_ws_bytes;
+  return a;
+}
+ua2_kv_geom kv_geom(const ua2_stage3* h, int gi, const ua2_gpt_desc& g, int l) {   // of layer l of GPT gi
+  ua2_kv_geom kv{};                      // ring_pages = 0: the LM's caches are linear
+  kv.k_pool = h->pools[gi][0][l]; kv.v_pool = h->pools[gi][1][l]; kv.page_table = g.page_table;
+  kv.max_pages = g.max_pages; kv.n_kv = g.n_kv; kv.n_head = g.n_head; kv.head_size = g.head_size;
+  return kv;
 }
 
 // Every Linear of the frame goes through here: with fp8 twins attached, a launch whose weight(s) all have one hands them to the launcher,
@@ -181,8 +213,7 @@ void fresh_args(const ua2_stage3* h, ua2_linear_args& a) {
 // times per frame.  Its time is one workgroup's latency chain, which the decode lengthens, not the stream.  It keeps bf16 (the same bits);
 // the trunk's down-projection (192 workgroups) gains and keeps its image.  UA2_L13_ALL=1: every served launch (A/B).
 bool l13_pays(const ua2_linear_args& a) {
-  static Ua2EnvInt all{"UA2_L13_ALL", 0};
-  if (all.get()) return true;
+  if (g_l13_all.get()) return true;
   const ua2_gemv_geometry g = ua2_pick_gemv_geometry(a.dtype, a.N, a.K, a.epilogue == UA2_EPI_SWIGLU ? 2 : 1);
   return !(g.cpw == 16 && ua2_ceil_div(a.N, 16) < 160);
 }
@@ -236,6 +267,39 @@ struct Handover {
   }
 };
 
+// The three head Linears are built here and nowhere else: the decode frame, the deferred flush and teacher-forced scoring share them, so
+// a row carries the same bits whichever of them computed it.
+// text_logits = lm_head(x) with the arg-max partials (model_new.py:617); ws: the launch's operand scratch (the flush has its own)
+ua2_linear_args lm_head_args(const ua2_stage3* h, int M, const float* x, float* y, float* part_max, int32_t* part_idx, int sum_order, void* ws, size_t ws_bytes) {
+  const ua2_stage3_desc& d = h->d;
+  ua2_linear_args a = fresh_args(h);
+  a.workspace = ws; a.workspace_bytes = ws_bytes;
+  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE; a.sum_order = sum_order;
+  a.M = M; a.N = d.vt; a.K = d.backbone.n_embd; a.x = x; a.ldx = a.K; a.w0 = d.lm_head; a.y = y; a.ldy = d.vt;
+  a.part_max = part_max; a.part_idx = part_idx;
+  return a;
+}
+// xd = projection(curr), handed over to the decoder's layer-0 norm under `scaled` (model_new.py:631)
+ua2_linear_args projection_args(ua2_stage3* h, int R, const float* curr, int order, bool scaled) {
+  const int C = h->d.backbone.n_embd, Cd = h->d.decoder.n_embd;
+  ua2_linear_args a = fresh_args(h);
+  a.dtype = h->d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE; a.sum_order = order;
+  a.M = R; a.N = Cd; a.K = C; a.x = curr; a.ldx = C; a.w0 = h->d.projection; a.y = h->xd; a.ldy = Cd;
+  if (scaled) Handover(h, R, Cd).produce(a, h->norms[3][0][0]);
+  return a;
+}
+// audio_logits[:, i] = audio_head[i](ln_f(xd)), arg-max partials over the columns >= forbid[m] (NULL: all) (model_new.py:630-641)
+ua2_linear_args audio_head_args(ua2_stage3* h, int R, int i, int order, bool scaled, const int32_t* forbid) {
+  const ua2_stage3_desc& d = h->d;
+  const int Cd = d.decoder.n_embd;
+  ua2_linear_args a = fresh_args(h);
+  a.dtype = d.dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_STORE; a.sum_order = order;
+  a.M = R; a.N = d.va; a.K = Cd; a.x = h->xd; a.ldx = Cd; a.norm_w = d.decoder.ln_f; a.eps = d.decoder.eps;
+  a.w0 = h->audio_head[i]; a.y = h->audio_logits + (size_t)i * d.va; a.ldy = d.n_cb * d.va;
+  a.part_max = h->pmax_a; a.part_idx = h->pidx_a; a.forbid = forbid;
+  if (scaled) Handover(h, R, Cd).consume(a);
+  return a;
+}
 // launches of R rows under the plan's order-free opt-in (ua2_stage3_set_order_free_rows; bf16 plans)
 bool order_free(const ua2_stage3* h, int R) { return h->d.dtype == UA2_BF16 && h->order_free_rows > 0 && R >= h->order_free_rows; }
 // ... run the scaled hand-over whatever the plan's decode form (the order-free GEMM's epilogues carry it at any row count, and the
@@ -244,14 +308,8 @@ bool order_free_scaled(const ua2_stage3* h, int R, bool prefill = false) {
   // Measured (profiles/r6_notes.md §3): the hand-over through ua2_gemm2.hip's epilogues does not pay in the frame — config-3 prefill
   // 46.43 (prep launches) vs 46.45 ms, B = 1024 decode 22.99 vs 24.55 ms per frame — and in prefill it doubles the distance to the
   // pinned plan (two different bf16 forms of the norm).  Default 0 = never; UA2_OF_SCALED = 1 decode frames, 2 prefill chunks too.
-  static Ua2EnvInt mode{"UA2_OF_SCALED", 0};
-  if (mode.get() < (prefill ? 2 : 1)) return false;
-  return order_free(h, R) && h->d.backbone.n_embd % 32 == 0 && h->d.decoder.n_embd % 32 == 0 && getenv("UA2_NO_SCALED") == nullptr;
-}
-
-bool no_local_fuse() {
-  static const bool v = getenv("UA2_NO_LOCAL_FUSE") != nullptr;   // A/B hook (profiles/r1_notes.md)
-  return v;
+  if (g_of_scaled.get() < (prefill ? 2 : 1)) return false;
+  return order_free(h, R) && h->d.backbone.n_embd % 32 == 0 && h->d.decoder.n_embd % 32 == 0 && !g_no_scaled.set();
 }
 
 // A one-row-tile GEMV (lm_head) whose column tiles travel on the idle CUs of a GPT's small launches (ua2_gemv.hip gemv_rider_kernel).
@@ -273,12 +331,12 @@ struct RiderPlan {
 // final_norm_w: weight of the RMSNorm + Linear that consumes this GPT's OUTPUT through UA2_PRO_SCALED (the depth decoder's
 // ln_f in front of audio_head), or NULL (the trunk GPTs end in ua2_rmsnorm_blend, which reads the fp32 stream).
 // With h->scaled the caller has already handed over x for layer 0 (embed_frame / rmsnorm_blend / the projection's epilogue).
-// rp: the launches of this GPT that can (RiderPlan::ok) carry their share of the rider's column tiles.
-int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const int32_t* row_pos,
-            const int32_t* row_seq, hipStream_t s, bool local = false, bool grouped = false, const float* final_norm_w = nullptr,
-            bool scaled = false, RiderPlan* rp = nullptr, bool qkv0_given = false, const ua2_argmax_fold* fold0 = nullptr) {
+// rider: the launches of this GPT that can (RiderPlan::ok) carry their share of the rider's column tiles.  qkv0_given / fold0: explained where layer 0 reads them.
+struct GptRun { bool local, grouped, scaled, qkv0_given; const float* final_norm_w; RiderPlan* rider; const ua2_argmax_fold* fold0; };
+int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const int32_t* row_pos, const int32_t* row_seq, hipStream_t s,
+            const GptRun& o) {
   auto launch = [&](const ua2_linear_args& a, int kind) -> int {
-    if (rp && rp->ok[kind]) {
+    if (RiderPlan* rp = o.rider; rp && rp->ok[kind]) {
       int t0, t1;
       rp->take(kind, t0, t1);
       const int rc = ua2_gemv_launch_with_rider(a, rp->r, t0, t1, s);
@@ -297,25 +355,21 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     if (order == UA2_SUM_ORDER_FREE) { a.split_ws = h->split_ws; a.split_ws_bytes = h->split_ws_bytes; }
   };
   for (int l = 0; l < g.n_layer; ++l) {
-    ua2_kv_geom kv{};                      // ring_pages = 0: the LM's caches are linear
-    kv.k_pool = h->pools[gi][0][l]; kv.v_pool = h->pools[gi][1][l]; kv.page_table = g.page_table;
-    kv.max_pages = g.max_pages; kv.n_kv = g.n_kv; kv.n_head = g.n_head; kv.head_size = g.head_size;
-
-    ua2_linear_args a;
-    fresh_args(h, a);
+    const ua2_kv_geom kv = kv_geom(h, gi, g, l);
+    ua2_linear_args a = fresh_args(h);
     a.dtype = dt; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_QKV_ROPE;
     a.M = R; a.N = nqkv; a.K = C; a.x = x; a.ldx = C; a.norm_w = h->norms[gi][0][l]; a.eps = g.eps;
     a.w0 = h->ptrs[gi][0][l]; a.row_pos = row_pos; a.row_seq = row_seq; a.rope_cos = g.rope_cos;
     a.rope_sin = g.rope_sin; a.q_out = h->q; a.kv = kv;
-    if (scaled) ho.consume(a);
+    if (o.scaled) ho.consume(a);
     a.sum_order = order;
-    if (!(qkv0_given && l == 0))        // depth decoder, steps >= 1: the previous step's arg-max wrote layer 0's q / k / v from the table
+    if (!(o.qkv0_given && l == 0))        // depth decoder, steps >= 1: the previous step's arg-max wrote layer 0's q / k / v from the table
       if (int rc = launch(a, 0)) return rc;
 
-    const bool fuse_attn = local && R == 1 && !no_local_fuse();
+    const bool fuse_attn = o.local && R == 1 && !g_no_local_fuse.set();
     // more than one row tile: the consumer runs a many-row kernel, so its producer writes the packed operand
     // directly and the consumer's prep launch disappears (same bits: the same RNE cast either way)
-    static const bool no_handover = getenv("UA2_NO_PACKED_HANDOVER") != nullptr;   // A/B hook
+    const bool no_handover = g_no_packed_handover.set();   // A/B hook
     const int kc = dt == UA2_BF16 ? 32 : 16;
     const bool pack_o = !no_handover && R > ua2_gemv_rows_preferred(dt, qn) && qn % kc == 0;
     const bool pack_act = !no_handover && R > ua2_gemv_rows_preferred(dt, g.inter) && g.inter % kc == 0;
@@ -324,41 +378,41 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
       memset(&at, 0, sizeof(at));
       at.dtype = dt; at.R = R; at.q = h->q; at.row_pos = row_pos; at.row_seq = row_seq; at.kv = kv;
       if (pack_o) at.y_packed = h->gemm_ws; else at.y = h->yattn;
-      if (grouped && !local && h->n_groups > 0) {
+      if (o.grouped && !o.local && h->n_groups > 0) {
         at.group_rows = h->group_rows; at.group_seq = h->group_seq; at.group_nkeys = h->group_nkeys;
         at.n_groups = h->n_groups; at.group_q_tiles = h->group_q_tiles;
       }
-      if (int rc = local ? ua2_attn_local_launch(at, s) : ua2_attn_launch(at, s)) return rc;
+      if (int rc = o.local ? ua2_attn_local_launch(at, s) : ua2_attn_launch(at, s)) return rc;
     }
-    fresh_args(h, a);
+    a = fresh_args(h);
     a.dtype = dt; a.prologue = fuse_attn ? UA2_PRO_LOCAL_ATTN : UA2_PRO_CAST; a.epilogue = UA2_EPI_RESIDUAL;
     a.M = R; a.N = C; a.K = qn; a.x = fuse_attn ? h->q : h->yattn; a.ldx = qn;
     a.w0 = h->ptrs[gi][1][l]; a.y = x; a.ldy = C; a.resid = x; a.ldr = C;
     if (fuse_attn) { a.row_pos = row_pos; a.row_seq = row_seq; a.kv = kv; }
-    if (fold0 && l == 0) {            // the previous step's arg-max and table gathers happen inside this launch (ua2_argmax_fold)
-      UA2_CHECK(fuse_attn && qkv0_given, "ua2_stage3: the arg-max fold needs the fused local attention and the q | k | v table");
-      a.fold = *fold0;
+    if (o.fold0 && l == 0) {            // the previous step's arg-max and table gathers happen inside this launch (ua2_argmax_fold)
+      UA2_CHECK(fuse_attn && o.qkv0_given, "ua2_stage3: the arg-max fold needs the fused local attention and the q | k | v table");
+      a.fold = *o.fold0;
     }
     if (pack_o && !fuse_attn) a.x_packed = h->gemm_ws;
-    if (scaled) ho.produce(a, h->norms[gi][1][l]);              // x after attention -> norm_2 + fc_1 / fc_2
+    if (o.scaled) ho.produce(a, h->norms[gi][1][l]);              // x after attention -> norm_2 + fc_1 / fc_2
     a.sum_order = order; free_scratch(a);
     if (int rc = launch(a, 1)) return rc;
 
-    fresh_args(h, a);
+    a = fresh_args(h);
     a.dtype = dt; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_SWIGLU;
     a.M = R; a.N = g.inter; a.K = C; a.x = x; a.ldx = C; a.norm_w = h->norms[gi][1][l]; a.eps = g.eps;
     a.w0 = h->ptrs[gi][2][l]; a.w1 = h->ptrs[gi][3][l]; a.ldy = g.inter;
     if (pack_act) a.y_packed = h->act_ws; else a.y = h->act;
-    if (scaled) ho.consume(a);
+    if (o.scaled) ho.consume(a);
     a.sum_order = order;
     if (int rc = lin(h, a, s)) return rc;
 
-    fresh_args(h, a);
+    a = fresh_args(h);
     a.dtype = dt; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_RESIDUAL;
     a.M = R; a.N = C; a.K = g.inter; a.x = h->act; a.ldx = g.inter; a.w0 = h->ptrs[gi][4][l];
     a.y = x; a.ldy = C; a.resid = x; a.ldr = C;
     if (pack_act) a.x_packed = h->act_ws;
-    if (scaled) ho.produce(a, l + 1 < g.n_layer ? h->norms[gi][0][l + 1] : final_norm_w);   // x after the MLP -> the next layer's norm_1 + qkv
+    if (o.scaled) ho.produce(a, l + 1 < g.n_layer ? h->norms[gi][0][l + 1] : o.final_norm_w);   // x after the MLP -> the next layer's norm_1 + qkv
     a.sum_order = order; free_scratch(a);
     a.range_ws = h->range_ws; a.range_ws_bytes = h->range_ws_bytes;      // 33-64 rows, K = 8192: one K range per workgroup + an in-order combine (same bits)
     if (int rc = launch(a, 2)) return rc;
@@ -463,9 +517,8 @@ __global__ __launch_bounds__(256) void text_flush_kernel(int R, int n_part, int 
 
 // rows of the stash ring in use: UA2_DEFER_ROWS=n (1 .. UA2_DEFER_CAP_ROWS, the default) for tests and sweeps; UA2_NO_DEFER_TEXT_HEAD=1: none (A/B)
 int defer_rows() {
-  static Ua2EnvInt rows{"UA2_DEFER_ROWS", UA2_DEFER_CAP_ROWS}, off{"UA2_NO_DEFER_TEXT_HEAD", 0};
-  if (off.get() == 1) return 0;
-  return std::min(std::max(rows.get(), 1), (int)UA2_DEFER_CAP_ROWS);
+  if (g_no_defer.get() == 1) return 0;
+  return std::min(std::max(g_defer_rows.get(), 1), (int)UA2_DEFER_CAP_ROWS);
 }
 
 // table rows row0 .. row0 + n - 1: position of the step that consumes row g = i * va + id is i + 1; page table of the scratch cache: row r -> page r
@@ -559,6 +612,7 @@ extern "C" size_t ua2_stage3_scratch_floats(const ua2_stage3_desc* d) { return d
 extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
   UA2_CHECK(d && out, "ua2_stage3_create: NULL argument");
   const Carve c = carve(*d);
+  const PlanKnobs knobs = read_plan_knobs();
   UA2_CHECK(d->scratch && d->scratch_floats >= c.total, "ua2_stage3_create: scratch too small (%zu < %zu floats)",
             d->scratch_floats, c.total);
   UA2_CHECK(d->max_batch > 0 && d->max_batch <= d->max_rows, "ua2_stage3_create: need 0 < max_batch <= max_rows");
@@ -597,10 +651,10 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
   // the producers' fragment-order stores cost more than the 140 prep launches they replace (12.6 vs 13.7 ms per frame).  The
   // choice is made once per plan, so every row count served by one plan computes the same function (rows of a 64-sequence
   // batch are bit-identical to their B = 1 runs under the same plan).
-  h->scaled = d->dtype == UA2_BF16 && getenv("UA2_NO_SCALED") == nullptr && d->backbone.n_embd % 32 == 0 && d->decoder.n_embd % 32 == 0 &&
+  h->scaled = d->dtype == UA2_BF16 && knobs.scaled && d->backbone.n_embd % 32 == 0 && d->decoder.n_embd % 32 == 0 &&
               d->max_batch <= 64;
   h->npart_t = (d->vt + 15) / 16; h->npart_a = (d->va + 15) / 16;
-  h->argmax_fold = getenv("UA2_NO_ARGMAX_FOLD") == nullptr;
+  h->argmax_fold = knobs.argmax_fold;
   if (c.ptab_rows) {
     // The table is what the frame's own projection launches would write: same entry point, same arguments, rows in groups of up to 64
     // (decode kernel / weights-stationary kernel: a row's bits do not depend on its group).  Null stream, once per plan.
@@ -621,8 +675,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
       const int n = (int)std::min<size_t>(chunk, c.ptab_rows - row0);
       if (d->dtype == UA2_BF16) hipLaunchKernelGGL(emb_rows_f32_kernel<UA2_BF16>, dim3(std::min(1024, n * 4)), dim3(256), 0, nullptr, d->audio_emb, (long long)row0, n, C, h->xa);
       else hipLaunchKernelGGL(emb_rows_f32_kernel<UA2_F32>, dim3(std::min(1024, n * 4)), dim3(256), 0, nullptr, d->audio_emb, (long long)row0, n, C, h->xa);
-      ua2_linear_args a;
-      fresh_args(h, a);
+      ua2_linear_args a = fresh_args(h);
       a.dtype = d->dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
       a.M = n; a.N = Cd; a.K = C; a.x = h->xa; a.ldx = C; a.w0 = d->projection; a.y = h->ptab_y + row0 * Cd; a.ldy = Cd;
       if (h->ptab_ho) {
@@ -640,7 +693,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
       hipLaunchKernelGGL(ptab_pos_kernel, dim3(1), dim3(64), 0, nullptr, tmp_i, n, (long long)row0, d->va);
       ua2_kv_geom kv{};
       kv.k_pool = tmp_k; kv.v_pool = tmp_v; kv.page_table = tmp_i + 64; kv.max_pages = 1; kv.n_kv = g.n_kv; kv.n_head = g.n_head; kv.head_size = g.head_size;
-      fresh_args(h, a);
+      a = fresh_args(h);
       a.dtype = d->dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_QKV_ROPE;
       a.M = n; a.N = nqkv; a.K = Cd; a.x = h->ptab_y + row0 * Cd; a.ldx = Cd; a.norm_w = h->norms[3][0][0]; a.eps = g.eps;
       a.w0 = h->ptrs[3][0][0]; a.row_pos = tmp_i; a.row_seq = nullptr; a.rope_cos = g.rope_cos; a.rope_sin = g.rope_sin;
@@ -657,7 +710,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
     if (tmp_k) { (void)hipFree(tmp_k); (void)hipFree(tmp_v); (void)hipFree(tmp_i); }
     if (e != hipSuccess) { ua2_set_error("ua2_stage3_create: building the projected-embedding table failed: %s", hipGetErrorString(e)); delete h; return -1; }
   }
-  if (d->dtype == UA2_BF16 && getenv("UA2_NO_LOSSLESS") == nullptr)
+  if (d->dtype == UA2_BF16 && knobs.lossless)
     if (int rc = build_l13(h)) { ua2_stage3_destroy(h); return rc; }
   *out = h;
   return 0;
@@ -665,7 +718,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
 
 extern "C" void ua2_stage3_destroy(ua2_stage3* h) {
   if (!h) return;
-  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
+  drop_graphs(h);
   if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
   if (h->l13_mem) (void)hipFree(h->l13_mem);
   delete h;
@@ -692,16 +745,17 @@ static int trunk_impl(ua2_stage3* h, int32_t R, bool identity, hipStream_t s, bo
   const Handover ho(h, R, C);
   ua2_handover e0{}, e1{}, e2{};
   if (scaled) { e0 = ho.rowwise(h->norms[0][0][0]); e1 = ho.rowwise(h->norms[1][0][0]); e2 = ho.rowwise(h->norms[2][0][0]); }
+  GptRun run{}; run.grouped = grouped; run.scaled = scaled;
   if (int rc = ua2_embed_frame(d.dtype, R, C, d.n_cb, d.va, d.tokens, d.mask, d.audio_emb, d.wte, h->xa, h->text, &e0, s)) return rc;
   if (!skip_experts)
-    if (int rc = run_gpt(h, 0, d.und, h->xa, R, d.row_pos, d.row_seq, s, false, grouped, nullptr, scaled)) return rc;
+    if (int rc = run_gpt(h, 0, d.und, h->xa, R, d.row_pos, d.row_seq, s, run)) return rc;
   // backbone_input = h_audio*audio_step + text_embeds*text_step   (model_new.py:607)
   if (int rc = ua2_rmsnorm_blend(R, C, h->xa, d.und.ln_f, d.und.eps, h->text, d.mask, w, 0, d.n_cb, h->xb, nullptr, &e1, s)) return rc;
-  if (int rc = run_gpt(h, 1, d.backbone, h->xb, R, d.row_pos, d.row_seq, s, false, grouped, nullptr, scaled)) return rc;
+  if (int rc = run_gpt(h, 1, d.backbone, h->xb, R, d.row_pos, d.row_seq, s, run)) return rc;
   // h = ln_f(x); generation_input = h*audio_step                   (model_new.py:609-610)
   if (int rc = ua2_rmsnorm_blend(R, C, h->xb, d.backbone.ln_f, d.backbone.eps, nullptr, d.mask, w, 0, -1, h->xg, h->hbuf, &e2, s)) return rc;
   if (!skip_experts)
-    if (int rc = run_gpt(h, 2, d.gen, h->xg, R, d.row_pos, d.row_seq, s, false, grouped, nullptr, scaled)) return rc;
+    if (int rc = run_gpt(h, 2, d.gen, h->xg, R, d.row_pos, d.row_seq, s, run)) return rc;
   // h_final = h_audio*audio_step + h*text_step                     (model_new.py:613)
   if (int rc = ua2_rmsnorm_blend(R, C, h->xg, d.gen.ln_f, d.gen.eps, h->hbuf, d.mask, w, 0, d.n_cb, h->hfin, nullptr, nullptr, s)) return rc;
   return 0;
@@ -735,10 +789,7 @@ extern "C" int ua2_stage3_set_prefill_groups(ua2_stage3* h, const int32_t* group
 
 extern "C" int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows) {
   UA2_CHECK(h != nullptr && rows >= 0, "ua2_stage3_set_order_free_rows: NULL handle or rows < 0");
-  if (h->order_free_rows != rows) {                  // recorded frames bake the kernel choice: drop them
-    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
-  }
+  if (h->order_free_rows != rows) drop_graphs(h);    // recorded frames bake the kernel choice
   h->order_free_rows = rows;
   return 0;
 }
@@ -758,8 +809,7 @@ extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32
     UA2_CHECK(mine, "ua2_stage3_set_w8: entry %d is not a weight of this plan", i);
     m[e.w] = ua2_stage3::W8Twin{e.q, e.exp};
   }
-  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);     // recorded frames bake the kernels and the weight pointers: drop them
-  h->graphs.clear();
+  drop_graphs(h);                                    // recorded frames bake the kernels and the weight pointers
   h->w8.swap(m);
   return 0;
 }
@@ -767,10 +817,7 @@ extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32
 extern "C" int ua2_stage3_set_lossless(ua2_stage3* h, int32_t on) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_lossless: NULL handle");
   const bool want = on != 0 && !h->l13.empty();
-  if (want != h->lossless) {                          // recorded frames bake the kernels and the weight pointers: drop them
-    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
-  }
+  if (want != h->lossless) drop_graphs(h);           // recorded frames bake the kernels and the weight pointers
   h->lossless = want;
   return 0;
 }
@@ -790,10 +837,7 @@ extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, 
   }
   UA2_CHECK(n <= 16, "ua2_stage3_set_ngram: n must be <= 16, got %d", n);
   UA2_CHECK(hist && hist_len && cap >= 1, "ua2_stage3_set_ngram: missing history buffers");
-  if (fallback != h->ngram_fallback || hist != h->ngram_hist || hist_len != h->ngram_hist_len || cap != h->ngram_cap) {
-    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);   // recorded text frames bake the filter's arguments: drop them
-    h->graphs.clear();
-  }
+  if (fallback != h->ngram_fallback || hist != h->ngram_hist || hist_len != h->ngram_hist_len || cap != h->ngram_cap) drop_graphs(h);   // recorded text frames bake the filter's arguments
   h->ngram_n = n; h->ngram_fallback = fallback; h->ngram_hist = hist; h->ngram_hist_len = hist_len; h->ngram_cap = cap;
   return 0;
 }
@@ -801,12 +845,8 @@ extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, 
 extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
                                           int32_t n_pools) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_beam: NULL handle");
-  auto drop = [&] {
-    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);   // recorded beam frames bake the state's pointers: drop them
-    h->graphs.clear();
-  };
   if (W == 0) {
-    if (h->beam_W != 0) drop();
+    if (h->beam_W != 0) drop_graphs(h);
     h->beam_W = 0; h->beam_G = 1;
     return 0;
   }
@@ -821,7 +861,7 @@ extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, i
   UA2_CHECK(d.und.max_pages == d.backbone.max_pages && d.gen.max_pages == d.backbone.max_pages && d.backbone.max_pages >= 1 &&
             (size_t)W * d.backbone.max_pages * sizeof(int32_t) <= 48 * 1024, "ua2_stage3_set_beam: the three trunk page tables must have one width");
   UA2_CHECK(d.vt >= W, "ua2_stage3_set_beam: vocabulary smaller than the beam");
-  if (W != h->beam_W || G != h->beam_G || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop();
+  if (W != h->beam_W || G != h->beam_G || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop_graphs(h);   // recorded beam frames bake the state's pointers
   h->beam_W = W; h->beam_G = G; h->beam_eos = eos; h->beam = *st; h->beam_pools = pools; h->beam_n_pools = n_pools;
   return 0;
 }
@@ -861,19 +901,14 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   // ua2_gemm2.hip since round 6); `scaled` as in trunk_impl
   const int order = order_free(h, R) ? UA2_SUM_ORDER_FREE : UA2_SUM_ORDER_INVARIANT;
   const bool scaled = h->scaled || order_free_scaled(h, R);
-  ua2_linear_args a;
-  // text_logits = lm_head(last_h); greedy text sample             (model_new.py:617,623)
-  fresh_args(h, a);
-  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
-  a.M = R; a.N = d.vt; a.K = C; a.x = h->hfin; a.ldx = C; a.w0 = d.lm_head; a.y = h->text_logits; a.ldy = d.vt;
-  a.part_max = h->pmax_t; a.part_idx = h->pidx_t; a.sum_order = order;
   UA2_CHECK(!(skip_text && text_only), "ua2_stage3_heads: nothing left to compute");
+  // text_logits = lm_head(last_h); greedy text sample             (model_new.py:617,623)
+  const ua2_linear_args lm = lm_head_args(h, R, h->hfin, h->text_logits, h->pmax_t, h->pidx_t, order, h->gemm_ws, h->gemm_ws_bytes);
   // lm_head does not feed the depth decoder (model_new.py:617 vs :629-640).  A forked graph branch for it replays 0.4 ms per frame
   // SLOWER than the linear chain on ROCm 7.2 (3.49 vs 3.09 ms, re-measured in round 6), so it stays in the chain — but not as a
   // launch of its own when the depth decoder's down-projections can carry it: each of their n_cb x n_layer launches fills half the
   // device (128 workgroups: the per-CU ingest cap, ua2_gemv.hip) and takes one slice of lm_head's column tiles on the other half.
   // Same bits as lm_head's own launch; the text sample moves behind the depth decoder (nothing in between reads it).
-  const ua2_linear_args lm = a;
   RiderPlan rp;
   bool ride = false;
   // fp8 twins attached: the rider kernel has no fp8 form, so lm_head runs as a launch of its own (on its fp8 image when it has one)
@@ -881,9 +916,9 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     const ua2_gpt_desc& g = d.decoder;
     const int qn = g.n_head * g.head_size, nqkv = (g.n_head + 2 * g.n_kv) * g.head_size;
     ua2_linear_args hs[3];
-    for (auto& v : hs) { fresh_args(h, v); v.dtype = d.dtype; v.M = R; v.x = h->act; }
+    for (auto& v : hs) { v = fresh_args(h); v.dtype = d.dtype; v.M = R; v.x = h->act; }
     hs[0].prologue = scaled ? UA2_PRO_SCALED : UA2_PRO_NORM; hs[0].epilogue = UA2_EPI_QKV_ROPE; hs[0].N = nqkv; hs[0].K = Cd;
-    hs[1].prologue = (R == 1 && d.n_cb <= 8 && !no_local_fuse()) ? UA2_PRO_LOCAL_ATTN : UA2_PRO_CAST; hs[1].epilogue = UA2_EPI_RESIDUAL; hs[1].N = Cd; hs[1].K = qn;
+    hs[1].prologue = (R == 1 && d.n_cb <= 8 && !g_no_local_fuse.set()) ? UA2_PRO_LOCAL_ATTN : UA2_PRO_CAST; hs[1].epilogue = UA2_EPI_RESIDUAL; hs[1].N = Cd; hs[1].K = qn;
     hs[2].prologue = UA2_PRO_CAST; hs[2].epilogue = UA2_EPI_RESIDUAL; hs[2].N = Cd; hs[2].K = g.inter;
     const double wk[3] = {0.0, 0.0, 1.0};    // the down-projections only: riders on the 6-us q|k|v / o launches made the frame slower (profiles/r6_notes.md)
     rp.r = lm; rp.ntiles = (lm.N + 15) / 16;
@@ -924,32 +959,19 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   bool fold_next = false;             // step i left its arg-max + table gather to layer 0's O-projection of step i + 1
   for (int i = 0; i < (text_only ? 0 : d.n_cb); ++i) {             // model_new.py:630-641
     const Handover hod(h, R, Cd);
-    if (!(tab && i > 0)) {
-      fresh_args(h, a);
-      a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
-      a.M = R; a.N = Cd; a.K = C; a.x = curr; a.ldx = C; a.w0 = d.projection; a.y = h->xd; a.ldy = Cd;
-      if (scaled) hod.produce(a, h->norms[3][0][0]);
-      a.sum_order = order;
-      if (int rc = lin(h, a, s)) return rc;
-    }
-    if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, d.n_cb <= 8, false,
-                         scaled ? d.decoder.ln_f : nullptr, scaled, ride ? &rp : nullptr, tab && i > 0 && h->ptab_q,
-                         fold_next ? &fg : nullptr)) return rc;
+    if (!(tab && i > 0))
+      if (int rc = lin(h, projection_args(h, R, curr, order, scaled), s)) return rc;
+    GptRun run{}; run.local = d.n_cb <= 8; run.scaled = scaled; run.final_norm_w = scaled ? d.decoder.ln_f : nullptr;
+    run.rider = ride ? &rp : nullptr; run.qkv0_given = tab && i > 0 && h->ptab_q; run.fold0 = fold_next ? &fg : nullptr;
+    if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, run)) return rc;
     fold_next = false;
-    fresh_args(h, a);
-    a.dtype = d.dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_STORE;
-    a.M = R; a.N = d.va; a.K = Cd; a.x = h->xd; a.ldx = Cd; a.norm_w = d.decoder.ln_f; a.eps = d.decoder.eps;
-    a.w0 = h->audio_head[i]; a.y = h->audio_logits + (size_t)i * d.va; a.ldy = d.n_cb * d.va;
-    a.part_max = h->pmax_a; a.part_idx = h->pidx_a; a.forbid = d.forbid;
-    if (scaled) hod.consume(a);
-    a.sum_order = order;
-    if (int rc = lin(h, a, s)) return rc;
+    if (int rc = lin(h, audio_head_args(h, R, i, order, scaled, d.forbid), s)) return rc;
     if (cfg)   // model_new.py:634-637
       if (int rc = ua2_cfg_mix(h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->cfg_scale, d.forbid, h->pmax_a,
                                h->pidx_a, R / 2, s)) return rc;
     // R == 1 with layer 0's q | k | v in the table and the attention fused into the O-projection: that launch of step i + 1 takes the tail
     const ua2_gpt_desc& gdec = d.decoder;
-    if (tab && i + 1 < d.n_cb && h->argmax_fold && h->ptab_q && R == 1 && !cfg && d.n_cb <= 8 && !no_local_fuse() && gdec.n_layer > 0 && h->w8.empty() &&
+    if (tab && i + 1 < d.n_cb && h->argmax_fold && h->ptab_q && R == 1 && !cfg && d.n_cb <= 8 && !g_no_local_fuse.set() && gdec.n_layer > 0 && h->w8.empty() &&
         ua2_gemv_fold_ok(d.dtype, gdec.n_embd, gdec.n_head * gdec.head_size)) {          // (fp8 plans keep the arg-max launches: the fold has no fp8 form)
       fg = ua2_argmax_fold{};
       fg.part_max = h->pmax_a; fg.part_idx = h->pidx_a; fg.n_part = h->npart_a; fg.limit = d.va;
@@ -960,11 +982,8 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
       const ua2_handover g = hod.rowwise(nullptr);
       ua2_qkv_gather qg{};
       if (h->ptab_q) {
-        const ua2_gpt_desc& gd = d.decoder;
-        qg.tab_q = h->ptab_q; qg.tab_k = h->ptab_k; qg.tab_v = h->ptab_v; qg.q_out = h->q; qg.qn = gd.n_head * gd.head_size;
-        qg.esz = d.dtype == UA2_BF16 ? 2 : 4; qg.pos = i + 1;
-        qg.kv.k_pool = h->pools[3][0][0]; qg.kv.v_pool = h->pools[3][1][0]; qg.kv.page_table = gd.page_table; qg.kv.max_pages = gd.max_pages;
-        qg.kv.n_kv = gd.n_kv; qg.kv.n_head = gd.n_head; qg.kv.head_size = gd.head_size;
+        qg.tab_q = h->ptab_q; qg.tab_k = h->ptab_k; qg.tab_v = h->ptab_v; qg.q_out = h->q; qg.qn = gdec.n_head * gdec.head_size;
+        qg.esz = d.dtype == UA2_BF16 ? 2 : 4; qg.pos = i + 1; qg.kv = kv_geom(h, 3, gdec, 0);
       }
       // with layer 0's q | k | v in hand nothing reads the hand-over of the projected row (its only consumer was that launch)
       if (int rc = ua2_argmax_gather(R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, h->ptab_y, h->ptab_h, h->ptab_ssq,
@@ -1072,14 +1091,14 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
     return feedback_impl(h, R, mode, reason_eos, reason_card, st, skip_text ? 1 : 0, defer_frames, fold_last);
   };
   if (!use_graph) return body(s);
-  int tbits, cbits;
-  memcpy(&tbits, &h->temperature, sizeof(int));
-  memcpy(&cbits, &h->cfg_scale, sizeof(int));
-  // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram)
-  const int ngram = mode == 1 ? h->ngram_n << 8 : 0;   // (mode 3: R is groups x beam width, and set_beam drops the graphs with the state, W or G)
-  const int dkey = defer ? (UA2_FRAME_DEFER_TEXT_HEAD | defer_frames << 8) : 0;   // (mode 0 only: the n-gram bits belong to mode 1)
-  const auto key = std::make_tuple((int)R, (int)mode | (skip_text && !defer ? UA2_FRAME_SKIP_TEXT_HEAD : 0) | (skip_experts ? UA2_FRAME_SKIP_AUDIO_EXPERTS : 0) | ngram | dkey,
-                                   (int)reason_eos, (int)reason_card, (int)h->topk, tbits, cbits);
+  // the launch-time knobs are baked into the recorded frames: after ua2_debug_refresh_env every frame is captured anew
+  if (const int gen = g_ua2_env_gen.load(std::memory_order_acquire); gen != h->env_gen) { drop_graphs(h); h->env_gen = gen; }
+  // the n-gram filter is part of a text-feedback frame: its n selects the graph (its buffers and fallback drop them, set_ngram; mode 3: R is
+  // groups x beam width, and set_beam drops the graphs with the state, W or G)
+  FrameKey key{};
+  key.rows = R; key.mode = mode; key.skip_text = skip_text; key.skip_experts = skip_experts; key.defer_slots = defer_frames;
+  key.ngram_n = mode == 1 ? h->ngram_n : 0; key.eos = reason_eos; key.card = reason_card; key.topk = h->topk;
+  memcpy(&key.temp_bits, &h->temperature, sizeof(int)); memcpy(&key.cfg_bits, &h->cfg_scale, sizeof(int));
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     hipGraph_t graph = nullptr;
@@ -1114,14 +1133,10 @@ extern "C" int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, i
   UA2_CHECK(h->topk == 1 && !(h->cfg_scale > 1.f && R > 1), "ua2_stage3_text_flush: the deferred text head is the greedy, unguided one");
   const int C = d.backbone.n_embd, M = n * R;      // M <= cap_frames * R <= UA2_DEFER_CAP_ROWS: the rows every defer_* buffer holds
   hipStream_t s = (hipStream_t)stream;
-  // the launch heads_impl builds for lm_head, over the stashed rows: the launcher picks the kernel by M as it does for a batch, and a
-  // row's bits depend on neither (row invariance), so ids and logits are those of the per-frame launch
-  ua2_linear_args a;
-  memset(&a, 0, sizeof(a));
-  a.workspace = h->defer_ws; a.workspace_bytes = h->defer_ws_bytes;
-  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
-  a.M = M; a.N = d.vt; a.K = C; a.x = h->defer_stash + (size_t)(frame0 % cap_frames) * R * C; a.ldx = C; a.w0 = d.lm_head;
-  a.y = h->defer_logits; a.ldy = d.vt; a.part_max = h->defer_pmax; a.part_idx = h->defer_pidx; a.sum_order = UA2_SUM_ORDER_INVARIANT;
+  // the frame's own lm_head launch (lm_head_args) over the stashed rows, with the flush's buffers: the launcher picks the kernel by M as
+  // it does for a batch, and a row's bits depend on neither (row invariance), so ids and logits are those of the per-frame launch
+  const ua2_linear_args a = lm_head_args(h, M, h->defer_stash + (size_t)(frame0 % cap_frames) * R * C, h->defer_logits, h->defer_pmax, h->defer_pidx,
+                                         UA2_SUM_ORDER_INVARIANT, h->defer_ws, h->defer_ws_bytes);
   if (int rc = lin(h, a, s)) return rc;
   hipLaunchKernelGGL(text_flush_kernel, dim3(M), dim3(256), 0, s, R, h->npart_t, d.vt, h->defer_pmax, h->defer_pidx, d.frame_log, frame0,
                      d.log_frames, d.max_rows, d.n_cb + 1);
@@ -1133,8 +1148,9 @@ extern "C" int ua2_stage3_text_flush(ua2_stage3* h, int32_t R, int32_t frame0, i
 // Teacher-forced scoring of the R rows ua2_stage3_trunk has just run (model_new.py:445-453 of forward, with the cross-entropy of
 // :59-109 taken on the device): heads_impl's plain path — no riders, no per-id tables, no arg-max fold, no graph, no guidance, no
 // sampler, forbid_prefix ignored — with ua2_xent_embed as the tail of every head: it scores the label and gathers the LABEL's
-// embedding for the next codebook step.  The launches are built as heads_impl builds them for !tab && !ride (prologues, hand-overs,
-// sum_order), so on the row-invariant plans a teacher-forced row carries the bits of the decode frame that saw the same ids.
+// embedding for the next codebook step.  The head launches come from the builders the frame uses (lm_head_args, projection_args,
+// audio_head_args) and the depth decoder from run_gpt, so on the row-invariant plans a teacher-forced row carries the bits of the decode
+// frame that saw the same ids.
 // labels / nll / pred: [R, n_cb + 1] in the token layout (a0 .. a(n_cb-1), text).  Writes none of out_tokens, frame_log, counters, the
 // n-gram history or the beam state.
 extern "C" int ua2_stage3_score(ua2_stage3* h, int32_t R, const int32_t* labels, float* nll, int32_t* pred, void* stream) {
@@ -1144,36 +1160,18 @@ extern "C" int ua2_stage3_score(ua2_stage3* h, int32_t R, const int32_t* labels,
   UA2_CHECK(h->beam_W == 0, "ua2_stage3_score: a beam search is attached (ua2_stage3_set_beam); end it first");
   hipStream_t s = (hipStream_t)stream;
   const ua2_stage3_desc& d = h->d;
-  const int C = d.backbone.n_embd, Cd = d.decoder.n_embd, w = d.n_cb + 1;
+  const int C = d.backbone.n_embd, w = d.n_cb + 1;
   const int order = order_free(h, R) ? UA2_SUM_ORDER_FREE : UA2_SUM_ORDER_INVARIANT;
   const bool scaled = h->scaled || order_free_scaled(h, R);
-  ua2_linear_args a;
   // text_logits = lm_head(h_final)                                (model_new.py:445)
-  fresh_args(h, a);
-  a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
-  a.M = R; a.N = d.vt; a.K = C; a.x = h->hfin; a.ldx = C; a.w0 = d.lm_head; a.y = h->text_logits; a.ldy = d.vt;
-  a.part_max = h->pmax_t; a.part_idx = h->pidx_t; a.sum_order = order;
-  if (int rc = lin(h, a, s)) return rc;
+  if (int rc = lin(h, lm_head_args(h, R, h->hfin, h->text_logits, h->pmax_t, h->pidx_t, order, h->gemm_ws, h->gemm_ws_bytes), s)) return rc;
   if (int rc = ua2_xent_embed(d.dtype, R, h->text_logits, d.vt, d.vt, labels, w, d.n_cb, nll, pred, w, d.n_cb, nullptr, 0, C, nullptr, s)) return rc;
   const float* curr = h->hfin;
+  GptRun run{}; run.local = d.n_cb <= 8; run.scaled = scaled; run.final_norm_w = scaled ? d.decoder.ln_f : nullptr;
   for (int i = 0; i < d.n_cb; ++i) {                               // model_new.py:447-453, one codebook position at a time
-    const Handover hod(h, R, Cd);
-    fresh_args(h, a);
-    a.dtype = d.dtype; a.prologue = UA2_PRO_CAST; a.epilogue = UA2_EPI_STORE;
-    a.M = R; a.N = Cd; a.K = C; a.x = curr; a.ldx = C; a.w0 = d.projection; a.y = h->xd; a.ldy = Cd;
-    if (scaled) hod.produce(a, h->norms[3][0][0]);
-    a.sum_order = order;
-    if (int rc = lin(h, a, s)) return rc;
-    if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, d.n_cb <= 8, false,
-                         scaled ? d.decoder.ln_f : nullptr, scaled)) return rc;
-    fresh_args(h, a);
-    a.dtype = d.dtype; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_STORE;
-    a.M = R; a.N = d.va; a.K = Cd; a.x = h->xd; a.ldx = Cd; a.norm_w = d.decoder.ln_f; a.eps = d.decoder.eps;
-    a.w0 = h->audio_head[i]; a.y = h->audio_logits + (size_t)i * d.va; a.ldy = d.n_cb * d.va;
-    a.part_max = h->pmax_a; a.part_idx = h->pidx_a;
-    if (scaled) hod.consume(a);
-    a.sum_order = order;
-    if (int rc = lin(h, a, s)) return rc;
+    if (int rc = lin(h, projection_args(h, R, curr, order, scaled), s)) return rc;
+    if (int rc = run_gpt(h, 3, d.decoder, h->xd, R, d.dec_pos + (size_t)i * d.max_rows, nullptr, s, run)) return rc;
+    if (int rc = lin(h, audio_head_args(h, R, i, order, scaled, nullptr), s)) return rc;
     // the last step's gather has no consumer
     const bool gather = i + 1 < d.n_cb;
     if (int rc = ua2_xent_embed(d.dtype, R, h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, labels, w, i, nll, pred, w, i,

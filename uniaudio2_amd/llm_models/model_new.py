@@ -357,6 +357,27 @@ class Model_stage3(nn.Module):
             self._ngram_hi = 0
         return R
 
+    def _run_chunks(self, tk, mk, ps, sq, chunk, groups, after=None):
+        """The time-major chunk loop of prefill and scoring.  tk, mk (R, 9), ps, sq (R,): the rows' tokens, masks, positions and
+        sequences.  Rows are sorted by position (stable), so a chunk only needs K/V of itself and of earlier chunks, and run `chunk`
+        rows at a time through ua2_stage3_trunk — with prefill row groups when `groups`.  after(order, s0, n), when given, is called
+        after each chunk's trunk, the chunk being rows order[s0:s0 + n] of the input.  Returns order."""
+        order = torch.argsort(ps, stable=True)
+        tk, mk, ps, sq = tk[order], mk[order], ps[order], sq[order]
+        lo, hi = ps[[0, -1]].tolist()                       # sorted: the extremes
+        self._check_positions(hi)
+        self._check_positions(lo)
+        s = ops.stream()
+        for s0 in range(0, tk.shape[0], chunk):
+            c = slice(s0, s0 + chunk)
+            n = self._load_rows(tk[c], mk[c], ps[c], sq[c])
+            if groups:
+                self._set_groups(ps[c], sq[c])
+            check(lib.ua2_stage3_trunk(self._h, n, s), "ua2_stage3_trunk")
+            if after is not None:
+                after(order, s0, n)
+        return order
+
     # ---- reference-compatible methods ---------------------------------------------------------
     @torch.inference_mode()
     def forward_prefix(self, tokens: torch.Tensor, labels: torch.Tensor = None, tokens_mask: torch.Tensor = None,
@@ -373,18 +394,7 @@ class Model_stage3(nn.Module):
             input_pos = torch.arange(S, device=tokens.device).unsqueeze(0).expand(B, S)
         mask = tokens_mask[:, :S]
         seq = torch.arange(B, device=tokens.device).unsqueeze(1).expand(B, S)
-        tk, mk = tokens.reshape(B * S, W), mask.reshape(B * S, W)
-        ps, sq = input_pos.reshape(-1), seq.reshape(-1)
-        # time-major chunks so every chunk only needs KV of earlier chunks
-        order = torch.argsort(ps, stable=True)
-        tk, mk, ps, sq = tk[order], mk[order], ps[order], sq[order]
-        self._check_positions(int(ps.max().item()))
-        self._check_positions(int(ps.min().item()))
-        R, mr = B * S, st["max_rows"]
-        for s0 in range(0, R, mr):
-            n = self._load_rows(tk[s0:s0 + mr], mk[s0:s0 + mr], ps[s0:s0 + mr], sq[s0:s0 + mr])
-            self._set_groups(ps[s0:s0 + mr], sq[s0:s0 + mr])
-            check(lib.ua2_stage3_trunk(self._h, n, ops.stream()), "ua2_stage3_trunk")
+        self._run_chunks(tokens.reshape(B * S, W), mask.reshape(B * S, W), input_pos.reshape(-1), seq.reshape(-1), st["max_rows"], True)
         return None
 
     # ---- teacher-forced scoring (model_new.py:402-454 forward; include/ua2hip.h ua2_stage3_score) ---------------------------------
@@ -419,23 +429,20 @@ class Model_stage3(nn.Module):
         audio_next = tokens_mask[:, 1:S + 1, 0].bool()                     # rows whose NEXT step is an audio step: the rows the local decoder scores
         lab = torch.cat([torch.where(audio_next.unsqueeze(-1), labels, torch.full_like(labels, -1)), text_labels.unsqueeze(-1)], dim=-1)
         seq = torch.arange(B, device=dev).unsqueeze(1).expand(B, S)
-        ps, sq = input_pos.to(dev).reshape(-1), seq.reshape(-1)
-        order = torch.argsort(ps, stable=True)                             # time-major: a chunk only needs K/V of itself and of earlier chunks
-        tk, mk = tokens.reshape(B * S, W)[order], tokens_mask[:, :S].reshape(B * S, W)[order]
-        lb = lab.reshape(B * S, W)[order].to(torch.int32).contiguous()
-        ps, sq = ps[order], sq[order]
-        self._check_positions(int(ps.max().item()))
-        self._check_positions(int(ps.min().item()))
-        R, mb = B * S, st["B"]
-        nll = torch.zeros(R, W, dtype=torch.float32, device=dev)
+        R = B * S
+        lb = lab.reshape(R, W).to(torch.int32)
+        nll = torch.zeros(R, W, dtype=torch.float32, device=dev)           # both in the chunks' (time-major) row order
         pred = torch.zeros(R, W, dtype=torch.int32, device=dev)
-        s = ops.stream()
-        for s0 in range(0, R, mb):
-            n = self._load_rows(tk[s0:s0 + mb], mk[s0:s0 + mb], ps[s0:s0 + mb], sq[s0:s0 + mb])
-            check(lib.ua2_stage3_trunk(self._h, n, s), "ua2_stage3_trunk")
-            check(lib.ua2_stage3_score(self._h, n, lb[s0:].data_ptr(), nll[s0:].data_ptr(), pred[s0:].data_ptr(), s), "ua2_stage3_score")
+
+        def score_chunk(order, s0, n):
+            rows = order[s0:s0 + n]
+            lab_n = lb[rows]                                               # the chunk's labels, contiguous
+            check(lib.ua2_stage3_score(self._h, n, lab_n.data_ptr(), nll[s0:].data_ptr(), pred[s0:].data_ptr(), ops.stream()), "ua2_stage3_score")
             if sink is not None:
-                sink(order[s0:s0 + n], n)
+                sink(rows, n)
+
+        order = self._run_chunks(tokens.reshape(R, W), tokens_mask[:, :S].reshape(R, W), input_pos.to(dev).reshape(-1), seq.reshape(-1),
+                                 st["B"], False, score_chunk)
         inv = torch.empty_like(order)
         inv[order] = torch.arange(R, device=dev)
         nll, pred = nll[inv].view(B, S, W), pred[inv].view(B, S, W)
@@ -699,14 +706,7 @@ class Model_stage3(nn.Module):
         mk = torch.cat([m.reshape(-1, m.shape[-1]) for m in mask_list]).to(dev)
         ps = torch.cat([torch.arange(t.shape[0], device=dev) for t in tokens_list])
         sq = torch.cat([torch.full((t.shape[0],), b, device=dev) for b, t in zip(seq_ids, tokens_list)])
-        order = torch.argsort(ps, stable=True)
-        tk, mk, ps, sq = tk[order], mk[order], ps[order], sq[order]
-        self._check_positions(int(ps.max().item()))
-        R, mr = tk.shape[0], st["max_rows"]
-        for s0 in range(0, R, mr):
-            n = self._load_rows(tk[s0:s0 + mr], mk[s0:s0 + mr], ps[s0:s0 + mr], sq[s0:s0 + mr])
-            self._set_groups(ps[s0:s0 + mr], sq[s0:s0 + mr])
-            check(lib.ua2_stage3_trunk(self._h, n, ops.stream()), "ua2_stage3_trunk")
+        self._run_chunks(tk, mk, ps, sq, st["max_rows"], True)
         return None
 
     @torch.inference_mode()
