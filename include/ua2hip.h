@@ -480,6 +480,17 @@ int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_t ld, int32
                     int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
                     int32_t C, float* next_h, int32_t row_key_shift, void* stream);
 
+/* [v10, addition] The same tail with one random stream PER ROW, read from device memory: row_key [M][2] int32 = the row's 64-bit seed
+ * (lo, hi), row_draw [M] int32 = the row's own draw index.  Philox4x32-10 keyed by (column, row_draw[m], 0, stream_id) under row_key[m]:
+ * neither the row index nor a shared counter enters, so a row's ids depend on nothing but its logits, its key and its draw — row m is
+ * bit-identical to a one-row ua2_sample_topk launch with seed 0, the device seed word row_key[m] and the draw index row_draw[m].
+ * Rows that hold equal (key, draw, logits) — the two rows of a guidance pair — draw equal ids.  Radix select, exponential race, forbid
+ * prefix, the all-NaN rule and the gather are ua2_sample_topk's (one device function).  Nothing is written to row_key / row_draw. */
+int ua2_sample_topk_rows(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                         const int32_t* forbid, const int32_t* row_key, const int32_t* row_draw, int32_t stream_id,
+                         int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                         int32_t C, float* next_h, void* stream);
+
 /* n-gram repeat filter of the text loop (evaluation/asr_task.py:329-432 generate_asr_with_ngram_sampling, :407-432).  Row r
  * (r < R): candidate c = out[r * ld], generated ids H = hist[r * cap ...], L = hist_len[r] of them.  c is replaced by `fallback`
  * when the n-gram (last n - 1 ids of H, c) already occurs in H; the final id is appended to H when L < cap and hist_len[r] becomes
@@ -879,6 +890,14 @@ void ua2_stage3_destroy(ua2_stage3* h);
  * The seed is written to counters[2..3] on `stream` (stream-ordered with the frames that follow); topk / temperature
  * select the captured graph, the seed does not. */
 int ua2_stage3_set_sampling(ua2_stage3* h, int32_t topk, float temperature, uint64_t seed, void* stream);
+/* [v10, addition] Per-row sampler streams (ua2_sample_topk_rows).  row_key [max_batch][2], row_draw [max_batch]: device arrays owned by
+ * the caller, alive while set.  While set, every sampler of a top-k frame (the text sampler — of mode 1 too — and the n_cb audio samplers,
+ * with the stream ids they have without it) draws row m under row_key[m] at row_draw[m], and the frame's one draw-index launch advances
+ * row_draw[0 .. R) instead of counters[1]; the seed of ua2_stage3_set_sampling and counters[1] are then neither read nor written.  The
+ * two rows of a guidance pair get the same key from the caller and advance together.  Greedy frames (topk == 1) neither read nor advance
+ * the streams.  NULL, NULL = off (the default).  The pointers are baked into recorded frames: a change of either drops them, on / off
+ * selects among them. */
+int ua2_stage3_set_row_streams(ua2_stage3* h, int32_t* row_key, int32_t* row_draw);
 /* Row groups (ua2_attn_args.group_*; device tables owned by the caller, alive until replaced) for the attention of the
  * NEXT ua2_stage3_trunk call (they are cleared when it returns): prefill rows of one sequence then share LDS-staged K/V
  * pages on the MFMA flash kernel.  ua2_stage3_frame (decode) never uses groups. */

@@ -238,6 +238,11 @@ extern "C" int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_
                                const int32_t* forbid, uint64_t seed, const int32_t* counter, int32_t stream_id,
                                int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
                                int32_t C, float* next_h, int32_t row_key_shift, void* stream);
+extern "C" int ua2_sample_topk_rows(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                                    const int32_t* forbid, const int32_t* row_key, const int32_t* row_draw, int32_t stream_id,
+                                    int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                                    int32_t C, float* next_h, void* stream);
+int ua2_row_draw_bump(int32_t* row_draw, int32_t R, hipStream_t s);   // row_draw[0 .. R) += 1, one launch (ua2_sample.hip)
 extern "C" int ua2_cfg_mix(float* logits, int32_t ld, int32_t V, float scale, const int32_t* forbid, float* part_max,
                            int32_t* part_idx, int32_t pairs, void* stream);
 // arg-max over the STORE epilogue's partials fused with a gather from the executor's projected-embedding table (ua2_misc.hip)

@@ -32,13 +32,14 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// One row of the tail: block m of either kernel below.  (draw, row_part, seed) is the row's random stream — Philox counter
+// (column, draw, row_part, stream_id) under the 64-bit key `seed`; everything else is the row's data.
 template <int DT>
-__global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restrict__ logits, int ld, int V, int topk,
-                                                           float temperature, const int32_t* __restrict__ forbid,
-                                                           unsigned long long seed, const int32_t* __restrict__ counter,
-                                                           int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
-                                                           int out_col, const void* __restrict__ emb, int emb_off, int C,
-                                                           float* __restrict__ next_h, int row_key_shift) {
+__device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits, int ld, int V, int topk, float temperature,
+                                                const int32_t* __restrict__ forbid, unsigned long long seed, unsigned draw,
+                                                unsigned row_part, int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
+                                                int out_col, const void* __restrict__ emb, int emb_off, int C,
+                                                float* __restrict__ next_h) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sel_prefix, sel_remaining;
   __shared__ float red_v[16];
@@ -82,16 +83,13 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restri
   mx = red_v[0];
   for (int w = 1; w < (nt >> 6); ++w) mx = fmaxf(mx, red_v[w]);
   __syncthreads();
-  const unsigned draw = (unsigned)counter[0];
-  // device-resident part of the key (ua2_stage3_set_sampling writes it): added to the by-value seed
-  seed += (unsigned long long)(unsigned)counter[1] | ((unsigned long long)(unsigned)counter[2] << 32);
   float bv = -INFINITY;
   int bi = UA2_TOK_NONE;
   for (int c = fb + tid; c < V; c += nt) {
     const float l = row[c] / temperature;
     if (key_of(l) < kth) continue;               // removed: strictly below the k-th value
     unsigned r[4];
-    philox4x32((unsigned)c, draw, (unsigned)(m >> row_key_shift), (unsigned)stream_id, (unsigned)seed, (unsigned)(seed >> 32), r);
+    philox4x32((unsigned)c, draw, row_part, (unsigned)stream_id, (unsigned)seed, (unsigned)(seed >> 32), r);
     const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);    // (0, 1)
     const float q = -logf(u);                                                // Exp(1)
     const float score = expf(l - mx) / q;                                    // probs / q up to the softmax constant
@@ -104,6 +102,40 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restri
     const size_t er = (size_t)tok + (size_t)emb_off;
     for (int c = tid; c < C; c += nt) next_h[(size_t)m * C + c] = load_elem<DT>(emb, er * C + c);
   }
+}
+
+// shared stream: one seed and one draw index for the launch, the row index (m >> row_key_shift) tells the rows apart
+template <int DT>
+__global__ __launch_bounds__(1024) void sample_topk_kernel(const float* __restrict__ logits, int ld, int V, int topk,
+                                                           float temperature, const int32_t* __restrict__ forbid,
+                                                           unsigned long long seed, const int32_t* __restrict__ counter,
+                                                           int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
+                                                           int out_col, const void* __restrict__ emb, int emb_off, int C,
+                                                           float* __restrict__ next_h, int row_key_shift) {
+  // device-resident part of the key (ua2_stage3_set_sampling writes it): added to the by-value seed
+  seed += (unsigned long long)(unsigned)counter[1] | ((unsigned long long)(unsigned)counter[2] << 32);
+  sample_topk_row<DT>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)counter[0], (unsigned)((int)blockIdx.x >> row_key_shift),
+                      stream_id, out_tokens, out_ld, out_col, emb, emb_off, C, next_h);
+}
+
+// per-row streams: row m draws under its own key row_key[m] = (lo, hi) at its own index row_draw[m]; neither the row index nor
+// a shared counter enters, so the row's ids are those of a one-row launch of the kernel above with that key and that index
+template <int DT>
+__global__ __launch_bounds__(1024) void sample_topk_rows_kernel(const float* __restrict__ logits, int ld, int V, int topk,
+                                                                float temperature, const int32_t* __restrict__ forbid,
+                                                                const int32_t* __restrict__ row_key, const int32_t* __restrict__ row_draw,
+                                                                int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
+                                                                int out_col, const void* __restrict__ emb, int emb_off, int C,
+                                                                float* __restrict__ next_h) {
+  const int m = blockIdx.x;
+  const unsigned long long seed = (unsigned long long)(unsigned)row_key[2 * m] | ((unsigned long long)(unsigned)row_key[2 * m + 1] << 32);
+  sample_topk_row<DT>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)row_draw[m], 0u, stream_id, out_tokens, out_ld, out_col,
+                      emb, emb_off, C, next_h);
+}
+
+// row_draw[0 .. R) += 1: the per-row form of the executor's one draw-index bump per sampled frame
+__global__ void bump_rows_kernel(int32_t* __restrict__ row_draw, int R) {
+  for (int m = threadIdx.x; m < R; m += blockDim.x) row_draw[m] = (int32_t)((unsigned)row_draw[m] + 1u);
 }
 
 }  // namespace
@@ -127,6 +159,36 @@ extern "C" int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_
     ua2_set_error("ua2_sample_topk: bad dtype %d", dtype);
     return -1;
   }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_sample_topk_rows(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                                    const int32_t* forbid, const int32_t* row_key, const int32_t* row_draw, int32_t stream_id,
+                                    int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                                    int32_t C, float* next_h, void* stream) {
+  UA2_CHECK(M > 0 && logits && V > 0 && out_tokens && row_key && row_draw, "ua2_sample_topk_rows: bad arguments");
+  UA2_CHECK(temperature > 0.f, "temperature must be > 0");
+  UA2_CHECK(topk >= 1 && topk <= V, "topk must be in 1..%d", V);
+  UA2_CHECK(!emb || next_h, "ua2_sample_topk_rows: next_h is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == UA2_BF16)
+    hipLaunchKernelGGL((sample_topk_rows_kernel<UA2_BF16>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid, row_key,
+                       row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
+  else if (dtype == UA2_F32)
+    hipLaunchKernelGGL((sample_topk_rows_kernel<UA2_F32>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid, row_key,
+                       row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
+  else {
+    ua2_set_error("ua2_sample_topk_rows: bad dtype %d", dtype);
+    return -1;
+  }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+int ua2_row_draw_bump(int32_t* row_draw, int32_t R, hipStream_t stream) {
+  UA2_CHECK(row_draw && R > 0, "ua2_row_draw_bump: bad arguments");
+  hipLaunchKernelGGL(bump_rows_kernel, dim3(1), dim3(64), 0, stream, row_draw, R);
   UA2_LAUNCH_CHECK();
   return 0;
 }

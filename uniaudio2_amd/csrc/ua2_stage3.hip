@@ -19,10 +19,10 @@
 
 namespace {
 // What a recorded frame bakes in beyond the plan's own state (the setters drop the graphs with theirs).  mode: without its flag bits;
-// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only
+// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only; row_streams: top-k frames only
 struct FrameKey {
-  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits;
-  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits); }
+  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams;
+  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams); }
   bool operator<(const FrameKey& o) const { return tied() < o.tied(); }
 };
 }  // namespace
@@ -89,6 +89,9 @@ struct ua2_stage3 {
   // n-gram repeat filter of the text-feedback frames (ua2_stage3_set_ngram; ngram_n <= 1 = off): caller-owned device history
   int32_t ngram_n = 0, ngram_fallback = 0, ngram_cap = 0;
   int32_t *ngram_hist = nullptr, *ngram_hist_len = nullptr;
+  // per-row sampler streams (ua2_stage3_set_row_streams; row_streams false = off): caller-owned device arrays, [max_batch][2] and [max_batch]
+  bool row_streams = false;
+  int32_t *row_key = nullptr, *row_draw = nullptr;
   // beam search of the text loop (ua2_stage3_set_beam[_groups]; beam_W == 0 = off): caller-owned device state of beam_G groups of
   // beam_W slots, the K / V pools of the fork
   int32_t beam_W = 0, beam_G = 1, beam_eos = -1, beam_n_pools = 0;
@@ -842,6 +845,18 @@ extern "C" int ua2_stage3_set_ngram(ua2_stage3* h, int32_t n, int32_t fallback, 
   return 0;
 }
 
+extern "C" int ua2_stage3_set_row_streams(ua2_stage3* h, int32_t* row_key, int32_t* row_draw) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_row_streams: NULL handle");
+  if (!row_key && !row_draw) {     // off: the frame graphs key on the mode, so the row-stream ones stay valid for the same arrays
+    h->row_streams = false;
+    return 0;
+  }
+  UA2_CHECK(row_key && row_draw, "ua2_stage3_set_row_streams: row_key and row_draw go together");
+  if (row_key != h->row_key || row_draw != h->row_draw) drop_graphs(h);   // recorded top-k frames bake the samplers' arguments
+  h->row_streams = true; h->row_key = row_key; h->row_draw = row_draw;
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
                                           int32_t n_pools) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_beam: NULL handle");
@@ -939,6 +954,15 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   const bool cfg = h->cfg_scale > 1.f && R > 1;
   UA2_CHECK(!cfg || R % 2 == 0, "ua2_stage3_heads: classifier-free guidance needs (conditional, unconditional) row pairs, R=%d", R);
   const int key_shift = cfg ? 1 : 0;                       // the two rows of a pair hold the same guided logits and draw the same numbers
+  // the frame's samplers: per-row streams when set (the caller gives both rows of a pair one key: no key shift), else the executor's one
+  // seed and draw index with the row index in the key
+  auto sample = [&](const float* logits, int ld, int V, int topk, const int32_t* forbid, int stream_id, const void* emb, int emb_off, float* next_h) -> int {
+    if (h->row_streams)
+      return ua2_sample_topk_rows(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, h->row_key, h->row_draw, stream_id, d.out_tokens, w,
+                                  stream_id, emb, emb_off, C, next_h, s);
+    return ua2_sample_topk(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, 0, d.counters + 1, stream_id, d.out_tokens, w, stream_id, emb,
+                           emb_off, C, next_h, key_shift, s);
+  };
   auto text_tail = [&]() -> int {
     if (skip_text || beam) return 0;   // (beam frames: ua2_beam_step reads the fp32 logits and chooses the ids)  the sampler streams are keyed by (seed, draw index, row, stream id), so the audio streams' draws do not move
     if (cfg)
@@ -946,8 +970,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     if (h->topk == 1)
       return ua2_argmax_embed_launch(d.dtype, R, h->npart_t, d.vt, h->pmax_t, h->pidx_t, d.out_tokens, w, 0, nullptr, 0, C, nullptr, s);
     // model_new.py:623 sample_topk(text_logits, topk, temperature)
-    return ua2_sample_topk(d.dtype, R, h->text_logits, d.vt, d.vt, std::min(h->topk, d.vt), h->temperature, nullptr, 0, d.counters + 1, 0,
-                           d.out_tokens, w, 0, nullptr, 0, C, nullptr, key_shift, s);
+    return sample(h->text_logits, d.vt, d.vt, std::min(h->topk, d.vt), nullptr, 0, nullptr, 0, nullptr);
   };
   if (!ride)
     if (int rc = text_tail()) return rc;
@@ -994,9 +1017,7 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
       if (int rc = ua2_argmax_embed_launch(d.dtype, R, h->npart_a, d.va, h->pmax_a, h->pidx_a, d.out_tokens, w, 1 + i, d.audio_emb,
                                     i * d.va, C, h->curr_h, s)) return rc;
     } else {   // model_new.py:639 audio_sample_topk(ci_logits, topk, temperature, forbid_prefix)
-      if (int rc = ua2_sample_topk(d.dtype, R, h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->topk, h->temperature,
-                                   d.forbid, 0, d.counters + 1, 1 + i, d.out_tokens, w, 1 + i, d.audio_emb, i * d.va, C, h->curr_h,
-                                   key_shift, s)) return rc;
+      if (int rc = sample(h->audio_logits + (size_t)i * d.va, d.n_cb * d.va, d.va, h->topk, d.forbid, 1 + i, d.audio_emb, i * d.va, h->curr_h)) return rc;
     }
     curr = h->curr_h;
   }
@@ -1005,8 +1026,12 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
     if (int rc = text_tail()) return rc;
   }
   if (h->topk != 1) {   // one draw index per frame, advanced after every sampler of the frame has read it
-    hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, s, d.counters + 1);
-    UA2_LAUNCH_CHECK();
+    if (h->row_streams) {
+      if (int rc = ua2_row_draw_bump(h->row_draw, R, s)) return rc;
+    } else {
+      hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, s, d.counters + 1);
+      UA2_LAUNCH_CHECK();
+    }
   }
   return 0;
 }
@@ -1099,6 +1124,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   key.rows = R; key.mode = mode; key.skip_text = skip_text; key.skip_experts = skip_experts; key.defer_slots = defer_frames;
   key.ngram_n = mode == 1 ? h->ngram_n : 0; key.eos = reason_eos; key.card = reason_card; key.topk = h->topk;
   memcpy(&key.temp_bits, &h->temperature, sizeof(int)); memcpy(&key.cfg_bits, &h->cfg_scale, sizeof(int));
+  key.row_streams = (h->row_streams && h->topk != 1) ? 1 : 0;     // greedy frames neither read nor advance the streams
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     hipGraph_t graph = nullptr;

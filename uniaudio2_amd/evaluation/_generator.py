@@ -235,16 +235,25 @@ class GeneratorBase:
         return de_reason.to(self.device), de_sem.to(self.device)
 
     @torch.inference_mode()
-    def _generate_audio_tokens_batch(self, prompts, topk=1, temperature=1.0, max_audio_frames=500, cfg_prompts=None):
+    def _generate_audio_tokens_batch(self, prompts, topk=1, temperature=1.0, max_audio_frames=500, cfg_prompts=None, seeds=None,
+                                     batch_size=None):
         """Many utterances at once on one GPU (the reference loops over them one by one,
         multi_task_inference.py:510): prompts = [(tokens (L_b, 9), mask (L_b, 9)), ...] of any lengths.  One ragged prefill,
         then all sequences decode together in device-side chunks; after each chunk the host runs every sequence's own
-        phase / EOS bookkeeping (the same PhaseSplitter as the single-utterance loop) and retires the finished ones, so
-        the batch shrinks as utterances end.  Greedy results equal the one-by-one results bit for bit (row invariance).
+        phase / EOS bookkeeping (the same PhaseSplitter as the single-utterance loop) and retires the finished ones.
+        batch_size (default: all): at most that many utterances are live; a waiting one is admitted into the running session
+        (Model_stage3.admit_rows) at the first chunk boundary at which a row is free, and runs its own max_audio_frames.
+        seeds: one sampler key per utterance (Model_stage3.set_row_seeds) — utterance b then draws what its own single run
+        draws under set_sampling(topk, temperature, seed=seeds[b]), whatever shares its batch.  Greedy results, and sampled
+        ones under seeds, equal the one-by-one results bit for bit (row invariance).
         With `is_cfg` (the reference's --use_cfg: an unconditional twin of every prompt, tts_task.py:228-245) utterance b
-        occupies the row PAIR (2b, 2b + 1) = (conditional, unconditional): guidance mixes inside a pair
-        (model_new.py:618-622,634-637), both rows continue from the pair's conditional sample (tts_task.py:278-280), the
-        bookkeeping reads the conditional row, and a finished utterance retires both of its rows."""
+        occupies a row PAIR (conditional, unconditional): guidance mixes inside a pair (model_new.py:618-622,634-637), both
+        rows continue from the pair's conditional sample (tts_task.py:278-280) and share the utterance's key, the bookkeeping
+        reads the conditional row, and an utterance admits and retires both of its rows.
+        Returns one slot per utterance, in input order: (reason, semantic), or — for an utterance whose generation failed
+        (PhaseSplitter.result) — the GenerationFailed instance; its batch-mates are not affected.  A call in which EVERY utterance
+        failed raises the first failure, as the single-utterance loop does."""
+        from ..parallel import GenerationFailed
         per = 2 if self.is_cfg else 1
         if self.is_cfg:
             if cfg_prompts is None or len(cfg_prompts) != len(prompts):
@@ -252,39 +261,72 @@ class GeneratorBase:
             for (t, _), (ct, _) in zip(prompts, cfg_prompts):
                 if t.shape != ct.shape:
                     raise ValueError("a prompt and its unconditional twin must have the same shape")
-            prompts = [p for pair in zip(prompts, cfg_prompts) for p in pair]
-        B = len(prompts)                                             # rows
+        n_utt = len(prompts)
+        if seeds is not None and len(seeds) != n_utt:
+            raise ValueError(f"one seed per utterance: got {len(seeds)} seeds for {n_utt} utterances")
+        if n_utt == 0:
+            return []
+        cap = n_utt if batch_size is None else max(1, min(int(batch_size), n_utt))      # live utterances
+        rows_of = lambda b: [(t, m.bool()) for t, m in ([prompts[b], cfg_prompts[b]] if self.is_cfg else [prompts[b]])]
+        keys_of = lambda seq: None if seeds is None else [seeds[b] for b in seq for _ in range(per)]
+        B = per * cap                                                # rows of the plan
         st = getattr(self._model, "_st", None)
         longest = max(int(t.shape[0]) for t, _ in prompts)
-        need_rows = sum(int(t.shape[0]) - 1 for t, _ in prompts)
+        need_rows = per * sum(int(t.shape[0]) - 1 for t, _ in prompts[:cap])
         if st is None or st["B"] < B or st["max_rows"] < min(need_rows, 8192) or st["log_frames"] < max_audio_frames:
             self._model.setup_caches(B, max_rows=max(64, min(need_rows, 8192)), log_frames=max(512, max_audio_frames))
-        self._model.begin_ragged([(t, m.bool()) for t, m in prompts])
+        active, waiting = list(range(cap)), list(range(cap, n_utt))  # live utterances in row(-pair) order; the queue
+        self._model.begin_ragged([p for b in active for p in rows_of(b)])
         self._set_sampling(topk, temperature)
-        n_utt = B // per
+        if seeds is not None:
+            self._model.set_row_seeds(keys_of(active))
         splitters = [PhaseSplitter(self.reason_eos, self.semantic_eos, self.audio_reason_card) for _ in range(n_utt)]
-        active, frame = list(range(n_utt)), 0                        # live utterances, in row(-pair) order
-        while active and frame < max_audio_frames:
-            n = min(self.chunk_frames, max_audio_frames - frame)
-            log = self._model.generate_frames(n, per * len(active), 2 if self.is_cfg else 0, reason_eos=self.reason_eos,
-                                              reason_card=self.audio_reason_card, max_pos=longest + max_audio_frames,
-                                              skip_text_head=self.skip_text_head).cpu()       # (n, rows, 9)
-            keep = []
-            for r, b in enumerate(active):
-                row = per * r                                        # the utterance's (conditional) row
-                for f in range(n):
-                    if not splitters[b].push(log[f, row:row + 1, 1:]):
-                        break
-                if not splitters[b].done:
-                    keep.append(r)
-            self._model.retire_rows([per * r + j for r in keep for j in range(per)], per * len(active))
-            active = [active[r] for r in keep]
-            frame += n
+        ran = [0] * n_utt                                            # frames run per utterance
+        used, log_frames = 0, self._model._st["log_frames"]          # log slots taken since the last rewind
+        try:
+            while active:
+                n = min(self.chunk_frames, min(max_audio_frames - ran[b] for b in active))
+                if used + n > log_frames:                            # a session that admits outlives the log: every slice is on the host
+                    self._model.rewind_frame_log()
+                    used = 0
+                log = self._model.generate_frames(n, per * len(active), 2 if self.is_cfg else 0, reason_eos=self.reason_eos,
+                                                  reason_card=self.audio_reason_card, max_pos=longest + max_audio_frames,
+                                                  skip_text_head=self.skip_text_head).cpu()       # (n, rows, 9)
+                used += n
+                keep = []
+                for r, b in enumerate(active):
+                    row = per * r                                    # the utterance's (conditional) row
+                    for f in range(n):
+                        if not splitters[b].push(log[f, row:row + 1, 1:]):
+                            break
+                    ran[b] += n
+                    if not splitters[b].done and ran[b] < max_audio_frames:
+                        keep.append(r)
+                self._model.retire_rows([per * r + j for r in keep for j in range(per)], per * len(active))
+                active = [active[r] for r in keep]
+                admit, waiting = waiting[:cap - len(active)], waiting[cap - len(active):]
+                if admit:
+                    self._model.admit_rows([p for b in admit for p in rows_of(b)], per * len(active), seeds=keys_of(admit))
+                    active += admit
+        finally:
+            if seeds is not None:
+                self._model.set_row_seeds(None)
         out = []
         for ph in splitters:
-            de_reason, de_sem = ph.result()
-            out.append((de_reason.to(self.device), de_sem.to(self.device)))
+            try:
+                de_reason, de_sem = ph.result()
+                out.append((de_reason.to(self.device), de_sem.to(self.device)))
+            except GenerationFailed as e:
+                out.append(e)
+        if all(isinstance(o, GenerationFailed) for o in out):       # nothing succeeded: there is no batch-mate to protect, the call fails as it always has
+            raise out[0]
         return out
+
+    def _batch_twin(self, prepare, prepare_cfg, inputs, topk, temperature, seeds, batch_size):
+        """The body of every generate_*_batch: inputs[b] = the arguments of the task's prepare_* methods for utterance b."""
+        prompts = [prepare(*a) for a in inputs]
+        cfg = [prepare_cfg(*a) for a in inputs] if self.is_cfg else None
+        return self._generate_audio_tokens_batch(prompts, topk=topk, temperature=temperature, cfg_prompts=cfg, seeds=seeds, batch_size=batch_size)
 
     @torch.inference_mode()
     def _generate_text(self, tokens, tokens_mask, topk=1, temperature=1.0, max_frames=500, no_repeat_ngram_size=0,

@@ -33,3 +33,13 @@ class Generator(GeneratorBase):
         if self.is_cfg:
             cfg_t, cfg_m = self.prepare_instruct_tts_task_for_cfg(task_prompt, caption, text_token)
         return self._generate_audio_tokens(tokens, mask, cfg_t, cfg_m, topk=topk, temperature=temperature)
+
+    @torch.inference_mode()
+    def generate_instruct_tts_batch(self, task_prompt, task_name, text_tokens, captions, temperature: float = 0.9, topk: int = 200,
+                                    cfg_scale=1.0, seeds=None, batch_size=None):
+        """Not in the reference: `generate_instruct_tts` for a list of (text, caption) decoded together on one GPU, as
+        tts_task.generate_tts_batch."""
+        if len(captions) != len(text_tokens):
+            raise ValueError(f"one caption per text: got {len(captions)} captions for {len(text_tokens)} texts")
+        return self._batch_twin(self.prepare_instruct_tts_task, self.prepare_instruct_tts_task_for_cfg,
+                                [(task_prompt, c, t) for c, t in zip(captions, text_tokens)], topk, temperature, seeds, batch_size)

@@ -23,3 +23,10 @@ class Generator(GeneratorBase):
         if self.is_cfg:
             cfg_t, cfg_m = self.prepare_LTS_task_for_cfg(task_prompt, text_token)
         return self._generate_audio_tokens(tokens, mask, cfg_t, cfg_m, topk=topk, temperature=temperature)
+
+    @torch.inference_mode()
+    def generate_LTS_batch(self, task_prompt, task_name, text_tokens, temperature: float = 0.9, topk: int = 200, cfg_scale=1.0,
+                           seeds=None, batch_size=None):
+        """Not in the reference: `generate_LTS` for a list of texts decoded together on one GPU, as tts_task.generate_tts_batch."""
+        return self._batch_twin(self.prepare_LTS_task, self.prepare_LTS_task_for_cfg, [(task_prompt, t) for t in text_tokens], topk,
+                                temperature, seeds, batch_size)

@@ -25,10 +25,11 @@ class Generator(GeneratorBase):
         return self._generate_audio_tokens(tokens, mask, cfg_t, cfg_m, topk=topk, temperature=temperature)
 
     @torch.inference_mode()
-    def generate_tts_batch(self, task_prompt, task_name, text_tokens, temperature: float = 0.9, topk: int = 200, cfg_scale=1.0):
-        """Not in the reference: `generate_tts` for a list of texts decoded together on one GPU (continuous batching);
-        returns [(reason (8, T_r), semantic (8, T_s)), ...] in input order, each equal to its own generate_tts result
-        under greedy decoding."""
-        prompts = [self.prepare_tts_task(task_prompt, t) for t in text_tokens]
-        cfg = [self.prepare_tts_task_for_cfg(task_prompt, t) for t in text_tokens] if self.is_cfg else None
-        return self._generate_audio_tokens_batch(prompts, topk=topk, temperature=temperature, cfg_prompts=cfg)
+    def generate_tts_batch(self, task_prompt, task_name, text_tokens, temperature: float = 0.9, topk: int = 200, cfg_scale=1.0,
+                           seeds=None, batch_size=None):
+        """Not in the reference: `generate_tts` for a list of texts decoded together on one GPU (continuous batching, at most
+        batch_size live at a time); returns one slot per text in input order, (reason (8, T_r), semantic (8, T_s)) or the
+        GenerationFailed of that utterance, each equal to its own generate_tts result under greedy decoding and, with one
+        sampler key per utterance in `seeds`, under top-k sampling too (_generate_audio_tokens_batch)."""
+        return self._batch_twin(self.prepare_tts_task, self.prepare_tts_task_for_cfg, [(task_prompt, t) for t in text_tokens], topk,
+                                temperature, seeds, batch_size)

@@ -68,6 +68,39 @@ def ragged_schedule(n_frames):
         active = [active[r] for r in keep]
 
 
+def admission_schedule(n_frames, batch_size=None):
+    """ragged_schedule with admission: at most `batch_size` sequences are live (None: all of them, which is ragged_schedule);
+    the first batch_size start together and a waiting sequence is admitted, in input order, at the first chunk boundary at which
+    a row is free.  Yields (step, active, keep, admit): run `step` frames with the sequences `active` (original indices, in row
+    order), keep the rows at positions `keep` as rows 0..len(keep)-1, then append the sequences `admit` as the rows behind them.
+    The first step's `active` is the set to start with.  Every sequence runs exactly n_frames[b] frames from its admission."""
+    N = len(n_frames)
+    cap = N if batch_size is None else int(batch_size)
+    if cap < 1 and N:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    waiting = list(range(N))
+    active, waiting = waiting[:cap], waiting[cap:]
+    end = {b: int(n_frames[b]) for b in active}          # the frame count of the session at which sequence b finishes
+    t_now = 0
+    while active:
+        step = min(end[b] for b in active) - t_now
+        t_now += step
+        keep = [r for r, b in enumerate(active) if end[b] > t_now]
+        free = cap - len(keep)
+        admit, waiting = waiting[:free], waiting[free:]
+        yield step, list(active), keep, admit
+        active = [active[r] for r in keep] + admit
+        for b in admit:
+            end[b] = t_now + int(n_frames[b])
+
+
+def _seed_words(seed):
+    """A 64-bit seed as the (lo, hi) int32 pair of row_key."""
+    seed = int(seed) & (2 ** 64 - 1)
+    s32 = lambda x: x - (1 << 32) if x >= (1 << 31) else x
+    return [s32(seed & 0xFFFFFFFF), s32(seed >> 32)]
+
+
 DEFER_CAP_ROWS = 64     # include/ua2hip.h UA2_DEFER_CAP_ROWS: rows of the executor's stash ring
 
 
@@ -261,6 +294,7 @@ class Model_stage3(nn.Module):
         self._ngram = None             # (n, fallback, capacity) of the text frames' n-gram filter (set_ngram); None = off
         self._ngram_hi = 0             # upper bound of every live row's n-gram history length (host side: no device sync)
         self._beam = None              # the running beam search (begin_beams .. end_beams); None = off
+        self._row_streams = False      # per-row sampler streams registered with the executor (set_row_seeds)
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
             self.set_order_free_rows(self.order_free_rows)
         if weight_dtype is not None:
@@ -316,6 +350,15 @@ class Model_stage3(nn.Module):
         st = self._st
         st["counters"][0:1].zero_()      # frame-log slot; the sampler's draw index [1] keeps counting (like a generator)
         st["forbid"].zero_()
+
+    def rewind_frame_log(self):
+        """Rewinds the frame-log slot (counters[0]) between two generate_frames calls of a running session, once the caller has
+        copied the last call's slice out (the returned slice is a view of the log): a session that admits runs more frames than
+        log_frames.  Nothing else moves — positions, forbid, draws and the caches stay.  Safe against the deferred text head: its
+        ring is indexed by counters[0] % capacity, the flush windows of a call are planned from the slot the call starts at, and
+        every flush is issued before generate_frames returns, so no stashed row outlives a call."""
+        self._need()
+        self._st["counters"][0:1].zero_()
 
     def _need(self):
         if self._h is None:
@@ -548,6 +591,34 @@ class Model_stage3(nn.Module):
             check(lib.ua2_stage3_set_sampling(self._h, key[0], key[1], key[2], ops.stream()), "ua2_stage3_set_sampling")
             self._sampling = key
 
+    def set_row_seeds(self, seeds, rows=None):
+        """Per-row sampler streams (include/ua2hip.h ua2_stage3_set_row_streams): row rows[i] (default i) of the decode state draws
+        under its own 64-bit key seeds[i] from draw index 0, so under top-k a row's ids depend on its key and its own frame count
+        alone — not on its row index, its neighbours or the frames run before it.  Row b with seed k then generates what a B = 1
+        run under set_sampling(topk, T, seed=k) generates.  The arrays (st["row_key"] [B, 2], st["row_draw"] [B]) are allocated on
+        first use, travel with retire_rows, and give both rows of a guided pair one stream when the caller gives them one seed.
+        set_row_seeds(None) returns to the shared stream of set_sampling.  Greedy frames never read the streams."""
+        self._need()
+        st = self._st
+        if seeds is None:
+            check(lib.ua2_stage3_set_row_streams(self._h, None, None), "ua2_stage3_set_row_streams")
+            self._row_streams = False
+            return
+        seeds = list(seeds)
+        rows = list(range(len(seeds))) if rows is None else [int(r) for r in rows]
+        if len(rows) != len(seeds) or len(set(rows)) != len(rows) or any(not 0 <= r < st["B"] for r in rows):
+            raise ValueError(f"rows must name {len(seeds)} distinct rows of the plan (0..{st['B'] - 1}), got {rows}")
+        if "row_key" not in st:
+            with torch.inference_mode(False):      # decode state like the rest of st: written in and out of inference mode
+                st["row_key"] = torch.zeros(st["B"], 2, dtype=torch.int32, device=st["device"])
+                st["row_draw"] = torch.zeros(st["B"], dtype=torch.int32, device=st["device"])
+        if rows:
+            idx = torch.tensor(rows, dtype=torch.long, device=st["device"])
+            st["row_key"][idx] = torch.tensor([_seed_words(s) for s in seeds], dtype=torch.int32, device=st["device"])
+            st["row_draw"][idx] = 0
+        check(lib.ua2_stage3_set_row_streams(self._h, st["row_key"].data_ptr(), st["row_draw"].data_ptr()), "ua2_stage3_set_row_streams")
+        self._row_streams = True
+
     def set_cfg(self, cfg_scale: float = 1.0):
         """Classifier-free guidance (model_new.py:618-622, 634-637): with cfg_scale > 1 a frame of two rows
         (conditional, unconditional) samples from l[1] + (l[0] - l[1]) * cfg_scale and both rows take that sample.
@@ -722,13 +793,68 @@ class Model_stage3(nn.Module):
         assert len(set(keep)) == len(keep) and all(0 <= k < batch for k in keep)
         gone = [r for r in range(batch) if r not in set(keep)]
         perm = torch.tensor(keep + gone, dtype=torch.long, device=st["device"])
-        for k in ("tokens", "mask", "row_pos", "forbid", "out_tokens", "ngram_hist", "ngram_len"):
+        for k in self._ROW_STATE:
             if k in st:
                 st[k][:batch] = st[k][:batch][perm]
         for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert):
             pt = g.kv_cache.page_table
             pt[:batch] = pt[:batch][perm]
         return len(keep)
+
+    # the per-row decode state: what retire_rows permutes and admit_rows keeps across its prefill
+    _ROW_STATE = ("tokens", "mask", "row_pos", "forbid", "out_tokens", "ngram_hist", "ngram_len", "row_key", "row_draw")
+
+    @torch.inference_mode()
+    def admit_rows(self, prompts, batch: int, seeds=None):
+        """Continuous batching: appends len(prompts) new sequences, prompts[i] = (tokens (L_i, 9), mask (L_i, 9)), as rows batch ..
+        batch + len(prompts) - 1 of a RUNNING decode session whose live sequences are rows 0..batch-1; returns the new row count.
+        The live rows are not disturbed: after retire_rows the page-table rows at indices >= batch are exactly the free ones
+        (retirement permutes), so every prompt[:-1] is prefilled into them (forward_prefix_ragged with seq_ids = batch ..); the
+        prefill's chunks pass through the decode state's first rows, so the live rows' state (_ROW_STATE and row_seq) is saved
+        before and put back after.  Each prompt's last frame then becomes the first decode frame of its row: position L_i - 1,
+        forbid 0, an empty n-gram history and, under set_row_seeds, key seeds[i] at draw 0.  The frame after an admission runs
+        the audio experts for every row (an admitted row's first frame consumes a prompt token).  Under guidance (mode 2) the
+        caller admits the two rows of a pair together, at an even row, with one seed.  ValueError: more rows than the plan holds,
+        or a prompt that does not fit max_seq_length."""
+        self._need()
+        st = self._st
+        dev = st["device"]
+        n, batch = len(prompts), int(batch)
+        if self._beam is not None:
+            raise ValueError("a beam search is running (end_beams): its rows and pages are live in the plan")
+        if not 0 <= batch <= st["B"] or batch + n > st["B"]:
+            raise ValueError(f"cannot admit {n} sequences beside {batch} live ones: setup_caches({st['B']}) holds {st['B']}")
+        if n == 0:
+            return batch
+        prompts = [(t.to(dev), m.to(dev)) for t, m in prompts]
+        Ls = [int(t.shape[0]) for t, _ in prompts]
+        limit = self.backbone.plan["max_seq"]
+        if min(Ls) < 1 or max(Ls) > limit:
+            raise ValueError(f"prompt lengths {Ls}: every prompt needs 1 .. {limit} frames (max_seq_length of setup_caches)")
+        if self._row_streams and (seeds is None or len(seeds) != n):
+            raise ValueError(f"row streams are on (set_row_seeds): admit_rows needs one seed per prompt, got {seeds}")
+        # the prefill loads its chunks through rows 0.. of these (_load_rows): whole copies, the live rows among them
+        saved = {k: st[k].clone() for k in ("tokens", "mask", "row_pos", "row_seq", "ngram_len") if k in st}
+        ngram_hi = self._ngram_hi
+        pre = [i for i in range(n) if Ls[i] > 1]
+        if pre:
+            self.forward_prefix_ragged([prompts[i][0][:-1] for i in pre], [prompts[i][1][:-1] for i in pre], seq_ids=[batch + i for i in pre])
+        for k, v in saved.items():
+            st[k].copy_(v)
+        self._ngram_hi = ngram_hi
+        new = slice(batch, batch + n)
+        st["tokens"][new] = torch.stack([t[-1] for t, _ in prompts]).to(torch.int32)
+        st["mask"][new] = torch.stack([m[-1] for _, m in prompts]).to(torch.uint8)
+        st["row_pos"][new] = torch.tensor([L - 1 for L in Ls], dtype=torch.int32, device=dev)
+        st["row_seq"][new] = torch.arange(batch, batch + n, dtype=torch.int32, device=dev)
+        st["forbid"][new] = 0
+        if "ngram_len" in st:
+            st["ngram_len"][new] = 0
+        if self._row_streams:
+            self.set_row_seeds(seeds, rows=range(batch, batch + n))
+        self._pos_hi = max(self._pos_hi, max(Ls) - 1)
+        self._text_fed_back = False        # the admitted rows' first frame is a prompt step: the next frame runs whole
+        return batch + n
 
     @torch.inference_mode()
     def begin_ragged(self, prompts):
@@ -752,25 +878,48 @@ class Model_stage3(nn.Module):
         return pos
 
     @torch.inference_mode()
-    def generate_ragged(self, prompts, n_frames, mode: int = 0, reason_eos: int = -1, reason_card: int = 0, skip_text_head: bool = False):
+    def generate_ragged(self, prompts, n_frames, mode: int = 0, reason_eos: int = -1, reason_card: int = 0, skip_text_head: bool = False,
+                        batch_size: Optional[int] = None, seeds=None):
         """Batched fixed-length generation with continuous batching: prompts[b] = (tokens (L_b, 9), mask (L_b, 9)),
-        n_frames[b] frames for sequence b (deterministic stop).  All sequences decode
-        together; a sequence leaves the batch the frame it finishes.  Returns a list of (n_frames[b], 9) int32
-        id tensors (device), each bit-identical to the sequence's own B = 1 run."""
+        n_frames[b] frames for sequence b (deterministic stop).  A sequence leaves the batch the frame it
+        finishes.  batch_size (default: all): at most that many sequences are live; a waiting prompt is admitted into a running
+        session at the first chunk boundary at which a row is free (admission_schedule, admit_rows).  seeds: per-row sampler
+        streams for the call, sequence b draws under seeds[b] (set_row_seeds).  Returns a list of (n_frames[b], 9) int32 id
+        tensors (device), each bit-identical to the sequence's own B = 1 run — under top-k with seeds: its run under
+        set_sampling(topk, T, seed=seeds[b]) — for any batch_size, on the default row-invariant plans.  The session may run more
+        frames than log_frames: the log slot is rewound between calls (rewind_frame_log)."""
         B = len(prompts)
-        assert len(n_frames) == B
-        pos = self.begin_ragged(prompts)
+        assert len(n_frames) == B and (seeds is None or len(seeds) == B)
         st = self._st
+        plan = list(admission_schedule(n_frames, None if batch_size is None else min(int(batch_size), max(B, 1))))
+        if not plan:
+            return []
+        first = plan[0][1]
+        self.begin_ragged([prompts[b] for b in first])
         dev = st["device"]
         out = [[] for _ in range(B)]
-        max_pos = max(int(p) + int(n) for p, n in zip(pos.tolist(), n_frames)) + 1
-        for step, active, keep in ragged_schedule(n_frames):
-            n_act = len(active)
-            if step > 0:
-                log = self.generate_frames(step, n_act, mode, reason_eos, reason_card, max_pos=max_pos, skip_text_head=skip_text_head).clone()
-                for r, b in enumerate(active):
-                    out[b].append(log[:, r])
-            self.retire_rows(keep, n_act)
+        pick = lambda seq: None if seeds is None else [seeds[b] for b in seq]
+        if seeds is not None:
+            self.set_row_seeds(pick(first))
+        used = 0                                   # log slots taken since the last rewind (begin_ragged starts at 0)
+        try:
+            for step, active, keep, admit in plan:
+                n_act, done = len(active), 0
+                while done < step:
+                    n = min(step - done, st["log_frames"])
+                    if used + n > st["log_frames"]:
+                        self.rewind_frame_log()        # every earlier slice has been copied out
+                        used = 0
+                    log = self.generate_frames(n, n_act, mode, reason_eos, reason_card, skip_text_head=skip_text_head).clone()
+                    for r, b in enumerate(active):
+                        out[b].append(log[:, r])
+                    done, used = done + n, used + n
+                n_act = self.retire_rows(keep, n_act)
+                if admit:
+                    self.admit_rows([prompts[b] for b in admit], n_act, seeds=pick(admit))
+        finally:
+            if seeds is not None:
+                self.set_row_seeds(None)
         return [torch.cat(o) if o else torch.zeros(0, st["ncb"] + 1, dtype=torch.int32, device=dev) for o in out]
 
     def begin_decode(self, tokens, tokens_mask, input_pos, forbid_prefix=0):

@@ -9,7 +9,10 @@ MI355X kernels.  Same flags, same `{name}_reason.pt` / `{name}_semantic.pt` (8, 
 
 Differences, all explicit:
   * `--dtype {bf16,fp32}` (default bf16) picks the kernel precision; the reference runs fp32.
-  * `--batch_size N` decodes N utterances of a --text_file together per GPU (continuous batching; TTS).
+  * `--batch_size N` decodes N utterances of a --text_file together per GPU (continuous batching; TTS / Yue_TTS, TTA, TTM, LTS,
+    InstructTTS — speech_s2s stays one by one).  Every utterance samples under its own key (--seed and its global index), so the
+    sampled output is the same for every --batch_size and world size, and equal to --batch_size 1.  A rank's shard runs as one
+    session of N rows: a waiting utterance is admitted into a row the moment one frees up.
   * Under `torchrun` (WORLD_SIZE > 1) the texts of --text_file are sharded over the ranks, one utterance
     per GPU at a time, and gathered with one RCCL all-gather (uniaudio2_amd/parallel.py); rank 0 writes.
   * --topk > 1 samples on the device with a counter-based generator seeded by --seed: reproducible, same
@@ -394,14 +397,19 @@ def run_generation_stage1(args):
         return gen_fn(task_prompt=task_prompt, task_name=task, text_token=ids[i], temperature=args.temperature,
                       topk=args.topk, cfg_scale=args.cfg_scale, **extra(i))
 
-    if args.batch_size > 1 and hasattr(generator, "generate_tts_batch") and _generation_method_name(task) == "generate_tts":
+    twin_name = _generation_method_name(task) + "_batch"
+    twin = getattr(generator, twin_name, None)
+    if args.batch_size > 1 and twin is not None:
         def many(idx):
-            # batched chunks are keyed by their first utterance and draw per (row, frame): samples here DO depend on the
-            # chunk composition, i.e. on --batch_size and the world size (greedy decoding, topk = 1, does not)
-            model.sampling_seed = parallel.utterance_seed(args.seed, idx[0])
-            return generator.generate_tts_batch(task_prompt=task_prompt, task_name=task, text_tokens=[ids[i] for i in idx],
-                                                temperature=args.temperature, topk=args.topk, cfg_scale=args.cfg_scale)
-        results = parallel.run_sharded_batched(list(range(len(items))), [len(x) for x in ids], many, args.batch_size)
+            # every utterance draws under its own key (its global index), whatever shares its batch: sampled output is the same
+            # for every --batch_size and world size, and equal to --batch_size 1 (tests/test_gpu_row_streams.py)
+            kw = {"captions": [ids[i] for i in idx]} if twin_name == "generate_instruct_tts_batch" else {}      # :520-521
+            return twin(task_prompt=task_prompt, task_name=task, text_tokens=[ids[i] for i in idx], temperature=args.temperature,
+                        topk=args.topk, cfg_scale=args.cfg_scale, seeds=[parallel.utterance_seed(args.seed, i) for i in idx],
+                        batch_size=args.batch_size, **kw)
+        # the rank's whole shard in one session of --batch_size rows: a waiting utterance is admitted into a freed row (measured
+        # faster than consecutive chunks of --batch_size on every workload tried: profiles/row_streams_admission.txt)
+        results = parallel.run_sharded_stream(list(range(len(items))), [len(x) for x in ids], many)
     else:
         results = parallel.run_sharded(list(range(len(items))), [len(x) for x in ids], one)
     _write_results(args, items, results, "[Stage1]")
@@ -595,8 +603,9 @@ def get_parser():
     p.add_argument("--length_penalty", type=float, default=0.6,
                    help="--beam_width: exponent of the length normalisation ((5 + length) / 6) ** length_penalty (the reference's default 0.6)")
     p.add_argument("--batch_size", type=int, default=1,
-                   help="utterances decoded together per GPU (extension; 1 = one by one as the reference).  TTS / Yue_TTS with --text_file: "
-                        "continuous batching.  ASR / Yue_ASR with --beam_width W: chunks of N utterances per beam-search frame, N * W <= 64; "
+                   help="utterances decoded together per GPU (extension; 1 = one by one as the reference).  TTS / Yue_TTS / TTA / TTM / LTS / "
+                        "InstructTTS with --text_file: at most N live utterances per GPU, waiting ones admitted into freed rows; greedy and sampled output "
+                        "independent of N.  ASR / Yue_ASR with --beam_width W: chunks of N utterances per beam-search frame, N * W <= 64; "
                         "the K/V plan then holds 2 * N * W sequences (128 sequences at 2048 positions: about 35 GB at the released sizes)")
     return p
 

@@ -172,7 +172,8 @@ def run_sharded(items: Sequence, lengths: Sequence[int], generate_fn) -> Dict[in
 
 def run_sharded_batched(items: Sequence, lengths: Sequence[int], generate_batch_fn, batch_size: int):
     """As run_sharded, but this rank's shard is processed `batch_size` items at a time by
-    generate_batch_fn(list of items) -> list of (reason, semantic) (continuous batching on one GPU)."""
+    generate_batch_fn(list of items) -> list of (reason, semantic) (continuous batching on one GPU).  A slot that holds a
+    GenerationFailed instance instead becomes that utterance's `Failed`; a call that raises one fails its whole chunk."""
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     mine = list(shard_indices(lengths, world, rank))
@@ -183,7 +184,8 @@ def run_sharded_batched(items: Sequence, lengths: Sequence[int], generate_batch_
             chunk = mine[s0:s0 + max(1, batch_size)]
             try:
                 for i, res in zip(chunk, generate_batch_fn([items[i] for i in chunk])):
-                    local[i] = res
+                    # a slot may hold its utterance's own failure (the batched generators return the exception instance)
+                    local[i] = Failed(f"{type(res).__name__}: {res}") if isinstance(res, GenerationFailed) else res
             except GenerationFailed as e:
                 for i in chunk:
                     local.setdefault(i, Failed(f"{type(e).__name__}: {e}"))
@@ -197,3 +199,10 @@ def run_sharded_batched(items: Sequence, lengths: Sequence[int], generate_batch_
         if exc is not None:
             raise e from exc
         raise
+
+
+def run_sharded_stream(items: Sequence, lengths: Sequence[int], generate_stream_fn):
+    """As run_sharded_batched, with this rank's WHOLE shard handed to one generate_stream_fn(list of items) call: the
+    generator schedules it itself (a bounded number of live utterances, admission into freed rows) and returns one slot per
+    item — (reason, semantic), or the GenerationFailed of that utterance, which becomes its `Failed`."""
+    return run_sharded_batched(items, lengths, generate_stream_fn, max(1, len(items)))
