@@ -640,6 +640,14 @@ typedef struct ua2_conv1d_args {
 } ua2_conv1d_args;
 
 int ua2_conv1d(const ua2_conv1d_args* a, void* stream);
+/* [v10, addition] Test hook: what ua2_conv1d would launch for *a — the launcher's own selection code, nothing launched, no pointer of
+ * *a dereferenced (they are only tested for NULL, as by ua2_conv1d; a geometry ua2_conv1d rejects is rejected here with the same message).
+ * Reads UA2_CONV_PIPE exactly as the launcher does.  kernel: 0 = exact fp32, 1 = bf16 x 3 plain, 2 = bf16 x 3 pipelined.  ntt: 16-step
+ * time tiles per wave.  rt: wave row-groups per workgroup (exact kernel: 4).  Pipelined kernel: tpw = consecutive time tiles per
+ * workgroup, gpu = channel groups per unit, npg = instantiated position groups, nw = waves per workgroup (8: the fused 128-channel
+ * unit).  Other kernels: tpw = 1, npg = 0, nw = 4; gpu = 0 (exact) or the row tiles per wave, RPW (plain bf16 x 3). */
+int ua2_debug_conv1d_plan(const ua2_conv1d_args* a, int32_t* kernel, int32_t* ntt, int32_t* rt, int32_t* tpw, int32_t* gpu,
+                          int32_t* npg, int32_t* nw);
 /* ---- codec decode side: convolutions on "time-major split planes" (round 4) --------------------------------------
  * Between the layers of the waveform DECODER (scalar24k.py:403-407: ScalarModel.decode = Conv1d -> N x ResDecoderBlock
  * [ConvTranspose1d up-sampler -> 5 dilated ResidualUnits, :143-151] -> PostProcessor -> Conv1d) activations travel as two

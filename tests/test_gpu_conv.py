@@ -1,5 +1,9 @@
 """GPU parity of the conv kernel against the PyTorch fp32 ops the reference calls (F.conv1d /
-F.conv_transpose1d on CPU), tolerance 2e-5 relative to the output scale (fp32, different summation order)."""
+F.conv_transpose1d on CPU), tolerance 2e-5 relative to the output scale (fp32, different summation order).
+
+The anchor of the conv family is tests/test_gpu_conv_parity.py: every kernel of ua2_conv1d / ua2_conv1d_tc against float64
+restatements (tests/conv_refs.py) under derived bars, with guard margins around every buffer.  The global tolerances here are
+kept as they were; the bit-identity tests below (pipelined == plain) hang from that anchor."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -215,8 +219,11 @@ def test_fused_residual_unit_matches_torch(C, dil, T):
 
 
 PIPE_CASES = [
-    # Cin, Cout, K, dil, T, residual, fused, in_repeat: every (K, channel-group run, position-group) instantiation family of the
-    # pipelined kernel, windows that end inside a tile, ragged channel counts, one and many units per tile
+    # Cin, Cout, K, dil, T, residual, fused, in_repeat: (K, channel-group run, position-group) instantiation families of the
+    # pipelined kernel, windows that end inside a tile, ragged channel counts, one and many units per tile.  That EVERY arm of the
+    # launcher is reached is proved elsewhere: tests/test_conv_refs_host.py::test_table_reaches_every_arm_of_the_launcher asks
+    # ua2_debug_conv1d_plan which instantiation each case of tests/conv_refs.py takes (at B = 2 a fused 128-channel unit of
+    # 700 steps, as below, runs the plain kernel on both sides: the 8-wave arm needs ntt = 4)
     (32, 32, 7, 9, 1000, True, True, 1), (64, 64, 7, 1, 4097, True, True, 1), (128, 128, 7, 5, 700, True, True, 1),
     (512, 512, 7, 3, 150, False, False, 1), (256, 256, 1, 1, 777, True, False, 1), (17, 19, 7, 3, 70, False, False, 1),
     (48, 40, 1, 1, 333, True, False, 1), (64, 32, 7, 1, 2049, False, False, 2), (1, 32, 7, 1, 5000, False, False, 1),

@@ -167,6 +167,7 @@ _EXPORTS = {
     "ua2_rmsnorm_blend": (C.c_int, [i32, i32, vp, vp, f32, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "ua2_argmax_embed": (C.c_int, [C.c_int, i32, i32, vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]),
     "ua2_conv1d": (C.c_int, [C.POINTER(Conv1dArgs), vp]),
+    "ua2_debug_conv1d_plan": (C.c_int, [C.POINTER(Conv1dArgs)] + [C.POINTER(i32)] * 7),
     "ua2_conv1d_tc": (C.c_int, [C.POINTER(ConvTcArgs), vp]),
     "ua2_tc_pack": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "ua2_tc_unpack": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

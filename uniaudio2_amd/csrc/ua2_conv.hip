@@ -767,13 +767,34 @@ extern "C" int ua2_dwconv1d(const float* x, const float* w, const float* bias, f
   return 0;
 }
 
-extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
+namespace {
+
+// What ua2_conv1d launches for a problem: which kernel, its template arguments and its launch geometry.  conv1d_select is the ONE
+// statement of the launcher's rules; ua2_conv1d launches what it returns and ua2_debug_conv1d_plan reports it.
+struct conv1d_plan {
+  int kernel;            // 0 = conv1d_kernel (exact), 1 = conv1d_x3_kernel, 2 = conv1d_x3p_kernel
+  int ntt, rt, rpw;      // time tiles per wave; wave row-groups per workgroup; row tiles per wave (plain x3 kernel)
+  int tpw, gpu, npg, nw; // pipelined kernel: tiles per workgroup, channel groups per unit, instantiated position groups, waves
+  int ntiles;            // pipelined kernel: time tiles
+  bool upt1;             // pipelined kernel: one unit per tile
+  dim3 grid;
+  size_t smem;
+};
+
+// the (CPU, GPU, NPG) instantiations of the 4-wave pipelined kernel: membership test in conv1d_select, cases in ua2_conv1d
+#define UA2_X3P_INSTANCES(X) \
+  X(7, 1, 1) X(7, 1, 2) X(7, 1, 3) X(1, 1, 2) X(1, 1, 4) X(2, 1, 2) X(2, 1, 4) X(2, 2, 1) X(2, 2, 2) X(4, 2, 1) X(4, 2, 2) X(4, 4, 1) X(8, 4, 1)
+
+int conv1d_select(const ua2_conv1d_args* a, conv1d_plan* p) {
   UA2_CHECK(a && a->x && a->w && a->y, "ua2_conv1d: NULL argument");
   UA2_CHECK(a->B > 0 && a->Cin > 0 && a->Cout > 0 && a->Tin > 0 && a->Tout > 0, "ua2_conv1d: empty problem");
   UA2_CHECK(a->K >= 1 && a->K <= kMaxK && a->stride >= 1 && a->dilation >= 1 && a->in_repeat >= 1 && a->out_phases >= 1,
             "ua2_conv1d: bad geometry K=%d stride=%d dil=%d", a->K, a->stride, a->dilation);
   UA2_CHECK(a->out_phases == 1 || (a->stride == 1 && a->dilation == 1), "ua2_conv1d: phase mode needs stride=dilation=1");
   UA2_CHECK(a->post_act != UA2_ACT_PRELU || a->post_alpha, "ua2_conv1d: PReLU needs post_alpha");
+  *p = conv1d_plan{};
+  p->tpw = 1;
+  p->nw = 4;
   const int tq = a->out_phases == 1 ? a->Tout : ua2_ceil_div(a->Tout + a->out_trim_left, a->out_phases);
   if (a->precision == 1) {
     UA2_CHECK(a->w_lo != nullptr, "ua2_conv1d: precision 1 (bf16 x 3) needs w_lo (ua2 host helper pack_conv_weight_x3)");
@@ -787,7 +808,6 @@ extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
                     (a->Cout == 32 || a->Cout == 64 || a->Cout == 128) && row_blocks3 == 1 && a->Tin == a->Tout,
                 "ua2_conv1d: the fused residual unit needs Cin == Cout in {32, 64, 128}, stride 1, Tin == Tout, w2_lo and residual");
     }
-    hipStream_t st = (hipStream_t)stream;
     // ---- software-pipelined kernel whenever a unit's weights and window fit its register budget ----
     {
       const int nw = (a->w2 && rows == 128) ? 8 : 4;                     // the fused 128-channel unit: 8 waves hold its 8 row tiles
@@ -848,35 +868,23 @@ extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
         int tpw = (int)std::min<int64_t>(8, std::max<int64_t>(1, (total + slots - 1) / slots));
         if (p_tpw > 0) tpw = p_tpw;
         const int64_t Wn = (int64_t)(wgt - 1) * a->stride + (a->K - 1) * a->dilation + 1;
-        const size_t smem = (size_t)lds_of(ntt, gpu);
         const int npgi = npg_inst(gpu, (int)((Wn + 63) / 64));
-        const dim3 grid(ua2_ceil_div(ntiles, tpw), p_rb, a->B);
         const int cpu = gpu * a->K;
-#define UA2_X3P(N, C, G, P) launch_x3p<N, C, G, P>(*a, grid, smem, p_rt, tpw, ntiles, ngroups == gpu, st)
-#define UA2_X3P_N(C, G, P) (ntt == 4 ? UA2_X3P(4, C, G, P) : ntt == 2 ? UA2_X3P(2, C, G, P) : UA2_X3P(1, C, G, P))
         if (nw == 8) {
           UA2_CHECK(ntt == 4 && cpu == 7 && npgi == 2, "ua2_conv1d: fused 128-channel unit outside its instantiation (ntt=%d K=%d npg=%d)", ntt, a->K, npgi);
-          launch_x3p<4, 7, 1, 2, 8>(*a, grid, smem, p_rt, tpw, ntiles, false, st);
-        } else
-        switch ((cpu * 8 + gpu) * 8 + npgi) {
-          case (7 * 8 + 1) * 8 + 1: UA2_X3P_N(7, 1, 1); break;
-          case (7 * 8 + 1) * 8 + 2: UA2_X3P_N(7, 1, 2); break;
-          case (7 * 8 + 1) * 8 + 3: UA2_X3P_N(7, 1, 3); break;
-          case (1 * 8 + 1) * 8 + 2: UA2_X3P_N(1, 1, 2); break;
-          case (1 * 8 + 1) * 8 + 4: UA2_X3P_N(1, 1, 4); break;
-          case (2 * 8 + 1) * 8 + 2: UA2_X3P_N(2, 1, 2); break;
-          case (2 * 8 + 1) * 8 + 4: UA2_X3P_N(2, 1, 4); break;
-          case (2 * 8 + 2) * 8 + 1: UA2_X3P_N(2, 2, 1); break;
-          case (2 * 8 + 2) * 8 + 2: UA2_X3P_N(2, 2, 2); break;
-          case (4 * 8 + 2) * 8 + 1: UA2_X3P_N(4, 2, 1); break;
-          case (4 * 8 + 2) * 8 + 2: UA2_X3P_N(4, 2, 2); break;
-          case (4 * 8 + 4) * 8 + 1: UA2_X3P_N(4, 4, 1); break;
-          case (8 * 8 + 4) * 8 + 1: UA2_X3P_N(8, 4, 1); break;
-          default: UA2_CHECK(false, "ua2_conv1d: no pipelined instantiation for K=%d gpu=%d npg=%d", a->K, gpu, npgi);
+        } else {
+          bool inst = false;
+#define UA2_X3P_IS(C, G, P) inst = inst || (cpu == C && gpu == G && npgi == P);
+          UA2_X3P_INSTANCES(UA2_X3P_IS)
+#undef UA2_X3P_IS
+          UA2_CHECK(inst && (ntt == 4 || ntt == 2 || ntt == 1), "ua2_conv1d: no pipelined instantiation for K=%d gpu=%d npg=%d ntt=%d", a->K, gpu, npgi, ntt);
         }
-#undef UA2_X3P_N
-#undef UA2_X3P
-        UA2_LAUNCH_CHECK();
+        p->kernel = 2;
+        p->ntt = ntt; p->rt = p_rt; p->rpw = 1; p->tpw = tpw; p->gpu = gpu; p->npg = npgi; p->nw = nw;
+        p->ntiles = ntiles;
+        p->upt1 = nw == 4 && ngroups == gpu;
+        p->grid = dim3(ua2_ceil_div(ntiles, tpw), p_rb, a->B);
+        p->smem = (size_t)lds_of(ntt, gpu);
         return 0;
       }
     }
@@ -888,20 +896,12 @@ extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
     };
     while (ntt > 1 && lds_bytes(ntt) > 52 * 1024) ntt >>= 1;            // keep three workgroups per CU resident (latency hiding beats tile size here)
     const int wgt = 16 * ntt * (4 / rt);
-    const int W3 = (wgt - 1) * a->stride + (a->K - 1) * a->dilation + 1;
     const size_t smem3 = lds_bytes(ntt);
     UA2_CHECK(smem3 <= 150 * 1024, "ua2_conv1d: window too large (%zu B LDS)", smem3);
-    const dim3 grid3(ua2_ceil_div(tq, wgt), row_blocks3, a->B);
-    if (rpw == 2) {
-      if (ntt == 4) launch_x3<4, 2>(*a, grid3, smem3, rt, st);
-      else if (ntt == 2) launch_x3<2, 2>(*a, grid3, smem3, rt, st);
-      else launch_x3<1, 2>(*a, grid3, smem3, rt, st);
-    } else {
-      if (ntt == 4) launch_x3<4, 1>(*a, grid3, smem3, rt, st);
-      else if (ntt == 2) launch_x3<2, 1>(*a, grid3, smem3, rt, st);
-      else launch_x3<1, 1>(*a, grid3, smem3, rt, st);
-    }
-    UA2_LAUNCH_CHECK();
+    p->kernel = 1;
+    p->ntt = ntt; p->rt = rt; p->rpw = rpw;
+    p->grid = dim3(ua2_ceil_div(tq, wgt), row_blocks3, a->B);
+    p->smem = smem3;
     return 0;
   }
   UA2_CHECK(a->precision == 0, "ua2_conv1d: precision must be 0 (exact fp32) or 1 (bf16 x 3)");
@@ -914,14 +914,61 @@ extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
   const int W = (bt - 1) * a->stride + (a->K - 1) * a->dilation + 1;
   const size_t smem = (size_t)kCIG * (W + 1) * sizeof(float) + (size_t)kCIG * a->K * sizeof(int);
   UA2_CHECK(smem <= 150 * 1024, "ua2_conv1d: window too large (%zu B LDS)", smem);
-  ua2_allow_big_lds<conv1d_kernel<4>>();
-  ua2_allow_big_lds<conv1d_kernel<2>>();
-  ua2_allow_big_lds<conv1d_kernel<1>>();
-  const dim3 grid(ua2_ceil_div(tq, bt), row_blocks, a->B);
-  if (ntt == 4) hipLaunchKernelGGL(conv1d_kernel<4>, grid, dim3(256), smem, (hipStream_t)stream, *a);
-  else if (ntt == 2) hipLaunchKernelGGL(conv1d_kernel<2>, grid, dim3(256), smem, (hipStream_t)stream, *a);
-  else hipLaunchKernelGGL(conv1d_kernel<1>, grid, dim3(256), smem, (hipStream_t)stream, *a);
+  p->kernel = 0;
+  p->ntt = ntt; p->rt = 4; p->rpw = 1;
+  p->grid = dim3(ua2_ceil_div(tq, bt), row_blocks, a->B);
+  p->smem = smem;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ua2_conv1d(const ua2_conv1d_args* a, void* stream) {
+  conv1d_plan p;
+  if (const int rc = conv1d_select(a, &p)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int ntt = p.ntt;
+  if (p.kernel == 2) {
+#define UA2_X3P(N, C, G, P) launch_x3p<N, C, G, P>(*a, p.grid, p.smem, p.rt, p.tpw, p.ntiles, p.upt1, st)
+#define UA2_X3P_CASE(C, G, P) case (C * 8 + G) * 8 + P: (ntt == 4 ? UA2_X3P(4, C, G, P) : ntt == 2 ? UA2_X3P(2, C, G, P) : UA2_X3P(1, C, G, P)); break;
+    if (p.nw == 8) launch_x3p<4, 7, 1, 2, 8>(*a, p.grid, p.smem, p.rt, p.tpw, p.ntiles, false, st);
+    else
+      switch ((p.gpu * a->K * 8 + p.gpu) * 8 + p.npg) {
+        UA2_X3P_INSTANCES(UA2_X3P_CASE)
+        default: UA2_CHECK(false, "ua2_conv1d: no pipelined instantiation for K=%d gpu=%d npg=%d", a->K, p.gpu, p.npg);
+      }
+#undef UA2_X3P_CASE
+#undef UA2_X3P
+  } else if (p.kernel == 1) {
+    if (p.rpw == 2) {
+      if (ntt == 4) launch_x3<4, 2>(*a, p.grid, p.smem, p.rt, st);
+      else if (ntt == 2) launch_x3<2, 2>(*a, p.grid, p.smem, p.rt, st);
+      else launch_x3<1, 2>(*a, p.grid, p.smem, p.rt, st);
+    } else {
+      if (ntt == 4) launch_x3<4, 1>(*a, p.grid, p.smem, p.rt, st);
+      else if (ntt == 2) launch_x3<2, 1>(*a, p.grid, p.smem, p.rt, st);
+      else launch_x3<1, 1>(*a, p.grid, p.smem, p.rt, st);
+    }
+  } else {
+    ua2_allow_big_lds<conv1d_kernel<4>>();
+    ua2_allow_big_lds<conv1d_kernel<2>>();
+    ua2_allow_big_lds<conv1d_kernel<1>>();
+    if (ntt == 4) hipLaunchKernelGGL(conv1d_kernel<4>, p.grid, dim3(256), p.smem, st, *a);
+    else if (ntt == 2) hipLaunchKernelGGL(conv1d_kernel<2>, p.grid, dim3(256), p.smem, st, *a);
+    else hipLaunchKernelGGL(conv1d_kernel<1>, p.grid, dim3(256), p.smem, st, *a);
+  }
   UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_debug_conv1d_plan(const ua2_conv1d_args* a, int32_t* kernel, int32_t* ntt, int32_t* rt, int32_t* tpw, int32_t* gpu,
+                                     int32_t* npg, int32_t* nw) {
+  UA2_CHECK(kernel && ntt && rt && tpw && gpu && npg && nw, "ua2_debug_conv1d_plan: NULL output");
+  conv1d_plan p;
+  if (const int rc = conv1d_select(a, &p)) return rc;
+  *kernel = p.kernel; *ntt = p.ntt; *rt = p.rt; *tpw = p.tpw; *nw = p.nw;
+  *gpu = p.kernel == 1 ? p.rpw : p.gpu;
+  *npg = p.npg;
   return 0;
 }
 

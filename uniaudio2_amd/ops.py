@@ -369,8 +369,33 @@ def pack_conv_weight_x3(w_rows):
     return pack_linear(hi.float().contiguous(), torch.bfloat16), pack_linear(lo, torch.bfloat16)
 
 
+def conv1d_plan(B, Cin, Cout, Tin, Tout, K, *, stride=1, dilation=1, in_repeat=1, out_phases=1, out_trim_left=0, pre_act=0, post_act=0,
+                precision=0, fused=False, residual=False):
+    """What ua2_conv1d would launch for this problem (ua2_debug_conv1d_plan: the launcher's own selection code; nothing is launched and
+    no device is needed): dict(kernel, ntt, rt, tpw, gpu, npg, nw), see include/ua2hip.h.  Reads UA2_CONV_PIPE as the launcher does."""
+    from ._lib import Conv1dArgs
+    a = Conv1dArgs()
+    a.B, a.Cin, a.Cout, a.Tin, a.Tout = B, Cin, Cout, Tin, Tout
+    a.K, a.stride, a.dilation = K, stride, dilation
+    a.in_repeat, a.out_phases, a.out_trim_left = in_repeat, out_phases, out_trim_left
+    a.pre_act, a.post_act, a.precision = pre_act, post_act, precision
+    some = 64                              # pointers are only tested for NULL
+    a.x = a.w = a.y = a.post_alpha = some
+    a.post_alpha_n = 1
+    if precision == 1:
+        a.w_lo = some
+    if fused:
+        a.w2 = a.w2_lo = some
+    if fused or residual:
+        a.residual = some
+    out = [C.c_int32() for _ in range(7)]
+    check(lib.ua2_debug_conv1d_plan(C.byref(a), *[C.byref(o) for o in out]), "ua2_debug_conv1d_plan")
+    return dict(zip(("kernel", "ntt", "rt", "tpw", "gpu", "npg", "nw"), (o.value for o in out)))
+
+
 def conv1d(x, w_packed, K, Cout, *, stride=1, dilation=1, pad_left=0, Tout=None, bias=None, pre_act=0, pre_alpha=None,
-           post_act=0, post_alpha=None, residual=None, in_repeat=1, out_phases=1, out_trim_left=0, w_lo=None, fused2=None):
+           post_act=0, post_alpha=None, residual=None, in_repeat=1, out_phases=1, out_trim_left=0, w_lo=None, fused2=None, out=None):
+    """`out`: an fp32, contiguous [B, Cout, Tout] tensor (or view) to write into instead of a fresh one."""
     from ._lib import Conv1dArgs
     B, Cin, Tin = x.shape
     a = Conv1dArgs()
@@ -378,7 +403,11 @@ def conv1d(x, w_packed, K, Cout, *, stride=1, dilation=1, pad_left=0, Tout=None,
     a.K, a.stride, a.dilation, a.pad_left = K, stride, dilation, pad_left
     a.in_repeat, a.out_phases, a.out_trim_left = in_repeat, out_phases, out_trim_left
     a.pre_act, a.post_act = pre_act, post_act
-    y = torch.empty(B, Cout, Tout, dtype=torch.float32, device=x.device)
+    if out is None:
+        y = torch.empty(B, Cout, Tout, dtype=torch.float32, device=x.device)
+    else:
+        assert out.shape == (B, Cout, Tout) and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
+        y = out
     a.x, a.w, a.bias = ptr(x), ptr(w_packed), ptr(bias)
     a.pre_alpha, a.post_alpha = ptr(pre_alpha), ptr(post_alpha)
     a.post_alpha_n = post_alpha.numel() if post_alpha is not None else 0
@@ -447,7 +476,7 @@ def tc_unpack(t):
 
 
 def conv1d_tc(x, w_hi, w_lo, K, Cout, *, dilation=1, pad_left=0, Tout=None, bias=None, post_act=0, post_alpha=None, in_repeat=1,
-              out_phases=1, out_trim_left=0, fused2=None, residual=None, out_f32=False, variant=0):
+              out_phases=1, out_trim_left=0, fused2=None, residual=None, out_f32=False, variant=0, out=None):
     """ua2_conv1d_tc: x a TC; (w_hi, w_lo) = pack_conv_weight_x3(filter rows).  Returns a TC, or fp32 [B, Cout, Tout] with
     out_f32 (the waveform).  fused2 = (w2_hi, w2_lo, bias2, alpha2): the 1 x 1 conv + PReLU + residual of a residual unit in
     the same launch (residual = x), with (w2_hi, w2_lo) = pack_conv_weight_x3(tc_w2_order(W2)); residual = a TC added after the
@@ -467,11 +496,18 @@ def conv1d_tc(x, w_hi, w_lo, K, Cout, *, dilation=1, pad_left=0, Tout=None, bias
         assert residual.shape == (B, Cout, Tout)
         a.res_hi, a.res_lo = ptr(residual.hi), ptr(residual.lo)
     dev = x.planes.device
+    if out is not None:                   # write into the caller's fp32 tensor (out_f32) or planes (anything with .hi / .lo / .shape)
+        assert tuple(out.shape) == (B, Cout, Tout)
+        y = out
     if out_f32:
-        y = torch.empty(B, Cout, Tout, dtype=torch.float32, device=dev)
+        if out is None:
+            y = torch.empty(B, Cout, Tout, dtype=torch.float32, device=dev)
+        assert y.dtype == torch.float32
         a.y_f32 = ptr(y)
     else:
-        y = TC.empty(B, Cout, Tout, dev)
+        if out is None:
+            y = TC.empty(B, Cout, Tout, dev)
+        assert y.hi.dtype == torch.bfloat16 and y.lo.dtype == torch.bfloat16
         a.y_hi, a.y_lo = ptr(y.hi), ptr(y.lo)
     check(lib.ua2_conv1d_tc(C.byref(a), stream()), "ua2_conv1d_tc")
     return y
