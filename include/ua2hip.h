@@ -491,6 +491,40 @@ int ua2_sample_topk_rows(int dtype, int32_t M, const float* logits, int32_t ld, 
                          int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
                          int32_t C, float* next_h, void* stream);
 
+/* [v10, addition] Nucleus (top-p) sampling: ua2_sample_topk / ua2_sample_topk_rows with one more filter between the top-k threshold and
+ * the race (llm_utils/sampling.py:66-82 sample_top_p, :85-105 sample_token(..., top_k, top_p)).  Per row, with l_c = logits[c] / T over
+ * the columns c in [forbid, V), K = the top-k kept set exactly as above (key(l_c) >= the k-th largest key; topk = V admits every
+ * column), mx = max l_c and e_c = expf(l_c - mx), the very values the race computes:
+ *   the nucleus keeps column c of K iff the mass of the columns of K whose value is STRICTLY GREATER than l_c is at most top_p times
+ *   the mass of K.
+ * This is the reference's `mask = probs_sum - probs_sort > p` without the sort, with one departure: columns that tie at the threshold
+ * value are all kept (the tie rule of the top-k filter), where torch.sort would split the tie arbitrarily — probabilities
+ * [.4, .2, .2, .1, .1] under top_p = .5 keep 3 columns here, 2 there.  The race then runs over the nucleus with the same Philox counter
+ * per column (column, draw, row part, stream_id) and the same score e_c / q: a row whose top-k-only id lies in the nucleus draws the
+ * same id, and pure nucleus sampling is topk = V.
+ * The masses are summed in integers, so that the kept set — and with it the row's id — is a function of the row's logits alone, not of
+ * thread scheduling, atomic order or launch geometry:
+ *   q_c = (uint64) floor(e_c * 2^40), 0 for a NaN or non-finite e_c;  Z = sum of q_c over K (at most 2^57 for V <= 2^17: a larger V is
+ *   refused);  P = (uint64) floor((double) top_p * 2^32);  S_gt(c) = sum of q_j over the j of K with key(l_j) > key(l_c);
+ *   c is kept iff S_gt(c) * 2^32 <= P * Z, compared exactly in 128 bits.
+ * Z == 0 (a row of -inf or NaN): no nucleus filter, the all-NaN rule above decides.  A NaN column (the largest key, mass 0) next to
+ * finite ones stays admitted and loses the race, as in ua2_sample_topk.
+ * top_p == 0 and top_p >= 1 mean OFF: ids and gathered rows are bit-identical to the top-k launch (with keep_count == NULL it IS that
+ * launch).  top_p outside [0, 1] or NaN, or V > 131072, is an error and nothing is launched.
+ * keep_count: optional [M] int32 (NULL = off) — the number of columns of row m that entered the race (the nucleus size; |K| when off).
+ * The threshold value is found by a weighted 4-pass radix select on the keys (256 buckets of uint64 mass per pass, native LDS 64-bit
+ * adds, runs of equal buckets summed per thread and per wave first); one 1024-thread workgroup per row, like the top-k tail. */
+int ua2_sample_topp(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                    const int32_t* forbid, uint64_t seed, const int32_t* counter, int32_t stream_id,
+                    int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                    int32_t C, float* next_h, int32_t row_key_shift, float top_p, int32_t* keep_count, void* stream);
+/* [v10, addition] ... with one random stream per row (ua2_sample_topk_rows): row m equals a one-row ua2_sample_topp launch with that key
+ * and draw, bit for bit; nothing is written to row_key / row_draw. */
+int ua2_sample_topp_rows(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                         const int32_t* forbid, const int32_t* row_key, const int32_t* row_draw, int32_t stream_id,
+                         int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                         int32_t C, float* next_h, float top_p, int32_t* keep_count, void* stream);
+
 /* n-gram repeat filter of the text loop (evaluation/asr_task.py:329-432 generate_asr_with_ngram_sampling, :407-432).  Row r
  * (r < R): candidate c = out[r * ld], generated ids H = hist[r * cap ...], L = hist_len[r] of them.  c is replaced by `fallback`
  * when the n-gram (last n - 1 ids of H, c) already occurs in H; the final id is appended to H when L < cap and hist_len[r] becomes
@@ -906,6 +940,12 @@ int ua2_stage3_set_sampling(ua2_stage3* h, int32_t topk, float temperature, uint
  * the streams.  NULL, NULL = off (the default).  The pointers are baked into recorded frames: a change of either drops them, on / off
  * selects among them. */
 int ua2_stage3_set_row_streams(ua2_stage3* h, int32_t* row_key, int32_t* row_draw);
+/* [v10, addition] Nucleus filter of the heads' samplers (ua2_sample_topp above): with topk > 1 and 0 < top_p < 1 every sampler of a frame —
+ * the text sampler and the n_cb audio samplers, shared stream or per-row streams, guided pairs included — runs the nucleus tail; 0
+ * (the default) and 1 are off and the frame is the top-k frame it was.  top_p outside [0, 1] or NaN is an error.  Greedy frames
+ * (topk == 1, the per-id tables and the arg-max fold with them), ua2_stage3_text_flush and beam frames ignore it.  top_p's bits select
+ * the captured graph next to topk / temperature: a changed value never replays a frame recorded under another. */
+int ua2_stage3_set_top_p(ua2_stage3* h, float top_p);
 /* Row groups (ua2_attn_args.group_*; device tables owned by the caller, alive until replaced) for the attention of the
  * NEXT ua2_stage3_trunk call (they are cleared when it returns): prefill rows of one sequence then share LDS-staged K/V
  * pages on the MFMA flash kernel.  ua2_stage3_frame (decode) never uses groups. */

@@ -195,6 +195,9 @@ _EXPORTS = {
     "ua2_attn_relbias": (C.c_int, [C.POINTER(AttnArgs), vp, vp, vp, i32, vp]),
     "ua2_sample_topk_rows": (C.c_int, [C.c_int, i32, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp]),
     "ua2_stage3_set_row_streams": (C.c_int, [vp, vp, vp]),
+    "ua2_sample_topp": (C.c_int, [C.c_int, i32, vp, i32, i32, i32, f32, vp, C.c_uint64, vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, f32, vp, vp]),
+    "ua2_sample_topp_rows": (C.c_int, [C.c_int, i32, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, f32, vp, vp]),
+    "ua2_stage3_set_top_p": (C.c_int, [vp, f32]),
     "ua2_ngram_filter": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "ua2_beam_step": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
     "ua2_beam_reorder": (C.c_int, [i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),

@@ -10,6 +10,13 @@
 // Randomness: counter-based Philox4x32-10 keyed by (seed + the 64-bit device word counter[1..2], draw index
 // counter[0] from the device frame counter, row, stream) — reproducible under hipGraph replay and independent of launch geometry.  It cannot
 // reproduce torch's generator stream; parity with the reference is distributional (tests).
+//
+// Nucleus (top-p) filter (llm_utils/sampling.py:66-82 sample_top_p; include/ua2hip.h ua2_sample_topp has the contract): among the
+// top-k kept columns, keep column c iff the mass of the kept columns of strictly greater value is at most top_p of the kept mass.
+// The masses are integers, q_c = floor(expf(l_c - mx) * 2^40), so their sums do not depend on the order the threads add them in; the
+// threshold value is found by a second, WEIGHTED 4-pass radix select on the same keys (256 buckets of uint64 mass per pass), and the
+// race then runs over key >= max(k-th key, threshold key).  Ties at the threshold value are all kept, like the top-k filter's.
+// The filter is a template parameter: the top-k-only kernels are the code they were.
 #include "ua2_common.h"
 
 namespace {
@@ -34,12 +41,14 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
 
 // One row of the tail: block m of either kernel below.  (draw, row_part, seed) is the row's random stream — Philox counter
 // (column, draw, row_part, stream_id) under the 64-bit key `seed`; everything else is the row's data.
-template <int DT>
+// TOPP: the nucleus form — nucleus != 0 filters with P = floor(top_p * 2^32); keep_count (optional) [M] = columns that entered the race
+template <int DT, bool TOPP = false>
 __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits, int ld, int V, int topk, float temperature,
                                                 const int32_t* __restrict__ forbid, unsigned long long seed, unsigned draw,
                                                 unsigned row_part, int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
                                                 int out_col, const void* __restrict__ emb, int emb_off, int C,
-                                                float* __restrict__ next_h) {
+                                                float* __restrict__ next_h, int nucleus = 0, unsigned long long P = 0ull,
+                                                int32_t* __restrict__ keep_count = nullptr) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sel_prefix, sel_remaining;
   __shared__ float red_v[16];
@@ -83,11 +92,95 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   mx = red_v[0];
   for (int w = 1; w < (nt >> 6); ++w) mx = fmaxf(mx, red_v[w]);
   __syncthreads();
+  unsigned thr = kth;                            // the race admits key >= thr
+  int kept = 0;
+  if constexpr (TOPP) {
+    // ---- nucleus: lowest value v* whose strictly-greater kept mass S_gt satisfies S_gt * 2^32 <= P * Z ------------------------
+    __shared__ unsigned long long mass[256];
+    __shared__ unsigned long long nu_above, nu_pz_lo, nu_pz_hi;   // mass above the selected prefix; P * Z as 128 bits
+    __shared__ unsigned nu_prefix;
+    __shared__ int nu_on;
+    if (tid == 0) { nu_prefix = 0u; nu_above = 0ull; nu_on = nucleus; }
+    for (int pass = 3; pass >= 0 && nucleus; --pass) {
+      if (tid < 256) mass[tid] = 0ull;
+      __syncthreads();
+      if (!nu_on) break;                         // Z == 0 (a row of -inf or NaN): no filter, the all-NaN rule decides
+      const unsigned prefix = nu_prefix, shift = pass * 8;
+      const unsigned mask_hi = (pass == 3) ? 0u : (0xffffffffu << (shift + 8));
+      // a thread sums runs of columns that share a bucket before it touches LDS: neighbouring logits mostly share the top byte,
+      // and a flat row shares all four
+      int rb = -1;
+      unsigned long long rs = 0ull;
+      for (int c = fb + tid; c < V; c += nt) {
+        const float l = row[c] / temperature;
+        const unsigned k = key_of(l);
+        if (k < kth || (k & mask_hi) != prefix) continue;
+        const float e = expf(l - mx);
+        const unsigned long long q = (e == e && e < INFINITY) ? (unsigned long long)(e * 1099511627776.0f) : 0ull;   // floor(e * 2^40)
+        if (q == 0ull) continue;
+        const int b = (int)((k >> shift) & 255u);
+        if (b != rb) {
+          if (rs) atomicAdd(&mass[rb], rs);
+          rb = b; rs = 0ull;
+        }
+        rs += q;
+      }
+      const int b0 = __shfl(rb, 0);
+      if (__all(rb == b0)) {                     // the wave ends on one bucket (always on a flat row): one add per wave
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) rs += __shfl_xor(rs, o);
+        if ((tid & 63) == 0 && rs) atomicAdd(&mass[b0], rs);
+      } else if (rs) {
+        atomicAdd(&mass[rb], rs);
+      }
+      __syncthreads();
+      if (tid < 64) {
+        // The lowest bucket that holds mass and whose top value is kept (mass above it * 2^32 <= P * Z; the mass above only grows on
+        // the way down, so the kept buckets are the leading ones).  One wave: lane j owns buckets 255 - 4j .. 252 - 4j, a shuffle scan
+        // over the lanes gives the mass above each — 256 dependent LDS reads of one thread otherwise, as long as the pass itself.
+        unsigned long long m4[4], tot = 0ull;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { m4[i] = mass[255 - 4 * tid - i]; tot += m4[i]; }
+        unsigned long long inc = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const unsigned long long t = __shfl_up(inc, o);
+          if (tid >= o) inc += t;
+        }
+        unsigned long long pz_lo = nu_pz_lo, pz_hi = nu_pz_hi;
+        int on = nu_on;
+        if (pass == 3) {                         // the first pass's buckets hold every kept column: their total is Z
+          const unsigned long long Z = __shfl(inc, 63);
+          pz_lo = P * Z; pz_hi = __umul64hi(P, Z);
+          on = Z != 0ull;
+          if (tid == 0) { nu_pz_lo = pz_lo; nu_pz_hi = pz_hi; nu_on = on; }
+        }
+        unsigned long long acc = nu_above + (inc - tot), cand_acc = 0ull;
+        int cand = 256;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const unsigned long long a_hi = acc >> 32, a_lo = acc << 32;         // acc * 2^32 (acc <= 2^57)
+          if (m4[i] != 0ull && !(a_hi > pz_hi || (a_hi == pz_hi && a_lo > pz_lo))) { cand = 255 - 4 * tid - i; cand_acc = acc; }
+          acc += m4[i];
+        }
+        int sel = cand;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) sel = min(sel, __shfl_xor(sel, o));
+        if (on && sel < 256 && cand == sel) {    // (on: the top bucket that holds mass always qualifies, so sel < 256; one lane owns it)
+          nu_prefix = prefix | ((unsigned)sel << shift);
+          nu_above = cand_acc;
+        }
+      }
+      __syncthreads();
+    }
+    if (nucleus && nu_on) thr = max(kth, nu_prefix);
+  }
   float bv = -INFINITY;
   int bi = UA2_TOK_NONE;
   for (int c = fb + tid; c < V; c += nt) {
     const float l = row[c] / temperature;
-    if (key_of(l) < kth) continue;               // removed: strictly below the k-th value
+    if (key_of(l) < thr) continue;               // removed: strictly below the k-th value (and, TOPP, below the nucleus threshold)
+    if constexpr (TOPP) ++kept;
     unsigned r[4];
     philox4x32((unsigned)c, draw, row_part, (unsigned)stream_id, (unsigned)seed, (unsigned)(seed >> 32), r);
     const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);    // (0, 1)
@@ -98,6 +191,19 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   // every kept column scored NaN (a NaN or all -inf row): the lowest column the row may sample (ua2_row_token)
   const int tok = ua2_row_token(bv, bi, V, red_v, red_i, &tok_s, [&] { return (tid == 0 && fb < V) ? fb : UA2_TOK_NONE; });
   if (tid == 0) out_tokens[(size_t)m * out_ld + out_col] = tok;
+  if constexpr (TOPP) {
+    if (keep_count) {                            // red_i is free again: ua2_row_token's last reader is behind its barriers
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) kept += __shfl_xor(kept, o);
+      if ((tid & 63) == 0) red_i[tid >> 6] = kept;
+      __syncthreads();
+      if (tid == 0) {
+        int n = 0;
+        for (int w = 0; w < (nt >> 6); ++w) n += red_i[w];
+        keep_count[m] = n;
+      }
+    }
+  }
   if (emb) {
     const size_t er = (size_t)tok + (size_t)emb_off;
     for (int c = tid; c < C; c += nt) next_h[(size_t)m * C + c] = load_elem<DT>(emb, er * C + c);
@@ -131,6 +237,34 @@ __global__ __launch_bounds__(1024) void sample_topk_rows_kernel(const float* __r
   const unsigned long long seed = (unsigned long long)(unsigned)row_key[2 * m] | ((unsigned long long)(unsigned)row_key[2 * m + 1] << 32);
   sample_topk_row<DT>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)row_draw[m], 0u, stream_id, out_tokens, out_ld, out_col,
                       emb, emb_off, C, next_h);
+}
+
+// the two kernels above with the nucleus filter (sample_topk_row<DT, true>): the same streams, the same race
+template <int DT>
+__global__ __launch_bounds__(1024) void sample_topp_kernel(const float* __restrict__ logits, int ld, int V, int topk,
+                                                           float temperature, const int32_t* __restrict__ forbid,
+                                                           unsigned long long seed, const int32_t* __restrict__ counter,
+                                                           int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
+                                                           int out_col, const void* __restrict__ emb, int emb_off, int C,
+                                                           float* __restrict__ next_h, int row_key_shift, int nucleus,
+                                                           unsigned long long P, int32_t* __restrict__ keep_count) {
+  seed += (unsigned long long)(unsigned)counter[1] | ((unsigned long long)(unsigned)counter[2] << 32);
+  sample_topk_row<DT, true>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)counter[0], (unsigned)((int)blockIdx.x >> row_key_shift),
+                            stream_id, out_tokens, out_ld, out_col, emb, emb_off, C, next_h, nucleus, P, keep_count);
+}
+
+template <int DT>
+__global__ __launch_bounds__(1024) void sample_topp_rows_kernel(const float* __restrict__ logits, int ld, int V, int topk,
+                                                                float temperature, const int32_t* __restrict__ forbid,
+                                                                const int32_t* __restrict__ row_key, const int32_t* __restrict__ row_draw,
+                                                                int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
+                                                                int out_col, const void* __restrict__ emb, int emb_off, int C,
+                                                                float* __restrict__ next_h, int nucleus, unsigned long long P,
+                                                                int32_t* __restrict__ keep_count) {
+  const int m = blockIdx.x;
+  const unsigned long long seed = (unsigned long long)(unsigned)row_key[2 * m] | ((unsigned long long)(unsigned)row_key[2 * m + 1] << 32);
+  sample_topk_row<DT, true>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)row_draw[m], 0u, stream_id, out_tokens, out_ld, out_col,
+                            emb, emb_off, C, next_h, nucleus, P, keep_count);
 }
 
 // row_draw[0 .. R) += 1: the per-row form of the executor's one draw-index bump per sampled frame
@@ -180,6 +314,75 @@ extern "C" int ua2_sample_topk_rows(int dtype, int32_t M, const float* logits, i
                        row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h);
   else {
     ua2_set_error("ua2_sample_topk_rows: bad dtype %d", dtype);
+    return -1;
+  }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+// top_p of the nucleus entries: 0 and >= 1 are off, anything outside [0, 1] (NaN included) is refused; P = floor(top_p * 2^32)
+static int topp_arguments(const char* who, int32_t V, float top_p, int* nucleus, unsigned long long* P) {
+  UA2_CHECK(top_p >= 0.f && top_p <= 1.f, "%s: top_p must be in [0, 1] (0 and 1 = off), got %g", who, (double)top_p);
+  UA2_CHECK(V <= (1 << 17), "%s: V = %d: the integer masses of the nucleus filter are sized for V <= 131072", who, V);
+  *nucleus = (top_p > 0.f && top_p < 1.f) ? 1 : 0;
+  *P = *nucleus ? (unsigned long long)((double)top_p * 4294967296.0) : 0ull;
+  return 0;
+}
+
+extern "C" int ua2_sample_topp(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                               const int32_t* forbid, uint64_t seed, const int32_t* counter, int32_t stream_id, int32_t* out_tokens,
+                               int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h,
+                               int32_t row_key_shift, float top_p, int32_t* keep_count, void* stream) {
+  int nucleus = 0;
+  unsigned long long P = 0ull;
+  if (int rc = topp_arguments("ua2_sample_topp", V, top_p, &nucleus, &P)) return rc;
+  if (!nucleus && !keep_count)                   // off and nothing to count: the top-k launch itself
+    return ua2_sample_topk(dtype, M, logits, ld, V, topk, temperature, forbid, seed, counter, stream_id, out_tokens, out_ld, out_col, emb,
+                           emb_row_offset, C, next_h, row_key_shift, stream);
+  UA2_CHECK(M > 0 && logits && V > 0 && out_tokens && counter && row_key_shift >= 0 && row_key_shift <= 1, "ua2_sample_topp: bad arguments");
+  UA2_CHECK(temperature > 0.f, "temperature must be > 0");
+  UA2_CHECK(topk >= 1 && topk <= V, "topk must be in 1..%d", V);
+  UA2_CHECK(!emb || next_h, "ua2_sample_topp: next_h is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == UA2_BF16)
+    hipLaunchKernelGGL((sample_topp_kernel<UA2_BF16>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid,
+                       (unsigned long long)seed, counter, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h, row_key_shift,
+                       nucleus, P, keep_count);
+  else if (dtype == UA2_F32)
+    hipLaunchKernelGGL((sample_topp_kernel<UA2_F32>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid,
+                       (unsigned long long)seed, counter, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h, row_key_shift,
+                       nucleus, P, keep_count);
+  else {
+    ua2_set_error("ua2_sample_topp: bad dtype %d", dtype);
+    return -1;
+  }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_sample_topp_rows(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,
+                                    const int32_t* forbid, const int32_t* row_key, const int32_t* row_draw, int32_t stream_id,
+                                    int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
+                                    int32_t C, float* next_h, float top_p, int32_t* keep_count, void* stream) {
+  int nucleus = 0;
+  unsigned long long P = 0ull;
+  if (int rc = topp_arguments("ua2_sample_topp_rows", V, top_p, &nucleus, &P)) return rc;
+  if (!nucleus && !keep_count)
+    return ua2_sample_topk_rows(dtype, M, logits, ld, V, topk, temperature, forbid, row_key, row_draw, stream_id, out_tokens, out_ld, out_col,
+                                emb, emb_row_offset, C, next_h, stream);
+  UA2_CHECK(M > 0 && logits && V > 0 && out_tokens && row_key && row_draw, "ua2_sample_topp_rows: bad arguments");
+  UA2_CHECK(temperature > 0.f, "temperature must be > 0");
+  UA2_CHECK(topk >= 1 && topk <= V, "topk must be in 1..%d", V);
+  UA2_CHECK(!emb || next_h, "ua2_sample_topp_rows: next_h is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == UA2_BF16)
+    hipLaunchKernelGGL((sample_topp_rows_kernel<UA2_BF16>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid, row_key,
+                       row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h, nucleus, P, keep_count);
+  else if (dtype == UA2_F32)
+    hipLaunchKernelGGL((sample_topp_rows_kernel<UA2_F32>), dim3(M), dim3(1024), 0, s, logits, ld, V, topk, temperature, forbid, row_key,
+                       row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h, nucleus, P, keep_count);
+  else {
+    ua2_set_error("ua2_sample_topp_rows: bad dtype %d", dtype);
     return -1;
   }
   UA2_LAUNCH_CHECK();

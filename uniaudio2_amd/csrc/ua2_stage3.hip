@@ -19,10 +19,10 @@
 
 namespace {
 // What a recorded frame bakes in beyond the plan's own state (the setters drop the graphs with theirs).  mode: without its flag bits;
-// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only; row_streams: top-k frames only
+// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only; row_streams, topp_bits: top-k frames only (topp_bits 0 = off)
 struct FrameKey {
-  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams;
-  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams); }
+  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits;
+  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits); }
   bool operator<(const FrameKey& o) const { return tied() < o.tied(); }
 };
 }  // namespace
@@ -80,6 +80,7 @@ struct ua2_stage3 {
   int32_t npart_t, npart_a;
   int32_t topk = 1;            // 1 = greedy (fused arg-max partials); > 1 = ua2_sample_topk
   float temperature = 1.f;
+  float top_p = 0.f;           // 0 < top_p < 1 with topk > 1: the samplers run the nucleus tail (ua2_sample_topp); 0 / 1 = off
   hipStream_t cap_stream = nullptr;                 // capture-only stream (the caller's may be the null stream, which cannot capture)
   float cfg_scale = 1.f;       // > 1: classifier-free guidance over a (conditional, unconditional) row pair
   int32_t order_free_rows = 0; // > 0 (bf16 plans): GPT launches (trunk and depth decoder) of at least this many rows take UA2_SUM_ORDER_FREE (ua2_stage3_set_order_free_rows)
@@ -781,6 +782,13 @@ extern "C" int ua2_stage3_set_sampling(ua2_stage3* h, int32_t topk, float temper
   return 0;
 }
 
+extern "C" int ua2_stage3_set_top_p(ua2_stage3* h, float top_p) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_top_p: NULL handle");
+  UA2_CHECK(top_p >= 0.f && top_p <= 1.f, "ua2_stage3_set_top_p: top_p must be in [0, 1] (0 and 1 = off), got %g", (double)top_p);
+  h->top_p = top_p;            // selects among the recorded frames (FrameKey.topp_bits): nothing to drop
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_prefill_groups(ua2_stage3* h, const int32_t* group_rows, const int32_t* group_seq, const int32_t* group_nkeys,
                                              int32_t n_groups, int32_t group_q_tiles) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_prefill_groups: NULL handle");
@@ -956,7 +964,14 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   const int key_shift = cfg ? 1 : 0;                       // the two rows of a pair hold the same guided logits and draw the same numbers
   // the frame's samplers: per-row streams when set (the caller gives both rows of a pair one key: no key shift), else the executor's one
   // seed and draw index with the row index in the key
+  const bool nucleus = h->top_p > 0.f && h->top_p < 1.f;
   auto sample = [&](const float* logits, int ld, int V, int topk, const int32_t* forbid, int stream_id, const void* emb, int emb_off, float* next_h) -> int {
+    if (nucleus && h->row_streams)
+      return ua2_sample_topp_rows(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, h->row_key, h->row_draw, stream_id, d.out_tokens, w,
+                                  stream_id, emb, emb_off, C, next_h, h->top_p, nullptr, s);
+    if (nucleus)
+      return ua2_sample_topp(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, 0, d.counters + 1, stream_id, d.out_tokens, w, stream_id, emb,
+                             emb_off, C, next_h, key_shift, h->top_p, nullptr, s);
     if (h->row_streams)
       return ua2_sample_topk_rows(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, h->row_key, h->row_draw, stream_id, d.out_tokens, w,
                                   stream_id, emb, emb_off, C, next_h, s);
@@ -1125,6 +1140,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   key.ngram_n = mode == 1 ? h->ngram_n : 0; key.eos = reason_eos; key.card = reason_card; key.topk = h->topk;
   memcpy(&key.temp_bits, &h->temperature, sizeof(int)); memcpy(&key.cfg_bits, &h->cfg_scale, sizeof(int));
   key.row_streams = (h->row_streams && h->topk != 1) ? 1 : 0;     // greedy frames neither read nor advance the streams
+  if (h->topk != 1 && h->top_p > 0.f && h->top_p < 1.f) memcpy(&key.topp_bits, &h->top_p, sizeof(int));   // (0 < top_p < 1: never the bits of 0)
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     hipGraph_t graph = nullptr;

@@ -71,6 +71,10 @@ class GeneratorBase:
     # feed it back under text_mask = False): the on-device loop skips lm_head + its sample there (ua2hip.h
     # UA2_FRAME_SKIP_TEXT_HEAD; identical (reason, semantic)).  UA2_KEEP_TEXT_HEAD=1 computes it as the reference does.
     skip_text_head = os.environ.get("UA2_KEEP_TEXT_HEAD") is None
+    # Nucleus (top-p) filter of every sampled loop (CLI --top_p; llm_utils/sampling.py:66-82): 0.0 = off.  It applies where the loop
+    # samples (topk > 1): the audio loops, single and batched (row seeds, admission, guided pairs), and the text loops; greedy loops
+    # ignore it.  Pure nucleus sampling is topk = the audio vocabulary width.
+    top_p = 0.0
 
     def __init__(self, model, train_args, audio_tokenizer_config=None, audio_model_path=None,
                  text_tokenizer_path=None, is_cfg=False):
@@ -184,6 +188,11 @@ class GeneratorBase:
     # ---- loops ----------------------------------------------------------------------------------
     def _set_sampling(self, topk, temperature):
         self._model.set_sampling(topk, temperature)
+        # nucleus filter (Model_stage3.set_top_p): the model hears of it only while it is on, and once more to turn it off
+        top_p = float(self.top_p)
+        if top_p != 0.0 or getattr(self, "_top_p_set", 0.0) != 0.0:
+            self._model.set_top_p(top_p)
+            self._top_p_set = top_p
 
     def _prefill(self, rows_tokens, rows_mask):
         """rows_*: list of (L, 9) prompts of equal length (1, or 2 with CFG; tts_task.py:228-245)."""

@@ -206,6 +206,7 @@ class Model_stage3(nn.Module):
         self.sampling_seed = None      # set by callers that key the sampler themselves (CLI: per-utterance keys)
         self.weight_dtype = None       # torch.float8_e4m3fn: every bf16 plan setup_caches builds computes with the fp8 weight-only forms W' and streams fp8 images in its few-row launches (CLI --weight_dtype)
         self.order_free_rows = 0       # > 0: every plan setup_caches builds opts its many-row launches into the order-free GEMM (CLI --order_free_rows)
+        self.top_p = 0.0               # set_top_p: nucleus filter of the sampled heads (0 = off), re-applied to every plan setup_caches builds
 
     # ---- caches / device plan ----------------------------------------------------------------
     def setup_caches(self, max_batch_size: int, dtype: Optional[torch.dtype] = None, max_seq_length: int = 2048,
@@ -297,6 +298,8 @@ class Model_stage3(nn.Module):
         self._row_streams = False      # per-row sampler streams registered with the executor (set_row_seeds)
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
             self.set_order_free_rows(self.order_free_rows)
+        if getattr(self, "top_p", 0.0) > 0.0:
+            self.set_top_p(self.top_p)         # a new plan starts with the filter off: re-apply what set_top_p remembered
         if weight_dtype is not None:
             for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert, self.decoder):
                 w8 += g.plan["w8"]
@@ -590,6 +593,19 @@ class Model_stage3(nn.Module):
             # a new key rewinds the draw index on the device; the same key keeps counting (like a global generator)
             check(lib.ua2_stage3_set_sampling(self._h, key[0], key[1], key[2], ops.stream()), "ua2_stage3_set_sampling")
             self._sampling = key
+
+    def set_top_p(self, top_p: float = 0.0):
+        """Nucleus (top-p) filter of the sampled heads (llm_utils/sampling.py:66-82; include/ua2hip.h ua2_sample_topp): with
+        set_sampling(topk > 1, ...) and 0 < top_p < 1 every sampler keeps, among its top-k columns, those whose strictly-more-probable
+        mass is at most top_p of the kept mass (ties at the threshold all kept), then draws as before.  0.0 (the default) and 1.0 are
+        off; pure nucleus sampling is topk = the audio vocabulary width.  Greedy frames and beam search ignore it.  The value is
+        remembered and re-applied to every plan setup_caches builds."""
+        top_p = float(top_p)
+        if not 0.0 <= top_p <= 1.0:            # (NaN fails both comparisons)
+            raise ValueError(f"top_p must be in [0, 1] (0 = off), got {top_p}")
+        self.top_p = top_p
+        if self._h is not None:
+            check(lib.ua2_stage3_set_top_p(self._h, top_p), "ua2_stage3_set_top_p")
 
     def set_row_seeds(self, seeds, rows=None):
         """Per-row sampler streams (include/ua2hip.h ua2_stage3_set_row_streams): row rows[i] (default i) of the decode state draws

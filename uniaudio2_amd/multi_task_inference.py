@@ -17,6 +17,9 @@ Differences, all explicit:
     per GPU at a time, and gathered with one RCCL all-gather (uniaudio2_amd/parallel.py); rank 0 writes.
   * --topk > 1 samples on the device with a counter-based generator seeded by --seed: reproducible, same
     distribution as the reference's sample_topk, but not torch's random stream.
+  * `--top_p P` (default 0 = off) adds the nucleus filter of the reference's llm_utils/sampling.py sample_top_p to every sampled loop,
+    on the device, after the --topk threshold; ties at the threshold value are all kept.  Pure nucleus sampling is --topk = the audio
+    vocabulary width (--topk 0 stays refused).  Outside [0, 1] it raises ValueError before a model is built.
   * --decode_type ngram (ASR / Yue_ASR: generate_asr_with_ngram_sampling, greedy, n = 3, as the reference's :310-322) runs the
     n-gram filter on the device; its prefill is generate_asr's (the reference's trains-mode prefill leaves the experts' caches
     empty, evaluation/asr_task.py).  lyric_recognition + ngram raises ValueError (the reference's lyric Generator has no such
@@ -176,6 +179,22 @@ def _generation_method_name(task):
     raise ValueError(f"Unknown generation task: {task}")
 
 
+def _check_top_p(args):
+    """--top_p: 0.0 = off, (0, 1) = the nucleus filter, 1.0 = off as well; anything else (NaN included) is refused before a model is built."""
+    top_p = float(getattr(args, "top_p", 0.0) or 0.0)
+    if not 0.0 <= top_p <= 1.0:
+        raise ValueError(f"--top_p must be in [0, 1] (0 = off), got {top_p}")
+    return top_p
+
+
+def _apply_top_p(args, generator):
+    """The generator hears of --top_p only when it is set: with the default nothing new is called anywhere."""
+    top_p = _check_top_p(args)
+    if top_p != 0.0:
+        generator.top_p = top_p
+    return generator
+
+
 def _check_decode(args):
     if args.decode_type != "greedy":
         raise NotImplementedError("--decode_type ngram/beamsearch are not on the device path (greedy only this round)")
@@ -288,6 +307,7 @@ def _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names,
 def run_understanding(args):
     task = args.task.strip().lower()
     _check_understanding_decode(args, task)
+    _check_top_p(args)
     raw_audio = _has_raw_audio(args)
     if raw_audio:
         token_dir, names = args.output_dir, []
@@ -303,6 +323,7 @@ def run_understanding(args):
     generator = _get_generator_class(task)(model, train_args, audio_tokenizer_config=args.audio_tokenizer_config,
                                            audio_model_path=args.audio_model_path, text_tokenizer_path=args.text_tokenizer_path,
                                            is_cfg=args.use_cfg)
+    _apply_top_p(args, generator)
     if raw_audio:
         token_dir, names = _encode_audio_to_tokens(args, generator, args.output_dir, "pass --reason_pt + --semantic_pt or --token_dir")
     beam_batch = int(getattr(args, "batch_size", 1) or 1) if int(getattr(args, "beam_width", 0) or 0) >= 1 else 1
@@ -363,6 +384,7 @@ def run_generation_stage1(args):
     from . import parallel
     task = args.task.strip().lower()
     _check_decode(args)
+    _check_top_p(args)
     os.makedirs(args.output_dir, exist_ok=True)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -371,6 +393,7 @@ def run_generation_stage1(args):
     generator = _get_generator_class(task)(model, train_args, audio_tokenizer_config=args.audio_tokenizer_config,
                                            audio_model_path=args.audio_model_path, text_tokenizer_path=args.text_tokenizer_path,
                                            is_cfg=args.use_cfg)
+    _apply_top_p(args, generator)
     tok = generator._text_tokenizer
     task_prompt = _get_prompt_tensor(args, tok, args.task)
     if task == "speech_s2s":
@@ -572,6 +595,11 @@ def get_parser():
     p.add_argument("--use_cfg", type=str2bool, default=False)
     p.add_argument("--temperature", type=float, default=0.9)
     p.add_argument("--topk", type=int, default=50)
+    p.add_argument("--top_p", type=float, default=0.0,
+                   help="nucleus sampling (extension; the rule of the reference's llm_utils/sampling.py sample_top_p): among the --topk most "
+                        "probable ids keep those whose strictly-more-probable mass is at most this share of the kept mass (ties at the "
+                        "threshold all kept), then draw.  0 = off (default), as is 1; it acts where --topk does (no effect on greedy loops).  "
+                        "Pure nucleus sampling: --topk = the audio vocabulary width (reason + semantic cardinality)")
     p.add_argument("--cfg_scale", type=float, default=1.0)
     p.add_argument("--decode_type", type=str, default="greedy", choices=["greedy", "ngram", "beamsearch"])
     p.add_argument("--codec_steps", type=int, default=50)
@@ -612,6 +640,7 @@ def get_parser():
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
+    _check_top_p(args)
     task = args.task.strip().lower()
     if task in [t.lower() for t in UNDERSTANDING_TASKS]:
         has_input = ((args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)) or
