@@ -1,5 +1,5 @@
 """Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py, tests/test_gpu_attn_flash_parity.py and
-tests/test_gpu_rowwise.py.
+tests/test_gpu_rowwise.py (and, through tests/encoder_refs.py, by tests/test_gpu_encoder_parity.py).
 
 Every helper takes `dt`: torch.float64 is the reference a kernel is compared with; torch.float32 evaluates the SAME formula in
 plain fp32 on the host, whose error against the float64 result (`E_ref`) sizes the bar of a tolerance test:
@@ -74,9 +74,11 @@ class PagedCache:
         return K, V
 
 
-def attn_ref(q, K, V, pos, seq, n_head, n_kv, window=0, dt=F64):
+def attn_ref(q, K, V, pos, seq, n_head, n_kv, window=0, dt=F64, score_bias=None, q_prescaled=False):
     """softmax(q k^T / sqrt(hs)) v over keys max(0, pos + 1 - window) .. pos of the row's sequence.  q [R, n_head * hs];
-    K, V: per sequence [L, n_kv, hs], the values actually stored (already rounded to the cache dtype); pos, seq [R] ints."""
+    K, V: per sequence [L, n_kv, hs], the values actually stored (already rounded to the cache dtype); pos, seq [R] ints.
+    score_bias(rows, keys) -> [r, n_kv, G, l] in `dt` (rows: indices into the launch's rows, keys: positions) is added to the
+    scores before the mask; q_prescaled: q already carries 1 / sqrt(hs) (tests/encoder_refs.py: ua2_attn_relbias)."""
     q = torch.as_tensor(q).to(dt)
     pos, seq = np.asarray(pos, dtype=np.int64), np.asarray(seq, dtype=np.int64)
     R, G = q.shape[0], n_head // n_kv
@@ -90,8 +92,12 @@ def attn_ref(q, K, V, pos, seq, n_head, n_kv, window=0, dt=F64):
         first = int(lo.min())
         Kb, Vb = K[b][first:n].to(dt), V[b][first:n].to(dt)                        # [n', n_kv, hs]
         qb = q[rows].view(len(rows), n_kv, G, hs)
-        s = torch.einsum("rkgd,lkd->rkgl", qb, Kb) / math.sqrt(hs)
+        s = torch.einsum("rkgd,lkd->rkgl", qb, Kb)
+        if not q_prescaled:
+            s = s / math.sqrt(hs)
         key = torch.arange(first, n)
+        if score_bias is not None:
+            s = s + score_bias(rows, key).to(dt)
         vis = (key[None, :] <= p[:, None]) & (key[None, :] >= lo[:, None])         # [r, n']
         s = s.masked_fill(~vis[:, None, None, :], float("-inf"))
         w = torch.softmax(s, dim=-1)
@@ -247,21 +253,25 @@ def causal_visible(key, pos):
 
 
 def attn_flash_model(q, K, V, pos, seq, n_head, n_kv, mode, keys_per_step=64, score_dt=torch.float32, dt=torch.float32,
-                     visible=causal_visible):
+                     visible=causal_visible, score_bias=None, q_prescaled=False):
     """The arithmetic contract of attn_flash_kernel (header comment in csrc/ua2_attn.hip), nothing of its lane layout:
     q * log2(e) / sqrt(hs) in fp32, rounded by `mode` ("split": 16 significant bits as bf16 hi + lo; "bf16": one bf16; "fp32":
     left alone); scores accumulated in `score_dt` and handed on in `dt`; keys visited in steps of `keys_per_step` with the running
     max / alpha / l recurrence on exp2; masked keys contribute exact zeros; l sums the unrounded weights; the weights entering
     P V are rounded by `mode`; O accumulates in `dt`.  dt = score_dt = float64 with mode "fp32" is attn_ref in another order.
     mode may be a pair (q rounder, p rounder) of names or callables, and `visible(key, pos)` another mask: the hooks with which
-    tests/test_kernel_refs.py builds deliberately wrong models."""
+    tests/test_kernel_refs.py builds deliberately wrong models.  score_bias(rows, keys) -> [r, n_kv, G, l] in `dt`, already in
+    the log2 domain, is added to the handed-on scores with one rounding before the mask; q_prescaled: q carries 1 / sqrt(hs)
+    already and is scaled by log2(e) alone (both: the contract of attn_relbias_flash_kernel, tests/encoder_refs.py)."""
     rq, rp = (mode, mode) if isinstance(mode, str) else mode
     rq, rp = ROUNDERS.get(rq, rq) if isinstance(rq, str) else rq, ROUNDERS.get(rp, rp) if isinstance(rp, str) else rp
     q = torch.as_tensor(q).to(dt)
     pos, seq = np.asarray(pos, dtype=np.int64), np.asarray(seq, dtype=np.int64)
     R, G = q.shape[0], n_head // n_kv
     hs = q.shape[1] // n_head
-    sc = torch.tensor(1.44269504088896340736, dtype=dt) / torch.sqrt(torch.tensor(float(hs), dtype=dt))
+    sc = torch.tensor(1.44269504088896340736, dtype=dt)
+    if not q_prescaled:
+        sc = sc / torch.sqrt(torch.tensor(float(hs), dtype=dt))
     qs = rq(q * sc)
     ninf = float("-inf")
     out = torch.zeros(R, n_head * hs, dtype=dt)
@@ -273,6 +283,8 @@ def attn_flash_model(q, K, V, pos, seq, n_head, n_kv, mode, keys_per_step=64, sc
         Vb = torch.where(torch.isnan(Vb), torch.zeros_like(Vb), Vb).to(dt)
         qb = qs[rows].view(len(rows), n_kv, G, hs)
         s_all = torch.einsum("rkgd,lkd->rkgl", qb.to(score_dt), Kb.to(score_dt)).to(dt)
+        if score_bias is not None:
+            s_all = s_all + score_bias(rows, torch.arange(n)).to(dt)
         vis = visible(torch.arange(n)[None, :], p[:, None])                               # [r, n]
         assert not bool(torch.isnan(torch.where(vis[:, None, None, :], s_all, torch.zeros_like(s_all))).any()), "a visible key is not stored"
         s_all = s_all.masked_fill(~vis[:, None, None, :], ninf)
