@@ -1,5 +1,6 @@
-"""Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py, tests/test_gpu_attn_flash_parity.py and
-tests/test_gpu_rowwise.py (and, through tests/encoder_refs.py, by tests/test_gpu_encoder_parity.py).
+"""Plain restatements of the row-wise kernels, used by tests/test_gpu_attn_decode.py (whose inputs and wrong models are in
+tests/attn_decode_cases.py), tests/test_gpu_attn_flash_parity.py and tests/test_gpu_rowwise.py (and, through tests/encoder_refs.py, by
+tests/test_gpu_encoder_parity.py).
 
 Every helper takes `dt`: torch.float64 is the reference a kernel is compared with; torch.float32 evaluates the SAME formula in
 plain fp32 on the host, whose error against the float64 result (`E_ref`) sizes the bar of a tolerance test:

@@ -1,12 +1,16 @@
 """The float64 references of tests/kernel_refs.py against the torch library functions they restate (CPU, float64, rtol 1e-12); the
 host model of the flash attention contract against attn_ref; the conditions every hostile input generator must meet; and a dry
 run in which deliberately wrong host models stand in for the device result of tests/test_gpu_attn_flash_parity.py and must
-fail its assertions."""
+fail its assertions; the same for the decode form: the inputs of tests/test_gpu_attn_decode.py (tests/attn_decode_cases.py), the
+conditions on its hostile generators, and the wrong models its bar must reject and the old 2e-4 did not."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import attn_decode_cases as dc
 import kernel_refs as kr
 
 RTOL = 1e-12
@@ -285,3 +289,94 @@ def test_wrong_packed_index_fails_the_packed_assertion():
         if dtype == torch.bfloat16:                      # not rounded to nearest: truncated
             trunc = kr.encode_packed((y.view(torch.int32) & -65536).view(torch.float32), dtype, fill)
             assert kr.packed_mismatch(trunc, y, R, K, dtype, fill) is not None
+
+
+# ---- the decode form: inputs, hostile generators and wrong models (tests/attn_decode_cases.py) -----------------------------------
+
+OLD_DECODE_BAR = 2e-4          # what tests/test_gpu_attn_decode.py asserted before it took kr.bar
+
+
+@functools.lru_cache(maxsize=None)
+def _decode_parity(nh, nkv, hs):
+    """The bf16 parity batch of the GPU module with its float64 reference, fp32 evaluation and bar, as that module computes them."""
+    cache, q, pos, seq = dc.parity_inputs(torch.bfloat16, nh, nkv, hs)
+    dc.check_indices(cache, pos, seq)
+    K, V = dc.stored(cache)
+    ref = kr.attn_ref(q, K, V, pos, seq, nh, nkv)
+    ref32 = kr.attn_ref(q, K, V, pos, seq, nh, nkv, dt=torch.float32)
+    return cache, q, pos, seq, K, V, ref, ref32
+
+
+@pytest.mark.parametrize("nh,nkv,hs", [(24, 8, 128), (4, 2, 32)])
+def test_decode_bar_rejects_wrong_models(nh, nkv, hs):
+    """Dry run of test_decode_attention_parity on the host, a wrong model standing in for the device.  The fp32 evaluation passes
+    its own bar by construction; q or the weights kept to 16 bits (the flash form's contract) and a score scale off by 2^-17 exceed
+    it, and all three lay below the 2e-4 the module used to assert; a read of the slot after row_pos exceeds it by more than 100x
+    because that slot holds LOUD (with a fill of 0.0 it is 20 .. 27x: the old caches would have shown it 100x fainter).
+    Measured x bar at 24/8/128 and 4/2/32: q16 1.8, 1.8; p16 2.0, 3.6; scale17 3.8, 5.8; stale_key 4.9e9, 8.6e9."""
+    cache, q, pos, seq, K, V, ref, ref32 = _decode_parity(nh, nkv, hs)
+    assert len(pos) == 766 and max(cache.lens) == 2047
+    scale = max(1.0, float(ref.abs().max()))
+    err, e_ref, bar = dc.unit_err(ref32, ref, ref32)
+    assert err == e_ref <= bar and bar < OLD_DECODE_BAR / 20
+    _close(dc.decode_wrong_model("none", q, K, V, pos, seq, nh, nkv), ref)
+    fill = float(cache.k[cache.table[0, 0], 0, cache.lens[0], 0])                 # the slot after the one-key sequence: as stored
+    assert fill == float(torch.tensor(dc.LOUD).to(cache.dtype)) and bool((cache.k[-1] == fill).all())
+    for kind in ("q16", "p16", "scale17"):
+        e = dc.unit_err(dc.decode_wrong_model(kind, q, K, V, pos, seq, nh, nkv), ref)[0]
+        assert e > bar, (kind, e / bar)
+        assert e * scale < OLD_DECODE_BAR, kind                                 # the old bar hid it
+    e = dc.unit_err(dc.decode_wrong_model("stale_key", q, K, V, pos, seq, nh, nkv, fill=fill), ref)[0]
+    assert e > 100.0 * bar, e / bar
+    y = ref32.clone()
+    y[5, 3] = float("nan")                                                      # an unwritten element
+    assert not dc.unit_err(y, ref)[0] <= bar
+
+
+def test_decode_case_generators_are_finite_and_in_range():
+    for lens, positions in ((dc.LENS, dc.positions), (dc.LONG_LENS, dc.long_positions)):
+        pos, seq = dc.rows(lens, positions, seed=1)
+        assert pos.dtype == np.int32 and seq.dtype == np.int32 and len(pos) == len(seq)
+        assert seq.min() >= 0 and seq.max() < len(lens) and pos.min() >= 0 and bool((pos < np.asarray(lens)[seq]).all())
+        for b, L in enumerate(lens):                                            # first and last position of every sequence
+            assert {0, L - 1} <= set(pos[seq == b].tolist())
+    p = dc.long_positions(8191)
+    assert {63, 64, 65, 4031, 4032, 4033, 4095, 4096, 4097, 8127, 8128, 8129, 8190} <= set(p.tolist()) and len(p) == 20
+    assert set(dc.long_positions(4097).tolist()) == {0, 63, 64, 65, 127, 128, 129, 4031, 4032, 4033, 4095, 4096}
+    cache, q, pos, seq = dc.parity_inputs(torch.float32, 4, 2, 32)
+    dc.check_indices(cache, pos, seq)
+    assert bool(torch.isfinite(q).all()) and bool(torch.isfinite(cache.k).all()) and bool(torch.isfinite(cache.v).all())
+    named = torch.zeros(cache.k.shape[0], dtype=torch.bool)
+    named[cache.table.long().reshape(-1)] = True
+    assert int((~named).sum()) == dc.EXTRA_PAGES and bool((cache.k[~named] == dc.LOUD).all()) and bool((cache.v[~named] == dc.LOUD).all())
+
+
+@pytest.mark.parametrize("kind", dc.HOSTILE_KINDS)
+@pytest.mark.parametrize("nh,nkv,hs", [(24, 8, 128), (8, 2, 32), (4, 4, 64)])
+def test_decode_hostile_inputs_keep_fp32_useful(nh, nkv, hs, kind):
+    """Every hostile kind is finite, its float64 reference and its plain-fp32 evaluation are finite, and E_ref (fp32 against float64,
+    relative to the row's max magnitude) is at most 1e-3: the bar 4 E_ref of the device test stays a statement about the kernel.
+    Measured E_ref over the three geometries and both cache dtypes: peaked_q 3.0e-6 .. 7.3e-6, dominant_key 1.1e-6 .. 1.6e-6,
+    wide_v 7.4e-7 .. 1.1e-6, equal_keys 9.2e-7 .. 1.5e-6, rising 2.5e-5 .. 4.5e-5, falling 3.0e-5 .. 5.6e-5, zero_q 6.2e-7 .. 8.0e-7,
+    common_offset 1.7e-5 .. 2.9e-5 (RAMP = 140, OFFSET = 90 needed no adjustment)."""
+    K, V, q, pos, seq = dc.hostile_inputs(kind, nh, nkv, hs)
+    assert len(pos) == sum(dc.HOSTILE_LENS) and all(bool(torch.isfinite(t).all()) for t in K + V + [q])
+    for dtype in (torch.bfloat16, torch.float32):
+        cache = dc.linear_cache(dc.HOSTILE_LENS, nkv, hs, dtype, 1, K, V)
+        dc.check_indices(cache, pos, seq)
+        Ks, Vs = dc.stored(cache)
+        ref = kr.attn_ref(q, Ks, Vs, pos, seq, nh, nkv)
+        ref32 = kr.attn_ref(q, Ks, Vs, pos, seq, nh, nkv, dt=torch.float32)
+        assert bool(torch.isfinite(ref).all()) and bool(torch.isfinite(ref32).all())
+        assert kr.rel_row_err(ref32, ref) <= 1e-3
+        if kind == "zero_q":
+            np.testing.assert_allclose(ref.numpy(), dc.mean_of_v(Vs, pos, seq, nh, nkv).numpy(), rtol=0, atol=1e-12)
+        r = int(np.nonzero((seq == 3) & (pos == 299))[0][0])
+        s = torch.einsum("kgd,lkd->kgl", q[r].view(nkv, nh // nkv, hs).to(F64), Ks[3]) / hs ** 0.5                 # natural units
+        if kind in ("rising", "falling"):
+            step = s[..., 16:] - s[..., :-16] if dtype == torch.bfloat16 else s[..., 1:] - s[..., :-1]            # bf16 keys plateau
+            assert bool((step > 0).all() if kind == "rising" else (step < 0).all())
+            assert float((s.amax(-1) - s.amin(-1)).min()) > 87.0                                                    # past exp2's underflow
+        if kind == "common_offset":
+            assert float(s.min()) > 70.0 and float(s.amax(-1).max()) > 89.0                                         # exp overflows fp32
+            assert 0.5 < float((s.amax(-1) - s.amin(-1)).max()) < 10.0                                              # a real soft-max remains
