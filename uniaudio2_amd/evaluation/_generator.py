@@ -389,6 +389,89 @@ class GeneratorBase:
                                             skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
         return [self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long)) for ids, _, _ in out]
 
+    @torch.inference_mode()
+    def _generate_text_batch(self, prompts, topk=1, temperature=1.0, max_frames=500, no_repeat_ngram_size=0, ngram_fallback=128000,
+                             seeds=None, batch_size=None):
+        """_generate_text for many utterances at once — the text twin of _generate_audio_tokens_batch (the reference decodes them one
+        by one, multi_task_inference.py:300-382): prompts = [(tokens (L_b, 9), mask (L_b, 9)), ...] of any lengths.  One ragged
+        prefill, then all live rows decode together in text-feedback chunks of `chunk_frames`; after each chunk the host scans every
+        live row's text column up to its first TEXT_EOS, exactly as _text_loop does, and retires the rows that met it or have run
+        their max_frames.  batch_size (default: all): at most that many utterances are live; a waiting one is admitted into the
+        running session (Model_stage3.admit_rows) at the first chunk boundary at which a row is free.
+        max_frames: an int, or one int per utterance.  no_repeat_ngram_size >= 2: the device n-gram filter is on for the call, every
+        row against its own history (capacity: the largest max_frames; an admitted row starts with an empty one).  seeds: one
+        sampler key per utterance (Model_stage3.set_row_seeds) — utterance b then draws what its own _generate_text draws under
+        set_sampling(topk, temperature, seed=seeds[b]), whatever shares its batch.  Greedy and n-gram-filtered texts, and sampled
+        ones under seeds, equal the one-by-one texts (row invariance).  Returns the decoded texts in input order."""
+        n_utt = len(prompts)
+        if seeds is not None and len(seeds) != n_utt:
+            raise ValueError(f"one seed per utterance: got {len(seeds)} seeds for {n_utt} utterances")
+        limit = [int(max_frames)] * n_utt if isinstance(max_frames, int) else [int(x) for x in max_frames]
+        if len(limit) != n_utt:
+            raise ValueError(f"max_frames: one int, or one per utterance; got {len(limit)} for {n_utt} utterances")
+        if n_utt == 0:
+            return []
+        if min(limit) < 1:
+            raise ValueError(f"max_frames must be >= 1 for every utterance, got {min(limit)}")
+        cap = n_utt if batch_size is None else max(1, min(int(batch_size), n_utt))      # live utterances = rows of the plan
+        row_of = lambda b: (prompts[b][0], prompts[b][1].bool())
+        keys_of = lambda seq: None if seeds is None else [seeds[b] for b in seq]
+        st = getattr(self._model, "_st", None)
+        longest, most = max(int(t.shape[0]) for t, _ in prompts), max(limit)
+        need_rows = sum(int(t.shape[0]) - 1 for t, _ in prompts[:cap])
+        if st is None or st["B"] < cap or st["max_rows"] < min(need_rows, 8192) or st["log_frames"] < most:
+            self._model.setup_caches(cap, max_rows=max(64, min(need_rows, 8192)), log_frames=max(512, most))
+        active, waiting = list(range(cap)), list(range(cap, n_utt))  # live utterances in row order; the queue
+        self._model.begin_ragged([row_of(b) for b in active])
+        self._set_sampling(topk, temperature)
+        ngram = no_repeat_ngram_size > 1
+        text = [[] for _ in range(n_utt)]
+        ran = [0] * n_utt                                            # frames run per utterance
+        used, log_frames = 0, self._model._st["log_frames"]          # log slots taken since the last rewind
+        # text-only continuation: see _text_loop.  The frame after the prefill, and the one after every admission, run whole
+        skip = os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None
+        try:
+            if ngram:
+                self._model.set_ngram(no_repeat_ngram_size, ngram_fallback, capacity=max(most, 1))
+            if seeds is not None:
+                self._model.set_row_seeds(keys_of(active))
+            while active:
+                n = min(self.chunk_frames, min(limit[b] - ran[b] for b in active))
+                if used + n > log_frames:                            # a session that admits outlives the log: every slice is on the host
+                    self._model.rewind_frame_log()
+                    used = 0
+                log = self._model.generate_frames(n, len(active), 1, max_pos=longest + most, skip_audio_experts=skip).cpu()   # (n, rows, 9)
+                used += n
+                keep = []
+                for r, b in enumerate(active):
+                    done = False
+                    for f in range(n):
+                        t = int(log[f, r, 0])
+                        if t == TEXT_EOS:
+                            done = True
+                            break
+                        text[b].append(t)
+                    ran[b] += n
+                    if not done and ran[b] < limit[b]:
+                        keep.append(r)
+                if len(keep) < len(active):
+                    self._model.retire_rows(keep, len(active))
+                    active = [active[r] for r in keep]
+                admit, waiting = waiting[:cap - len(active)], waiting[cap - len(active):]
+                if admit:
+                    self._model.admit_rows([row_of(b) for b in admit], len(active), seeds=keys_of(admit))
+                    active += admit
+        finally:
+            if seeds is not None:
+                self._model.set_row_seeds(None)
+            if ngram:
+                self._model.set_ngram(0)
+        return [self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long)) for ids in text]
+
+    def _text_twin(self, prepare, inputs, **kw):
+        """The body of every batched text method: inputs[b] = the arguments of the task's prepare_* method for utterance b."""
+        return self._generate_text_batch([prepare(*a) for a in inputs], **kw)
+
     def _text_loop(self, L, max_frames):
         text, frame, done = [], 0, False
         while not done and frame < max_frames:

@@ -60,8 +60,35 @@ class Generator(GeneratorBase):
         prompts = [self.prepare_asr_task(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)]
         return self._beam_search_text_batch(prompts, beam_width, length_penalty, max_length)
 
+    @torch.inference_mode()
+    def generate_asr_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, temperature: float = 0.9, topk: int = 200,
+                           cfg_scale=1.0, seeds=None, batch_size=None) -> list:
+        """generate_asr for several utterances at once (an extension: the reference decodes them one by one).  reason_tokens /
+        semantic_tokens: lists of (T, 8) tensors, one pair per utterance, argument order as generate_asr_beam_search_batch.  At most
+        batch_size utterances (default: all) are live in one decode session, a waiting one is admitted into a freed row
+        (_generate_text_batch).  Returns the texts in the order given — greedy (topk = 1): each the text generate_asr returns for
+        that utterance alone; sampled: under seeds, utterance b's run with the sampler keyed by seeds[b]."""
+        if len(reason_tokens) != len(semantic_tokens):
+            raise ValueError("one semantic tensor per reason tensor is needed")
+        return self._text_twin(self.prepare_asr_task, [(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)], topk=topk,
+                               temperature=temperature, seeds=seeds, batch_size=batch_size)
+
+    @torch.inference_mode()
+    def generate_asr_with_ngram_sampling_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, temperature: float = 0.9,
+                                               topk: int = 200, cfg_scale=1.0, no_repeat_ngram_size: int = 3,
+                                               repetition_penalty: float = 1.2, *, fallback_token: int = 128000, seeds=None,
+                                               batch_size=None) -> list:
+        """generate_asr_with_ngram_sampling for several utterances at once: generate_asr_batch with the device n-gram filter on, every
+        row against its own history (an admitted row starts with an empty one).  Each text is the one the single method returns."""
+        if len(reason_tokens) != len(semantic_tokens):
+            raise ValueError("one semantic tensor per reason tensor is needed")
+        return self._text_twin(self.prepare_asr_task, [(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)], topk=topk,
+                               temperature=temperature, no_repeat_ngram_size=no_repeat_ngram_size, ngram_fallback=fallback_token,
+                               seeds=seeds, batch_size=batch_size)
+
     # audio_music_caption_task.py uses the same prompt layout and loop under another name
     generate_audio_caption = generate_asr
+    generate_audio_caption_batch = generate_asr_batch
 
     @torch.inference_mode()
     def generate_answer(self, task_prompt, task_name, d=None, keys=None, types=None, temperature: float = 0.9,
@@ -69,3 +96,10 @@ class Generator(GeneratorBase):
         """audio_understanding.py:284-339."""
         tokens, mask = self.get_condition_seq(d, keys, types, task_prompt)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature)
+
+    @torch.inference_mode()
+    def generate_answer_batch(self, task_prompt, task_name, ds, keys, types, temperature: float = 0.9, topk: int = 200, cfg_scale=1.0,
+                              seeds=None, batch_size=None) -> list:
+        """generate_answer for several utterances at once: ds = one `d` per utterance, keys / types shared (_generate_text_batch)."""
+        return self._text_twin(self.get_condition_seq, [(d, keys, types, task_prompt) for d in ds], topk=topk, temperature=temperature,
+                               seeds=seeds, batch_size=batch_size)

@@ -19,6 +19,19 @@ class Generator(_AsrGenerator):
         tokens, mask = self.prepare_lyric_asr_task(task_prompt, reason_token, semantic_token)
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature)
 
+    @torch.inference_mode()
+    def generate_lyric_asr_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, temperature: float = 0.9, topk: int = 200,
+                                 cfg_scale=1.0, seeds=None, batch_size=None) -> list:
+        """generate_lyric_asr for several utterances at once (an extension; asr_task.Generator.generate_asr_batch): lists of (T, 8)
+        tensors in, the lyric texts out in the order given, each the text generate_lyric_asr returns for that utterance alone."""
+        if len(reason_tokens) != len(semantic_tokens):
+            raise ValueError("one semantic tensor per reason tensor is needed")
+        return self._text_twin(self.prepare_lyric_asr_task, [(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)],
+                               topk=topk, temperature=temperature, seeds=seeds, batch_size=batch_size)
+
+    # the command line calls generate_asr for this task as well (multi_task_inference.py:310-327), and so its batched form
+    generate_asr_batch = generate_lyric_asr_batch
+
     def generate_asr_beam_search(self, *args, **kwargs):
         """The reference's lyric Generator has no beam search either."""
         raise ValueError("beam search is not available for lyric_recognition: the reference's lyric Generator "
@@ -28,3 +41,5 @@ class Generator(_AsrGenerator):
         """The reference's lyric Generator has no n-gram variant (the CLI's `--decode_type ngram` fails there with AttributeError)."""
         raise ValueError("--decode_type ngram is not available for lyric_recognition: the reference's lyric Generator "
                          "(evaluation/lyric_asr_task.py) has no generate_asr_with_ngram_sampling")
+
+    generate_asr_with_ngram_sampling_batch = generate_asr_with_ngram_sampling       # refused alike

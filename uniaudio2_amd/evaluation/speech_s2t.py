@@ -28,3 +28,22 @@ class Generator(GeneratorBase):
         if tokens.shape[0] >= MAX_PROMPT_FRAMES:
             return -1, -1
         return self._generate_text(tokens, mask, topk=topk, temperature=temperature), 1
+
+    @torch.inference_mode()
+    def generate_answer_batch(self, task_prompt, task_name, ds, keys, types, temperature: float = 0.9, topk: int = 200, cfg_scale=1.0,
+                              seeds=None, batch_size=None) -> list:
+        """generate_answer for several utterances at once (an extension): ds = one `d` per utterance, keys / types shared.  Returns
+        one slot per utterance in the order given: (text, 1), or (-1, -1) for a prompt of MAX_PROMPT_FRAMES frames or more, which
+        takes no row of the session.  The task samples: seeds gives one sampler key per utterance (refused ones included, so the
+        list lines up with ds) — utterance b then draws what generate_answer draws for it alone under
+        set_sampling(topk, temperature, seed=seeds[b]), whatever shares its batch and whatever batch_size is."""
+        if seeds is not None and len(seeds) != len(ds):
+            raise ValueError(f"one seed per utterance: got {len(seeds)} seeds for {len(ds)} utterances")
+        prompts = [self.get_condition_seq(d, keys, types, task_prompt) for d in ds]
+        fits = [b for b, (t, _) in enumerate(prompts) if t.shape[0] < MAX_PROMPT_FRAMES]
+        texts = self._generate_text_batch([prompts[b] for b in fits], topk=topk, temperature=temperature,
+                                          seeds=None if seeds is None else [seeds[b] for b in fits], batch_size=batch_size)
+        out = [(-1, -1)] * len(ds)
+        for b, text in zip(fits, texts):
+            out[b] = (text, 1)
+        return out

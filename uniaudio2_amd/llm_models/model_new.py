@@ -291,9 +291,9 @@ class Model_stage3(nn.Module):
         self._w8_on = False            # fp8 twins attached (set_w8)
         self._order_free = 0           # set_order_free_rows
         self._pos_hi = 0
-        self._text_fed_back = False    # the last frame run was a text-feedback frame (every row now holds masks audio 0 / text 1)
+        self._text_fed_back = 0        # rows 0.._text_fed_back-1 were fed back by a text-feedback frame (they hold masks audio 0 / text 1); 0 = none known
         self._ngram = None             # (n, fallback, capacity) of the text frames' n-gram filter (set_ngram); None = off
-        self._ngram_hi = 0             # upper bound of every live row's n-gram history length (host side: no device sync)
+        self._ngram_rows = [0] * B     # per-row upper bounds of the n-gram history lengths (host side: no device sync), in row order
         self._beam = None              # the running beam search (begin_beams .. end_beams); None = off
         self._row_streams = False      # per-row sampler streams registered with the executor (set_row_seeds)
         if getattr(self, "order_free_rows", 0) > 0 and dtype == torch.bfloat16:
@@ -363,6 +363,15 @@ class Model_stage3(nn.Module):
         self._need()
         self._st["counters"][0:1].zero_()
 
+    @property
+    def _ngram_hi(self):
+        """Upper bound of the longest n-gram history of any row of the plan; assigning sets every row's bound."""
+        return max(self._ngram_rows, default=0)
+
+    @_ngram_hi.setter
+    def _ngram_hi(self, frames):
+        self._ngram_rows = [int(frames)] * len(self._ngram_rows)
+
     def _need(self):
         if self._h is None:
             raise TypeError("You need to call `model.setup_caches()`")
@@ -393,14 +402,14 @@ class Model_stage3(nn.Module):
         """tokens (R, 9) any int dtype, mask (R, 9) bool, pos (R,), seq (R,) -> device state."""
         st = self._st
         R = tokens.shape[0]
-        self._text_fed_back = False                # tokens / masks from outside: nothing is known about the rows' step kinds
+        self._text_fed_back = 0                    # tokens / masks from outside: nothing is known about the rows' step kinds
         st["tokens"][:R].copy_(tokens)
         st["mask"][:R].copy_(tokens_mask)
         st["row_pos"][:R].copy_(pos)
         st["row_seq"][:R].copy_(seq)
         if "ngram_len" in st:                      # rows that start here start with an empty n-gram history
             st["ngram_len"][:R].zero_()
-            self._ngram_hi = 0
+            self._ngram_hi = 0                     # (every row: a session starts here)
         return R
 
     def _run_chunks(self, tk, mk, ps, sq, chunk, groups, after=None):
@@ -737,9 +746,12 @@ class Model_stage3(nn.Module):
                 raise ValueError(f"beam step log full: {bm['steps']} + {n_frames} steps > max_length {bm['cap']} (begin_beams)")
             bm["steps"] += n_frames
         if mode == 1 and self._ngram is not None:
-            # every text frame appends one id to each row's n-gram history: never filter against a truncated one
-            if self._ngram_hi + n_frames > self._ngram[2]:
-                raise ValueError(f"n-gram history full: {self._ngram_hi} + {n_frames} frames > capacity {self._ngram[2]} (set_ngram)")
+            # every text frame appends one id to each live row's n-gram history: never filter against a truncated one.  The bound
+            # follows the rows (retire_rows permutes it, admit_rows starts a row at 0): a session that admits may run more frames
+            # in all than `capacity`, no row may
+            ngram_hi = max(self._ngram_rows[:batch], default=0)
+            if ngram_hi + n_frames > self._ngram[2]:
+                raise ValueError(f"n-gram history full: {ngram_hi} + {n_frames} frames > capacity {self._ngram[2]} (set_ngram)")
         start = int(st["counters"][0].item())
         if start + n_frames > st["log_frames"]:
             raise ValueError("frame log too small: raise log_frames in setup_caches")
@@ -752,7 +764,7 @@ class Model_stage3(nn.Module):
             self._check_positions(self._pos_hi + n_frames - 1)
         self._pos_hi += n_frames
         if mode == 1 and self._ngram is not None:
-            self._ngram_hi += n_frames
+            self._ngram_rows[:batch] = [k + n_frames for k in self._ngram_rows[:batch]]
         s = ops.stream()
         cap_rows = self._defer_cap_rows(batch, mode, n_frames, skip_text_head) if defer_text_head else 0
         flush_after = {f0 + n - 1: (f0, n) for f0, n in defer_windows(start, n_frames, batch, cap_rows)} if cap_rows else {}
@@ -760,7 +772,7 @@ class Model_stage3(nn.Module):
             # skip_audio_experts (text-only continuations: asr_task.py:666-682 and twins): from the session's SECOND text-feedback frame on
             # every row is a text step fed back by the executor itself (masks audio 0 / text 1) — the first frame consumes the prompt's
             # last token, which may be an audio step, and runs whole.  UA2_FRAME_SKIP_AUDIO_EXPERTS = 32.
-            m = mode | 32 if (skip_audio_experts and self._text_fed_back) else mode
+            m = mode | 32 if (skip_audio_experts and batch <= self._text_fed_back) else mode
             if cap_rows and i < n_frames - 1:
                 m = mode | 64                      # UA2_FRAME_DEFER_TEXT_HEAD
             check(lib.ua2_stage3_frame(self._h, batch, m, reason_eos, reason_card, int(use_graph), s),
@@ -768,7 +780,7 @@ class Model_stage3(nn.Module):
             if start + i in flush_after:           # the frame filled the ring's last slot, or is the call's last deferred one
                 f0, n = flush_after[start + i]
                 check(lib.ua2_stage3_text_flush(self._h, batch, f0, n, s), "ua2_stage3_text_flush")
-            self._text_fed_back = mode in (1, 3)
+            self._text_fed_back = batch if mode in (1, 3) else 0       # rows past `batch` may still hold a prompt's audio step
             if frame_events is not None:           # measurement hook: one event after every frame (bench.py p50 / p99)
                 frame_events[i].record()
         return st["frame_log"][start:start + n_frames, :batch]
@@ -815,6 +827,9 @@ class Model_stage3(nn.Module):
         for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert):
             pt = g.kv_cache.page_table
             pt[:batch] = pt[:batch][perm]
+        self._ngram_rows[:batch] = [self._ngram_rows[r] for r in keep + gone]
+        # the survivors are text-fed-back rows only if every permuted row was one; the rows behind them are not vouched for any more
+        self._text_fed_back = len(keep) if batch <= self._text_fed_back else 0
         return len(keep)
 
     # the per-row decode state: what retire_rows permutes and admit_rows keeps across its prefill
@@ -851,13 +866,14 @@ class Model_stage3(nn.Module):
             raise ValueError(f"row streams are on (set_row_seeds): admit_rows needs one seed per prompt, got {seeds}")
         # the prefill loads its chunks through rows 0.. of these (_load_rows): whole copies, the live rows among them
         saved = {k: st[k].clone() for k in ("tokens", "mask", "row_pos", "row_seq", "ngram_len") if k in st}
-        ngram_hi = self._ngram_hi
+        ngram_rows = list(self._ngram_rows)
         pre = [i for i in range(n) if Ls[i] > 1]
         if pre:
             self.forward_prefix_ragged([prompts[i][0][:-1] for i in pre], [prompts[i][1][:-1] for i in pre], seq_ids=[batch + i for i in pre])
         for k, v in saved.items():
             st[k].copy_(v)
-        self._ngram_hi = ngram_hi
+        self._ngram_rows = ngram_rows
+        self._ngram_rows[batch:batch + n] = [0] * n      # as on the device: an admitted row starts with an empty history
         new = slice(batch, batch + n)
         st["tokens"][new] = torch.stack([t[-1] for t, _ in prompts]).to(torch.int32)
         st["mask"][new] = torch.stack([m[-1] for _, m in prompts]).to(torch.uint8)
@@ -869,7 +885,7 @@ class Model_stage3(nn.Module):
         if self._row_streams:
             self.set_row_seeds(seeds, rows=range(batch, batch + n))
         self._pos_hi = max(self._pos_hi, max(Ls) - 1)
-        self._text_fed_back = False        # the admitted rows' first frame is a prompt step: the next frame runs whole
+        self._text_fed_back = 0            # the admitted rows' first frame is a prompt step: the next frame runs whole
         return batch + n
 
     @torch.inference_mode()

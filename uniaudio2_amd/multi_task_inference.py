@@ -32,8 +32,15 @@ Differences, all explicit:
     `--batch_size N` together with --beam_width W decodes the utterances of --token_dir / --audio_dir in chunks of N, the N beams as
     row groups of one frame (Generator.generate_asr_beam_search_batch): the same results file as --batch_size 1 on the default plan,
     in the order of the names, missing files skipped as before.  N * W is at most 64 (ValueError otherwise); the plan holds 2 * N * W
-    sequences — 128 sequences at 2048 positions are about 35 GB of K/V at the released sizes (135 kB per position).  Without
-    --beam_width the understanding tasks ignore --batch_size, as before.
+    sequences — 128 sequences at 2048 positions are about 35 GB of K/V at the released sizes (135 kB per position).
+  * `--batch_size N` without --beam_width decodes the understanding tasks in batches too (greedy and --decode_type ngram ASR /
+    Yue_ASR, lyric_recognition, audio_caption / music_caption, audio_understanding, speech_s2t): the utterances of --token_dir /
+    --audio_dir that exist go into ONE `generate_*_batch` call — one decode session of at most N rows (N is clamped to the number of
+    utterances), a row retired at its EOS and a waiting utterance admitted into it at the next chunk boundary — and the results file
+    has one line per utterance in the order of the names.  Greedy and n-gram results files are byte-identical to --batch_size 1.
+    speech_s2t samples: with N > 1 utterance i (its index among the names) draws under its own key, parallel.utterance_seed(--seed, i),
+    so its text is the same for every N >= 2 and equals its single run under that key; --batch_size 1 keeps the one-by-one loop and
+    its single sampler stream, whose draws depend on the utterances before.
     Any non-greedy --decode_type for the generation tasks raises NotImplementedError.  No trained checkpoint ships with this
     repository: the search is verified on toy and random weights, not for task quality.
   * Encoding raw audio (--audio / --audio_dir; the understanding tasks and the speech_s2s source) runs the codec's three frozen
@@ -304,6 +311,57 @@ def _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names,
     flush()
 
 
+def _understand_in_one_session(args, generator, task, task_prompt, token_dir, names, f_out):
+    """--batch_size N > 1 without --beam_width: the pairs that exist, in the order of names, through ONE generate_*_batch call — a
+    decode session of at most N rows with admission into freed rows (GeneratorBase._generate_text_batch); one results line per
+    utterance, in the order of names.  Greedy and n-gram tasks: the texts of the one-by-one loop.  speech_s2t: utterance i of names
+    samples under parallel.utterance_seed(--seed, i), whatever shares its batch."""
+    from . import parallel
+    items = []                                                   # (index in names, name, reason (T, 8), semantic (T, 8))
+    for i, name in enumerate(names):
+        pair = _load_token_pair(token_dir, name)
+        if pair is not None:
+            items.append((i, name, pair[0], pair[1]))
+    if not items:
+        return
+    kw = dict(temperature=args.temperature, cfg_scale=args.cfg_scale, batch_size=int(args.batch_size))
+    if task == "audio_understanding":
+        question = _question(args)
+        q = torch.tensor(generator._text_tokenizer.tokenize(question), dtype=torch.long)
+        ds = [{"text_seq_question": q, "reason_seq": r.transpose(0, 1), "semantic_seq": s.transpose(0, 1)} for _, _, r, s in items]
+        texts = generator.generate_answer_batch(task_prompt, task_name=task, ds=ds, keys=list(ds[0]), types=["text", "audio", "audio"],
+                                                topk=1, **kw)
+    elif task == "speech_s2t":                                   # samples with --topk: one key per utterance
+        ds = [{"reason_seq": r, "semantic_seq": s} for _, _, r, s in items]
+        texts = generator.generate_answer_batch(task_prompt, task_name="speech_s2t", ds=ds, keys=["reason_seq", "semantic_seq"],
+                                                types=["audio", "audio"], topk=args.topk,
+                                                seeds=[parallel.utterance_seed(args.seed, i) for i, _, _, _ in items], **kw)
+    else:
+        method = ("generate_audio_caption_batch" if task in ("audio_caption", "music_caption") else
+                  "generate_asr_with_ngram_sampling_batch" if args.decode_type == "ngram" else "generate_asr_batch")
+        texts = getattr(generator, method)(task_prompt, task_name=task, reason_tokens=[r for _, _, r, _ in items],
+                                           semantic_tokens=[s for _, _, _, s in items], topk=1, **kw)
+    if len(texts) != len(items):
+        raise RuntimeError(f"the batched decode returned {len(texts)} texts for {len(items)} utterances")
+    for (_, name, _, _), text_out in zip(items, texts):
+        if task == "speech_s2t":
+            if text_out == (-1, -1):
+                print(f"[Skip] {name}: sequence too long for speech_s2t")
+                continue
+            text_out = text_out[0] if isinstance(text_out, tuple) else text_out
+        f_out.write(f"{name}\t{text_out}\n")
+        print(f"[{task}] {name} -> {text_out[:80]}...")
+
+
+def _question(args):
+    """--question, else the text of --question_file, else the reference's default (:345-349)."""
+    question = (args.question or "").strip()
+    if not question and args.question_file and os.path.isfile(args.question_file):      # :345-347
+        with open(args.question_file, "r", encoding="utf-8") as f:
+            question = f.read().strip()
+    return question or "What is described in this audio?"
+
+
 def run_understanding(args):
     task = args.task.strip().lower()
     _check_understanding_decode(args, task)
@@ -336,17 +394,16 @@ def run_understanding(args):
         if beam_batch > 1:                                       # asr, yue_asr under --beam_width (checked above)
             _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names, f_out)
             names = []
+        elif int(getattr(args, "beam_width", 0) or 0) < 1 and int(getattr(args, "batch_size", 1) or 1) > 1:
+            _understand_in_one_session(args, generator, task, task_prompt, token_dir, names, f_out)
+            names = []
         for name in names:
             pair = _load_token_pair(token_dir, name)
             if pair is None:
                 continue
             reason, semantic = pair                              # (T, 8)
             if task == "audio_understanding":
-                question = (args.question or "").strip()
-                if not question and args.question_file and os.path.isfile(args.question_file):      # :345-347
-                    with open(args.question_file, "r", encoding="utf-8") as f:
-                        question = f.read().strip()
-                question = question or "What is described in this audio?"
+                question = _question(args)
                 d = {"text_seq_question": torch.tensor(generator._text_tokenizer.tokenize(question), dtype=torch.long),
                      "reason_seq": reason.transpose(0, 1), "semantic_seq": semantic.transpose(0, 1)}
                 text_out = generator.generate_answer(task_prompt, task_name=task, d=d, keys=list(d), types=["text", "audio", "audio"],
@@ -634,7 +691,12 @@ def get_parser():
                    help="utterances decoded together per GPU (extension; 1 = one by one as the reference).  TTS / Yue_TTS / TTA / TTM / LTS / "
                         "InstructTTS with --text_file: at most N live utterances per GPU, waiting ones admitted into freed rows; greedy and sampled output "
                         "independent of N.  ASR / Yue_ASR with --beam_width W: chunks of N utterances per beam-search frame, N * W <= 64; "
-                        "the K/V plan then holds 2 * N * W sequences (128 sequences at 2048 positions: about 35 GB at the released sizes)")
+                        "the K/V plan then holds 2 * N * W sequences (128 sequences at 2048 positions: about 35 GB at the released sizes).  "
+                        "The understanding tasks without --beam_width (ASR / Yue_ASR greedy or --decode_type ngram, lyric_recognition, the "
+                        "caption tasks, audio_understanding, speech_s2t): the utterances of --token_dir / --audio_dir decode in one session of "
+                        "at most N rows (N is clamped to their number), a finished row taken by the next waiting utterance; greedy and ngram "
+                        "results equal --batch_size 1 byte for byte; speech_s2t then samples utterance i under its own key (--seed and i), the "
+                        "same text for every N >= 2")
     return p
 
 
