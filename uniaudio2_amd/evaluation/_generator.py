@@ -19,6 +19,8 @@ import os
 
 import torch
 
+from ..llm_models.model_new import admitting_session
+
 SPECIAL_TOKENS = {'<think>': 128002, '</think>': 128003, '</answer>': 128005,
                   '<transcription>': 128011, '</transcription>': 128012, '<lyric>': 128013,
                   '</lyric>': 128014, '<caption>': 128015, '</caption>': 128016, '<answer>': 128017,
@@ -243,13 +245,22 @@ class GeneratorBase:
         de_reason, de_sem = ph.result()
         return de_reason.to(self.device), de_sem.to(self.device)
 
+    def _size_plan(self, prompts, cap, per, frames):
+        """The model's plan for a batched session: `cap` live utterances of `per` rows each, the ragged prefill of the first `cap`
+        prompts (at most 8192 rows a pass) and a frame log for the `frames` one utterance may run.  A plan that is large enough is kept."""
+        st = getattr(self._model, "_st", None)
+        need_rows = per * sum(int(t.shape[0]) - 1 for t, _ in prompts[:cap])
+        if st is None or st["B"] < per * cap or st["max_rows"] < min(need_rows, 8192) or st["log_frames"] < frames:
+            self._model.setup_caches(per * cap, max_rows=max(64, min(need_rows, 8192)), log_frames=max(512, frames))
+
     @torch.inference_mode()
     def _generate_audio_tokens_batch(self, prompts, topk=1, temperature=1.0, max_audio_frames=500, cfg_prompts=None, seeds=None,
                                      batch_size=None):
         """Many utterances at once on one GPU (the reference loops over them one by one,
         multi_task_inference.py:510): prompts = [(tokens (L_b, 9), mask (L_b, 9)), ...] of any lengths.  One ragged prefill,
-        then all sequences decode together in device-side chunks; after each chunk the host runs every sequence's own
-        phase / EOS bookkeeping (the same PhaseSplitter as the single-utterance loop) and retires the finished ones.
+        then all sequences decode together in device-side chunks (model_new.admitting_session is the loop); after each
+        chunk the host runs every sequence's own phase / EOS bookkeeping (the same PhaseSplitter as the single-utterance
+        loop) and retires the finished ones.
         batch_size (default: all): at most that many utterances are live; a waiting one is admitted into the running session
         (Model_stage3.admit_rows) at the first chunk boundary at which a row is free, and runs its own max_audio_frames.
         seeds: one sampler key per utterance (Model_stage3.set_row_seeds) — utterance b then draws what its own single run
@@ -277,49 +288,20 @@ class GeneratorBase:
             return []
         cap = n_utt if batch_size is None else max(1, min(int(batch_size), n_utt))      # live utterances
         rows_of = lambda b: [(t, m.bool()) for t, m in ([prompts[b], cfg_prompts[b]] if self.is_cfg else [prompts[b]])]
-        keys_of = lambda seq: None if seeds is None else [seeds[b] for b in seq for _ in range(per)]
-        B = per * cap                                                # rows of the plan
-        st = getattr(self._model, "_st", None)
+        self._size_plan(prompts, cap, per, max_audio_frames)
         longest = max(int(t.shape[0]) for t, _ in prompts)
-        need_rows = per * sum(int(t.shape[0]) - 1 for t, _ in prompts[:cap])
-        if st is None or st["B"] < B or st["max_rows"] < min(need_rows, 8192) or st["log_frames"] < max_audio_frames:
-            self._model.setup_caches(B, max_rows=max(64, min(need_rows, 8192)), log_frames=max(512, max_audio_frames))
-        active, waiting = list(range(cap)), list(range(cap, n_utt))  # live utterances in row(-pair) order; the queue
-        self._model.begin_ragged([p for b in active for p in rows_of(b)])
-        self._set_sampling(topk, temperature)
-        if seeds is not None:
-            self._model.set_row_seeds(keys_of(active))
         splitters = [PhaseSplitter(self.reason_eos, self.semantic_eos, self.audio_reason_card) for _ in range(n_utt)]
-        ran = [0] * n_utt                                            # frames run per utterance
-        used, log_frames = 0, self._model._st["log_frames"]          # log slots taken since the last rewind
-        try:
-            while active:
-                n = min(self.chunk_frames, min(max_audio_frames - ran[b] for b in active))
-                if used + n > log_frames:                            # a session that admits outlives the log: every slice is on the host
-                    self._model.rewind_frame_log()
-                    used = 0
-                log = self._model.generate_frames(n, per * len(active), 2 if self.is_cfg else 0, reason_eos=self.reason_eos,
-                                                  reason_card=self.audio_reason_card, max_pos=longest + max_audio_frames,
-                                                  skip_text_head=self.skip_text_head).cpu()       # (n, rows, 9)
-                used += n
-                keep = []
-                for r, b in enumerate(active):
-                    row = per * r                                    # the utterance's (conditional) row
-                    for f in range(n):
-                        if not splitters[b].push(log[f, row:row + 1, 1:]):
-                            break
-                    ran[b] += n
-                    if not splitters[b].done and ran[b] < max_audio_frames:
-                        keep.append(r)
-                self._model.retire_rows([per * r + j for r in keep for j in range(per)], per * len(active))
-                active = [active[r] for r in keep]
-                admit, waiting = waiting[:cap - len(active)], waiting[cap - len(active):]
-                if admit:
-                    self._model.admit_rows([p for b in admit for p in rows_of(b)], per * len(active), seeds=keys_of(admit))
-                    active += admit
-        finally:
-            if seeds is not None:
-                self._model.set_row_seeds(None)
+        run = lambda n, rows: self._model.generate_frames(n, rows, 2 if self.is_cfg else 0, reason_eos=self.reason_eos,
+                                                          reason_card=self.audio_reason_card, max_pos=longest + max_audio_frames,
+                                                          skip_text_head=self.skip_text_head).cpu()       # (n, rows, 9)
+
+        def take(b, log):                                            # the utterance's conditional row (tts_task.py:256-258)
+            for f in range(log.shape[0]):
+                if not splitters[b].push(log[f, 0:1, 1:]):
+                    break
+            return splitters[b].done
+        admitting_session(self._model, rows_of=rows_of, n_utt=n_utt, cap=cap, limit=[max_audio_frames] * n_utt, chunk=self.chunk_frames,
+                          seeds=seeds, run=run, take=take, start=lambda: self._set_sampling(topk, temperature))
         out = []
         for ph in splitters:
             try:
@@ -394,10 +376,10 @@ class GeneratorBase:
                              seeds=None, batch_size=None):
         """_generate_text for many utterances at once — the text twin of _generate_audio_tokens_batch (the reference decodes them one
         by one, multi_task_inference.py:300-382): prompts = [(tokens (L_b, 9), mask (L_b, 9)), ...] of any lengths.  One ragged
-        prefill, then all live rows decode together in text-feedback chunks of `chunk_frames`; after each chunk the host scans every
-        live row's text column up to its first TEXT_EOS, exactly as _text_loop does, and retires the rows that met it or have run
-        their max_frames.  batch_size (default: all): at most that many utterances are live; a waiting one is admitted into the
-        running session (Model_stage3.admit_rows) at the first chunk boundary at which a row is free.
+        prefill, then all live rows decode together in text-feedback chunks of `chunk_frames` (model_new.admitting_session); after
+        each chunk the host scans every live row's text column up to its first TEXT_EOS, exactly as _text_loop does, and retires
+        the rows that met it or have run their max_frames.  batch_size (default: all): at most that many utterances are live; a
+        waiting one is admitted into the running session (Model_stage3.admit_rows) at the first chunk boundary at which a row is free.
         max_frames: an int, or one int per utterance.  no_repeat_ngram_size >= 2: the device n-gram filter is on for the call, every
         row against its own history (capacity: the largest max_frames; an admitted row starts with an empty one).  seeds: one
         sampler key per utterance (Model_stage3.set_row_seeds) — utterance b then draws what its own _generate_text draws under
@@ -414,56 +396,29 @@ class GeneratorBase:
         if min(limit) < 1:
             raise ValueError(f"max_frames must be >= 1 for every utterance, got {min(limit)}")
         cap = n_utt if batch_size is None else max(1, min(int(batch_size), n_utt))      # live utterances = rows of the plan
-        row_of = lambda b: (prompts[b][0], prompts[b][1].bool())
-        keys_of = lambda seq: None if seeds is None else [seeds[b] for b in seq]
-        st = getattr(self._model, "_st", None)
         longest, most = max(int(t.shape[0]) for t, _ in prompts), max(limit)
-        need_rows = sum(int(t.shape[0]) - 1 for t, _ in prompts[:cap])
-        if st is None or st["B"] < cap or st["max_rows"] < min(need_rows, 8192) or st["log_frames"] < most:
-            self._model.setup_caches(cap, max_rows=max(64, min(need_rows, 8192)), log_frames=max(512, most))
-        active, waiting = list(range(cap)), list(range(cap, n_utt))  # live utterances in row order; the queue
-        self._model.begin_ragged([row_of(b) for b in active])
-        self._set_sampling(topk, temperature)
+        self._size_plan(prompts, cap, 1, most)
         ngram = no_repeat_ngram_size > 1
         text = [[] for _ in range(n_utt)]
-        ran = [0] * n_utt                                            # frames run per utterance
-        used, log_frames = 0, self._model._st["log_frames"]          # log slots taken since the last rewind
         # text-only continuation: see _text_loop.  The frame after the prefill, and the one after every admission, run whole
         skip = os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None
-        try:
+        run = lambda n, rows: self._model.generate_frames(n, rows, 1, max_pos=longest + most, skip_audio_experts=skip).cpu()   # (n, rows, 9)
+
+        def take(b, log):                                            # as _text_loop: the row's text column up to its first TEXT_EOS
+            for t in log[:, 0, 0].tolist():
+                if t == TEXT_EOS:
+                    return True
+                text[b].append(t)
+            return False
+
+        def start():
+            self._set_sampling(topk, temperature)
             if ngram:
                 self._model.set_ngram(no_repeat_ngram_size, ngram_fallback, capacity=max(most, 1))
-            if seeds is not None:
-                self._model.set_row_seeds(keys_of(active))
-            while active:
-                n = min(self.chunk_frames, min(limit[b] - ran[b] for b in active))
-                if used + n > log_frames:                            # a session that admits outlives the log: every slice is on the host
-                    self._model.rewind_frame_log()
-                    used = 0
-                log = self._model.generate_frames(n, len(active), 1, max_pos=longest + most, skip_audio_experts=skip).cpu()   # (n, rows, 9)
-                used += n
-                keep = []
-                for r, b in enumerate(active):
-                    done = False
-                    for f in range(n):
-                        t = int(log[f, r, 0])
-                        if t == TEXT_EOS:
-                            done = True
-                            break
-                        text[b].append(t)
-                    ran[b] += n
-                    if not done and ran[b] < limit[b]:
-                        keep.append(r)
-                if len(keep) < len(active):
-                    self._model.retire_rows(keep, len(active))
-                    active = [active[r] for r in keep]
-                admit, waiting = waiting[:cap - len(active)], waiting[cap - len(active):]
-                if admit:
-                    self._model.admit_rows([row_of(b) for b in admit], len(active), seeds=keys_of(admit))
-                    active += admit
+        try:
+            admitting_session(self._model, rows_of=lambda b: [(prompts[b][0], prompts[b][1].bool())], n_utt=n_utt, cap=cap, limit=limit,
+                              chunk=self.chunk_frames, seeds=seeds, run=run, take=take, start=start)
         finally:
-            if seeds is not None:
-                self._model.set_row_seeds(None)
             if ngram:
                 self._model.set_ngram(0)
         return [self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long)) for ids in text]

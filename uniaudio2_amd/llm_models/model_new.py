@@ -54,6 +54,8 @@ def backtrack_beam_log(log, slot):
     return ids[::-1]
 
 
+# The plan an admitting session follows, worked out ahead for fixed frame counts.  Nothing in the package plans ahead (admitting_session
+# decides after every chunk): the two functions are the reference the host tests hold the running loop to.
 def ragged_schedule(n_frames):
     """Continuous-batching plan for fixed per-sequence frame counts: yields (step, active, keep) — run `step` frames with
     the sequences `active` (original indices, in row order), then keep the rows at positions `keep` (in order) as rows
@@ -99,6 +101,60 @@ def _seed_words(seed):
     seed = int(seed) & (2 ** 64 - 1)
     s32 = lambda x: x - (1 << 32) if x >= (1 << 31) else x
     return [s32(seed & 0xFFFFFFFF), s32(seed >> 32)]
+
+
+def admitting_session(model, *, rows_of, n_utt, cap, limit, chunk, seeds, run, take, start=None):
+    """The loop of every batched generation (continuous batching with admission): at most `cap` of the `n_utt` utterances are live;
+    the first `cap` start together (begin_ragged) and a waiting one is admitted, in input order, at the first chunk boundary at
+    which a slot is free (admit_rows).  rows_of(b): the prompt rows of utterance b — one, or the (conditional, unconditional) pair;
+    an utterance's rows stay adjacent, survivors keep their order and the admitted follow them.  Utterance b runs at most limit[b]
+    frames from its own admission, in chunks of min(chunk, the least budget left among the live); run(n, rows) runs one chunk and
+    returns its log slice (n, rows, 9), copied out of the frame log; take(b, log_of_b) consumes the utterance's own rows of it and
+    returns True once b is finished.  An utterance leaves when `take` says so or when its budget is spent; retire_rows is called
+    only when somebody leaves.  seeds (or None): utterance b draws under seeds[b] on each of its rows (set_row_seeds, off again
+    when the session ends, also by an exception).  start(): whatever the caller sets up between begin_ragged and the row seeds.
+    The session may run more frames than log_frames: the log slot is rewound once the slices before it have been copied out.
+    The loop itself never synchronises with the device."""
+    if n_utt == 0:
+        return
+    if cap < 1:
+        raise ValueError(f"batch_size must be >= 1, got {cap}")
+    active, waiting = list(range(n_utt))[:cap], list(range(n_utt))[cap:]     # live utterances in row order; the queue
+    first = [p for b in active for p in rows_of(b)]
+    per = len(first) // len(active)
+    keys_of = lambda seq: None if seeds is None else [seeds[b] for b in seq for _ in range(per)]
+    model.begin_ragged(first)
+    ran = [0] * n_utt                                      # frames run per utterance
+    used, log_frames = 0, model._st["log_frames"]          # log slots taken since the last rewind (begin_ragged starts at 0)
+    try:
+        if start is not None:
+            start()
+        if seeds is not None:
+            model.set_row_seeds(keys_of(active))
+        while active:
+            n = min(chunk, min(limit[b] - ran[b] for b in active))
+            if n:                                          # (0: utterances of no frames at all, which only leave)
+                if used + n > log_frames:
+                    model.rewind_frame_log()               # every earlier slice has been copied out
+                    used = 0
+                log = run(n, per * len(active))
+                used += n
+            keep = []
+            for r, b in enumerate(active):
+                ran[b] += n
+                done = bool(n) and take(b, log[:, per * r:per * (r + 1)])
+                if not done and ran[b] < limit[b]:
+                    keep.append(r)
+            if len(keep) < len(active):
+                model.retire_rows([per * r + j for r in keep for j in range(per)], per * len(active))
+                active = [active[r] for r in keep]
+            admit, waiting = waiting[:cap - len(active)], waiting[cap - len(active):]
+            if admit:
+                model.admit_rows([p for b in admit for p in rows_of(b)], per * len(active), seeds=keys_of(admit))
+                active += admit
+    finally:
+        if seeds is not None:
+            model.set_row_seeds(None)
 
 
 DEFER_CAP_ROWS = 64     # include/ua2hip.h UA2_DEFER_CAP_ROWS: rows of the executor's stash ring
@@ -915,7 +971,7 @@ class Model_stage3(nn.Module):
         """Batched fixed-length generation with continuous batching: prompts[b] = (tokens (L_b, 9), mask (L_b, 9)),
         n_frames[b] frames for sequence b (deterministic stop).  A sequence leaves the batch the frame it
         finishes.  batch_size (default: all): at most that many sequences are live; a waiting prompt is admitted into a running
-        session at the first chunk boundary at which a row is free (admission_schedule, admit_rows).  seeds: per-row sampler
+        session at the first chunk boundary at which a row is free (admitting_session, admit_rows).  seeds: per-row sampler
         streams for the call, sequence b draws under seeds[b] (set_row_seeds).  Returns a list of (n_frames[b], 9) int32 id
         tensors (device), each bit-identical to the sequence's own B = 1 run — under top-k with seeds: its run under
         set_sampling(topk, T, seed=seeds[b]) — for any batch_size, on the default row-invariant plans.  The session may run more
@@ -923,36 +979,12 @@ class Model_stage3(nn.Module):
         B = len(prompts)
         assert len(n_frames) == B and (seeds is None or len(seeds) == B)
         st = self._st
-        plan = list(admission_schedule(n_frames, None if batch_size is None else min(int(batch_size), max(B, 1))))
-        if not plan:
-            return []
-        first = plan[0][1]
-        self.begin_ragged([prompts[b] for b in first])
-        dev = st["device"]
         out = [[] for _ in range(B)]
-        pick = lambda seq: None if seeds is None else [seeds[b] for b in seq]
-        if seeds is not None:
-            self.set_row_seeds(pick(first))
-        used = 0                                   # log slots taken since the last rewind (begin_ragged starts at 0)
-        try:
-            for step, active, keep, admit in plan:
-                n_act, done = len(active), 0
-                while done < step:
-                    n = min(step - done, st["log_frames"])
-                    if used + n > st["log_frames"]:
-                        self.rewind_frame_log()        # every earlier slice has been copied out
-                        used = 0
-                    log = self.generate_frames(n, n_act, mode, reason_eos, reason_card, skip_text_head=skip_text_head).clone()
-                    for r, b in enumerate(active):
-                        out[b].append(log[:, r])
-                    done, used = done + n, used + n
-                n_act = self.retire_rows(keep, n_act)
-                if admit:
-                    self.admit_rows([prompts[b] for b in admit], n_act, seeds=pick(admit))
-        finally:
-            if seeds is not None:
-                self.set_row_seeds(None)
-        return [torch.cat(o) if o else torch.zeros(0, st["ncb"] + 1, dtype=torch.int32, device=dev) for o in out]
+        run = lambda n, rows: self.generate_frames(n, rows, mode, reason_eos, reason_card, skip_text_head=skip_text_head).clone()
+        take = lambda b, log: out[b].append(log[:, 0])           # (None: nobody finishes before its count)
+        admitting_session(self, rows_of=lambda b: [prompts[b]], n_utt=B, cap=B if batch_size is None else min(int(batch_size), B),
+                          limit=[int(k) for k in n_frames], chunk=st["log_frames"], seeds=seeds, run=run, take=take)
+        return [torch.cat(o) if o else torch.zeros(0, st["ncb"] + 1, dtype=torch.int32, device=st["device"]) for o in out]
 
     def begin_decode(self, tokens, tokens_mask, input_pos, forbid_prefix=0):
         """Loads the first decode frame (the last prompt frame, tts_task.py:253-255) into the device state."""
