@@ -473,6 +473,12 @@ int ua2_cfg_mix(float* logits, int32_t ld, int32_t V, float scale, const int32_t
  * [1], [2] = low / high half of a 64-bit word added to `seed` (zeros for a purely by-value seed; the frame
  * executor keeps its seed there so that one captured graph serves every seed).  Reproducible under graph replay;
  * it does not reproduce torch's generator stream (parity with the reference is distributional).
+ * The draw, stated so that it can be replayed on the host (tests/sampler_refs.py does, id by id): for every kept column c,
+ *   r = Philox4x32-10(counter = (c, draw index, row part, stream_id), key = (lo, hi) of (seed + device seed word) mod 2^64),
+ *   x = r[0] >> 8,  u = fminf(RN(x + 0.5f) * 2^-24, 1 - 2^-24)  (fp32; strictly inside (0, 1): RN(x + 0.5f) is 2^24 at x = 2^24 - 1,
+ *   and u = 1.0f would make q = -0.0f and the score -inf for the very column that drew the smallest q),
+ *   q = -logf(u),  score = expf(l_c - mx) / q with mx = the largest admitted l;  the id is the arg-max, the LOWEST column among
+ *   equal scores.  Draw index and seed words are read as unsigned 32-bit values; the carry of the low into the high key half counts.
  * row_key_shift (0 or 1): the row part of the key is m >> row_key_shift — 1 makes the two rows of a guidance pair draw the
  * same numbers (they hold the same guided logits: both continue from one sample, model_new.py:622). */
 int ua2_sample_topk(int dtype, int32_t M, const float* logits, int32_t ld, int32_t V, int32_t topk, float temperature,

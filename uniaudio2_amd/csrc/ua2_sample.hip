@@ -183,7 +183,9 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     if constexpr (TOPP) ++kept;
     unsigned r[4];
     philox4x32((unsigned)c, draw, row_part, (unsigned)stream_id, (unsigned)seed, (unsigned)(seed >> 32), r);
-    const float u = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);    // (0, 1)
+    // (0, 1): x + 0.5 rounds to even from x = 2^23 on and reaches 2^24 at x = 2^24 - 1 — u == 1.0f, q == -0.0f, score == -inf for the
+    // column that drew the SMALLEST q — so the product is held at the largest fp32 below 1 (include/ua2hip.h; one draw in 2^24 changes)
+    const float u = fminf(((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
     const float q = -logf(u);                                                // Exp(1)
     const float score = expf(l - mx) / q;                                    // probs / q up to the softmax constant
     if (score > bv || (score == bv && c < bi)) { bv = score; bi = c; }
