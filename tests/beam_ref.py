@@ -47,11 +47,15 @@ def log_softmax64(row):
         return x, (x - m) - math.log(np.exp(x - m).sum())
 
 
-def rank(logits, beam, eos, alpha=0.6):
+def rank(logits, beam, eos, alpha=0.6, lp_n=None):
     """All candidates of one step, best first (stable), and per live row its W + 1 largest logits.  Candidate = (score, parent,
-    token or -1, fin, ids)."""
+    token or -1, fin, ids).  lp_n: the length of the device's table of 1 / lp — the rule with the length clamped at lp_n - 1, which is
+    what ua2_beam_state states for a table shorter than the search (the product's table is longer than max_length: no clamp)."""
     W = len(beam)
     cands, tops = [], []
+
+    def lp(L, alpha):
+        return ((5 + (L if lp_n is None else min(L, lp_n - 1))) / 6) ** alpha
     for j, b in enumerate(beam):
         if b.fin == FINISHED:
             cands.append((b.score, j, -1, FINISHED, b.ids))
@@ -70,12 +74,12 @@ def rank(logits, beam, eos, alpha=0.6):
     return sorted(cands, key=lambda c: c[0], reverse=True), tops       # stable: equal scores stay in candidate order (:560)
 
 
-def select(logits, beam, eos, alpha=0.6):
+def select(logits, beam, eos, alpha=0.6, lp_n=None):
     """One step.  logits [W, V] (rows of finished / dead slots are not read), beam: list of W Slots.  Returns (new beam, parents,
     fed-back ids (0 for a finished slot), margins) with margins = (gap between the W-th and the (W+1)-th candidate score, smallest gap
-    between a live row's W-th and (W+1)-th logit); inf where there is no (W+1)-th."""
+    between a live row's W-th and (W+1)-th logit); inf where there is no (W+1)-th.  lp_n: as in rank."""
     W = len(beam)
-    ranked, tops = rank(logits, beam, eos, alpha)
+    ranked, tops = rank(logits, beam, eos, alpha, lp_n)
     logit_gap = min([float(t[W - 1] - t[W]) for t in tops if t.size > W and np.isfinite(t[W - 1])], default=INF)
     score_gap = float(ranked[W - 1][0] - ranked[W][0]) if len(ranked) > W and np.isfinite(ranked[W - 1][0]) else INF
     new, parents, fed = [], [], []
@@ -142,3 +146,92 @@ def search(oracle, tokens, mask, W, eos, alpha=0.6, max_length=500, early_stoppi
             break
     best, final_gap = finish(beam)
     return dict(beam=beam, best=best, steps=steps, margins=(score_gap, logit_gap, final_gap))
+
+
+# ---- plain host restatements of csrc/ua2_beam.hip's two step kernels (tests/test_beam_refs_host.py, tests/test_gpu_beam_parity.py) ----
+def topw_ref(row, W):
+    """What beam_topw_kernel owes for one fp32 row: (ids of the W best columns under "larger value, then lower id" — a NaN ordered as
+    -inf, as rank() orders it —, float64 logp of those columns)."""
+    x, logp = log_softmax64(row)
+    kth = np.partition(x, x.size - W)[x.size - W]                       # the W-th largest value
+    idx = np.flatnonzero(x >= kth)                                      # ascending ids, every column tied with it included
+    ids = idx[np.argsort(-x[idx], kind="stable")][:W]
+    return ids.astype(np.int64), logp[ids]
+
+
+def logp32_replay(row, ids, width=1024, summed=None):
+    """The fp32 score contract of DESIGN.md §2 in numpy fp32: m = row maximum, S = `width` partial sums of exp(x - m) (column c in
+    partial c % width, ascending c, one rounded add per column) joined by the halving tree s = width / 2 .. 1, logp = f32(f32(x - m) -
+    f32(log S)).  numpy's fp32 exp and log stand for expf and logf: the replay states the order, not the device's last bit.  Its
+    error against log_softmax64 is E_ref.  summed: the number of leading columns that enter S (wrong models; default all)."""
+    f = np.float32
+    x = np.asarray(row, dtype=f).copy()
+    x[np.isnan(x)] = -INF
+    ids = np.asarray(ids, dtype=np.int64)
+    m = x.max()
+    if m == -INF:
+        return np.full(ids.size, -INF, f)
+    n = -(-x.size // width)
+    e = np.zeros(n * width, f)                                          # the columns past V add +0: no rounding
+    e[:x.size] = np.exp(x - m)
+    if summed is not None:
+        e[summed:] = 0
+    part = np.zeros(width, f)
+    for r in e.reshape(n, width):
+        part = part + r
+    s = width // 2
+    while s >= 1:
+        part[:s] = part[:s] + part[s:2 * s]
+        s //= 2
+    return ((x[ids] - m) - np.log(part[0])).astype(f)
+
+
+def _ninf32(v):
+    v = np.float32(v)
+    return v if v == v else np.float32(-INF)
+
+
+def select32(cand_logp, cand_id, beam_state, lp_inv, eos, W, lp_index=None, score=None, pick=None):
+    """beam_select_kernel in numpy fp32, from fp32 candidates.  cand_logp / cand_id: 8 entries per slot (slot j, rank r at j * 8 + r;
+    only a live slot's first W are read); beam_state: dict(score, fin, len: the W slots; step, done: ctrl[0], ctrl[1]; log_cap);
+    lp_inv: the fp32 table, lp_n = its length.  Candidates in slot order, a live slot's in rank order, a finished slot's one; a NaN is
+    -inf; Ln = L for the EOS id, else L + 1; score = f32(score + f32(logp * lp_inv[min(Ln, lp_n - 1)])); the W best, equal scores in
+    candidate order; slots without a candidate are dead (score -inf, parent = the slot, len 0).  The ids are taken as given (the
+    device's are clamped already).  Returns dict(score: fp32 bits, fin, len, parent, token: the fed-back ids, log: the W records of this
+    step or None outside the log's capacity, step, done).  lp_index / score / pick replace one stated operation each (wrong models)."""
+    f = np.float32
+    lp_index = lp_index or (lambda L, Ln, lp_n: min(Ln, lp_n - 1))
+    score = score or (lambda sc, lp, inv: f(sc) + f(f(lp) * f(inv)))    # numpy rounds each fp32 operation once
+    pick = pick or (lambda cs, left: max(left, key=lambda i: (cs[i], -i)))      # the first of the best
+    cand_logp, cand_id, lp_inv = np.asarray(cand_logp, dtype=f), np.asarray(cand_id), np.asarray(lp_inv, dtype=f)
+    cands = []                                                          # (score, parent, token, fin, len)
+    with np.errstate(all="ignore"):
+        for j in range(W):
+            fin, L, sc = int(beam_state["fin"][j]), max(int(beam_state["len"][j]), 0), f(beam_state["score"][j])
+            if fin == FINISHED:
+                cands.append((_ninf32(sc), j, -1, FINISHED, L))
+            elif fin == LIVE:
+                for r in range(W):
+                    k = int(cand_id[j * 8 + r])
+                    Ln = L if k == eos else L + 1
+                    s = score(sc, _ninf32(cand_logp[j * 8 + r]), lp_inv[lp_index(L, Ln, lp_inv.size)])
+                    cands.append((_ninf32(s), j, -1 if k == eos else k, FINISHED if k == eos else LIVE, Ln))
+    cs = [float(c[0]) for c in cands]
+    left = list(range(len(cands)))
+    out = dict(score=[], fin=[], len=[], parent=[], token=[], log=[])
+    for t in range(W):
+        s, par, tok, fin, L = f(-INF), t, -1, DEAD, 0
+        if left:
+            best = pick(cs, left)
+            left.remove(best)
+            s, par, tok, fin, L = cands[best]
+        bits = int(np.array(s, dtype=f).view(np.int32))
+        out["score"].append(bits); out["fin"].append(fin); out["len"].append(L); out["parent"].append(par)
+        out["token"].append(tok if fin == LIVE else 0)
+        out["log"].append([par, tok if fin == LIVE else -1, bits, fin])
+    step, done = int(beam_state["step"]), int(beam_state["done"])
+    if not 0 <= step < int(beam_state["log_cap"]):
+        out["log"] = None
+    out["done"] = step if all(x == FINISHED for x in out["fin"]) and done < 0 else done
+    out["step"] = step + 1
+    return out

@@ -67,12 +67,16 @@ __global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __
       if (beam_better(x, c, lv[kBeamMaxW - 1], li[kBeamMaxW - 1])) {
         float cv = x;
         int ci = c;
+        // the exchange as selects, not as a branch per entry: the branching form lost a column that TIED with entry 0 on its
+        // value and won on its id (only an -inf / NaN column against the empty list can, ids being ascending) in the generated
+        // code of the first column of an outer iteration, so a row with fewer than W finite entries named the wrong -inf columns
 #pragma unroll
-        for (int k = 0; k < kBeamMaxW; ++k)
-          if (beam_better(cv, ci, lv[k], li[k])) {
-            const float tv = lv[k]; const int ti = li[k];
-            lv[k] = cv; li[k] = ci; cv = tv; ci = ti;
-          }
+        for (int k = 0; k < kBeamMaxW; ++k) {
+          const bool b = beam_better(cv, ci, lv[k], li[k]);
+          const float tv = lv[k]; const int ti = li[k];
+          lv[k] = b ? cv : tv; li[k] = b ? ci : ti;
+          cv = b ? tv : cv; ci = b ? ti : ci;
+        }
       }
     }
   }
@@ -162,8 +166,15 @@ __global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, 
         const float lp = beam_finite_or_ninf(st.cand_logp[j * kBeamMaxW + r]);
         const bool is_eos = k == eos;
         const int Ln = is_eos ? L : L + 1;        // the EOS id is not part of the text
-        // score + logp / lp(len): the host's float64 1 / lp as fp32, one rounded product, one rounded sum (no contraction)
-        const float s = __fadd_rn(sc, __fmul_rn(lp, st.lp_inv[min(Ln, st.lp_n - 1)]));
+        // score + logp / lp(len): the host's float64 1 / lp as fp32, one rounded product, one rounded sum.  __fmul_rn / __fadd_rn
+        // are a plain * and + here, which the default -ffp-contract=fast fused into one v_fmac_f32 (a single rounding): the
+        // contraction is switched off for this statement instead
+        float s;
+        {
+#pragma clang fp contract(off)
+          const float prod = lp * st.lp_inv[min(Ln, st.lp_n - 1)];
+          s = sc + prod;
+        }
         cs[at] = beam_finite_or_ninf(s); cpar[at] = j; ctok[at] = is_eos ? -1 : k; cfin[at] = is_eos ? 1 : 0; clen[at] = Ln; taken[at] = 0;
       }
     }
