@@ -94,7 +94,7 @@ const char* ua2_last_error(void);
 int ua2_version(void);
 /* sizeof() of the ABI structs as this library was compiled, for a binding to check its own layout against:
  * which = 0 ua2_kv_geom, 1 ua2_linear_args, 2 ua2_attn_args, 3 ua2_conv1d_args, 4 ua2_gpt_desc, 5 ua2_stage3_desc,
- * 6 ua2_convtc_args; else 0. */
+ * 6 ua2_convtc_args, 7 ua2_beam_ngram; else 0. */
 size_t ua2_struct_size(int which);
 
 /* Number of elements (of `dtype`) in the packed form of an [N,K] Linear weight. */
@@ -611,6 +611,29 @@ int ua2_beam_step_groups(const float* logits, int32_t ld, int32_t V, int32_t W, 
 int ua2_beam_reorder_groups(int32_t W, int32_t G, const int32_t* parent, const int32_t* row_pos, int32_t pos_add,
                             const ua2_beam_pool* pools, int32_t n_pools, int32_t* const* tables, int32_t n_tables,
                             int32_t table_rows, int32_t max_pages, void* stream);
+/* The step under a no-repeat-n-gram ban (added under ABI v10 like the entry points above; opt-in — the reference's
+ * `_apply_ngram_constraint`, evaluation/asr_task.py:602-628, bans an always-empty set, and the entry points above reproduce that).
+ *   n: 0 = off, or 2 .. 16;  cap: ids one history holds (>= 1);
+ *   hist [G][2][8][cap] int32, caller-owned: per group two sets of 8 histories.  A step reads set (ctrl[0] & 1) of its group — slot
+ *   j's text ids h[0 .. L), L = len[j] — and writes the other set: for every new LIVE slot t the history of parent[t] plus the new id.
+ *   Finished and dead slots keep no history.  Start: len = 0, so the content of hist does not matter.
+ * The rule, for a live slot with L >= n:  p = h[L - n + 1 .. L),  ban = { h[i + n - 1] : 0 <= i <= L - n, h[i .. i + n - 1) == p }
+ * (the EOS id is never part of a history, hence never banned); the banned columns count as -inf in the row maximum, in S and in the
+ * top-W selection — mask, then softmax.  Everything else is the contract of ua2_beam_step above, so
+ *   - a banned step on a row x owes bit for bit what ua2_beam_step_groups owes on x with the banned columns overwritten by -inf;
+ *   - a group's result depends only on its own rows and histories.
+ * Finished and dead slots read no logits and ban nothing.  L < n bans nothing; a slot with L > cap is not filtered (like
+ * ua2_ngram_filter); nothing is written at or past cap; history ids are clamped into [0, V) before they index anything.  The logits
+ * are read-only: the ban is a bitmap over the V columns in shared memory ((V + 31) / 32 words <= 48 KB).
+ * ng == NULL or ng->n == 0: exactly ua2_beam_step_groups (the same two launches).  Checked before any launch: n in {0, 2 .. 16},
+ * cap >= 1, hist non-NULL when n >= 2.  Two launches (1024 threads per live row; 256 per group: the copy of the histories). */
+typedef struct ua2_beam_ngram {
+  int32_t n;
+  int32_t cap;
+  int32_t* hist;
+} ua2_beam_ngram;
+int ua2_beam_step_groups_ngram(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st,
+                               const ua2_beam_ngram* ng, int32_t* token, int32_t token_ld, void* stream);
 
 /* ---- codec: residual vector quantisation ------------------------------------------------ */
 
@@ -1018,6 +1041,11 @@ int ua2_stage3_set_beam(ua2_stage3* h, int32_t W, int32_t eos, const ua2_beam_st
  * G >= 1, G * W <= 64 and 2 G W <= max_batch.  A new G drops the captured frame graphs as a new W does. */
 int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
                                int32_t n_pools);
+/* The no-repeat-n-gram ban of the attached beam (ua2_beam_step_groups_ngram; opt-in): mode 3 frames then run the step under it.  Valid
+ * only while a beam is attached; ng is copied by value and hist ([G][2][8][cap] for the attached G) stays alive while set.  NULL or
+ * n == 0 = off.  Checked as ua2_beam_step_groups_ngram checks it.  A call that changes anything drops the captured frame graphs;
+ * every ua2_stage3_set_beam[_groups] call clears the ban, so it is set after the beam is attached and gone once it is detached. */
+int ua2_stage3_set_beam_ngram(ua2_stage3* h, const ua2_beam_ngram* ng);
 /* cfg_scale > 1: frames of (conditional, unconditional) row pairs — rows 2p, 2p + 1; an even row count — sample from the guided
  * logits (ua2_cfg_mix); feedback mode 2 continues every row from its pair's conditional row. */
 int ua2_stage3_set_cfg(ua2_stage3* h, float cfg_scale);
@@ -1065,7 +1093,8 @@ int ua2_stage3_feedback(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_e
  * lm_head, the beam step on its fp32 logits, the K/V fork, then the text feedback of mode 1 with the ids the step chose (tokens
  * (0 x n_cb, id), masks (0.., 1), row_pos += 1; the frame log's text column holds them).  Checked before any launch: a beam is
  * attached (the set_beam calls above) and R equals its G * W; no classifier-free guidance, no n-gram filter, top-k = 1.  The caller keeps the step
- * count within the state's log and length-penalty tables and every position within the caches. */
+ * count within the state's log and length-penalty tables and every position within the caches.  With ua2_stage3_set_beam_ngram set the
+ * step is ua2_beam_step_groups_ngram under that ban (the greedy loop's n-gram filter stays excluded). */
 int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t reason_eos, int32_t reason_card,
                      int32_t use_graph, void* stream);
 /* Rows of the stash ring in use: UA2_DEFER_CAP_ROWS, or UA2_DEFER_ROWS=n from the environment (clamped to 1 .. UA2_DEFER_CAP_ROWS; tests and

@@ -14,7 +14,13 @@ repository (DIR: the commit before the groups, built) â€” G x its ms per frame â
 opens the device; it starts one fresh process per checkout (baseline, groups, baseline again: the two baseline runs bracket the
 grouped one and show the drift of the box), and a baseline process uses only the single-search API (begin_beams, generate_frames,
 end_beams).
-python tools/ubench/beam_search.py --groups --baseline-root ../parent > profiles/beam_search_groups.txt"""
+python tools/ubench/beam_search.py --groups --baseline-root ../parent > profiles/beam_search_groups.txt
+
+--ngram --baseline-root DIR: the no-repeat-n-gram ban inside the beam (beam_search(no_repeat_ngram_size=3)) at (G, W) = (1, 5) and (8, 5):
+ms per mode-3 frame over 32 frames that start at step 34 and at step 468 (histories of about 50 and about 500 ids; the K/V is that much
+longer too, so every column is compared at the same step), 3 repeats each, for the baseline checkout (DIR: the commit before the ban,
+built), this checkout with the ban off, and with the ban on.  Processes as under --groups: baseline, this checkout, baseline again.
+python tools/ubench/beam_search.py --ngram --baseline-root ../parent > profiles/beam_ngram.txt"""
 import argparse
 import json
 import os
@@ -28,6 +34,8 @@ sys.path.insert(0, ROOT)
 import torch
 
 GROUPS = ((1, 8), (2, 8), (4, 8), (8, 8), (4, 4), (16, 4))
+NGRAM_GROUPS = ((1, 5), (8, 5))
+NGRAM_STARTS = (34, 468)                               # the timed frames start here: texts of 34 .. 66 and of 468 .. 500 ids
 
 
 def prompt(dev, n_text=15, n_reason=53, n_sem=128):
@@ -109,6 +117,21 @@ def group_frames(model, p, G, W, frames):
         model.end_beams_groups()
 
 
+def group_frames_at(model, p, G, W, frames, start, ngram=0):
+    """ms per frame over `frames` frames behind `start` untimed ones; ngram = 0 passes nothing (a baseline checkout has no such argument)."""
+    kw = dict(no_repeat_ngram_size=ngram) if ngram else {}
+    model.begin_beams_groups([p] * G, beam_width=W, max_length=start + frames + 1, eos_id=-1, **kw)
+    try:
+        done = 0
+        while done < start:
+            n = min(frames, start - done)
+            model.generate_frames(n, G * W, 3, skip_audio_experts=True)
+            done += n
+        return timed(lambda: model.generate_frames(frames, G * W, 3, skip_audio_experts=True)) / frames
+    finally:
+        model.end_beams_groups()
+
+
 def group_entry_points(model, p, G, W, calls=200):
     """us per ua2_beam_step_groups and per ua2_beam_reorder_groups (fills 1-2 and 62-63) inside a started search; the search is discarded."""
     import ctypes as C
@@ -148,6 +171,17 @@ def child(a):
     model = bench.build_model(dev, seed=0)
     p = prompt(dev)
     out = {}
+    if a.child in ("ngram-base", "ngram"):
+        for G, W in NGRAM_GROUPS:
+            model.setup_caches(2 * G * W, dtype=torch.bfloat16, max_seq_length=2048, max_rows=max(64, p[0].shape[0]),
+                               log_frames=max(NGRAM_STARTS) + a.frames + 8)     # the frame log counts on through a search
+            for n in ((0,) if a.child == "ngram-base" else (0, 3)):
+                for start in NGRAM_STARTS:
+                    run = lambda: group_frames_at(model, p, G, W, a.frames, start, n)
+                    run()                                                  # capture the graphs
+                    out[f"{G}x{W} n{n} @{start}"] = [run() for _ in range(a.repeats)]
+        print("RESULT " + json.dumps(out), flush=True)
+        return
     for G, W in ([(1, 8), (1, 4)] if a.child == "single" else GROUPS):
         model.setup_caches(2 * G * W, dtype=torch.bfloat16, max_seq_length=2048, max_rows=max(64, p[0].shape[0]), log_frames=a.frames + 8)
         run = (lambda: beam_frames(model, p, W, a.frames)) if a.child == "single" else (lambda: group_frames(model, p, G, W, a.frames))
@@ -157,18 +191,41 @@ def child(a):
     print("RESULT " + json.dumps(out), flush=True)
 
 
+def _spawn(a, mode, root):
+    root = os.path.abspath(root)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--root", root, "--frames", str(a.frames), "--repeats", str(a.repeats)]
+    print(f"[beam_search] measuring: {mode} ...", file=sys.stderr, flush=True)
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.child_timeout, cwd=root)
+    if r.returncode != 0:
+        sys.exit(f"the {mode} process ended with {r.returncode}: nothing further is started")
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+
+
+def ngram_report(a):
+    if not a.baseline_root or not os.path.isdir(os.path.join(a.baseline_root, "uniaudio2_amd")):
+        sys.exit("--ngram needs --baseline-root DIR: a built checkout of the commit to compare against")
+    base_a = _spawn(a, "ngram-base", a.baseline_root)
+    new = _spawn(a, "ngram", ROOT)
+    base_b = _spawn(a, "ngram-base", a.baseline_root)
+    fmt = lambda xs: " ".join(f"{x:.4f}" for x in xs)
+    print(f"released sizes, bf16, prompt of 196 frames per utterance, {a.frames} timed frames per run behind 34 / 468 untimed ones, {a.repeats} runs; "
+          "one process per checkout, in the order baseline, this checkout, baseline; ms per mode-3 frame")
+    for G, W in NGRAM_GROUPS:
+        for start in NGRAM_STARTS:
+            k = f"{G}x{W} n0 @{start}"
+            xa, xb, off, on = base_a[k], base_b[k], new[k], new[f"{G}x{W} n3 @{start}"]
+            base = min(xa + xb)
+            print(f"G = {G}, W = {W}, steps {start}..{start + a.frames}: baseline before {fmt(xa)} | after {fmt(xb)}; best {base:.4f}, spread of the six runs "
+                  f"{(max(xa + xb) - base) * 1e3:.1f} us ({(max(xa + xb) / base - 1) * 100:.2f} %)")
+            print(f"    ban off {fmt(off)}; best {min(off):.4f} ({(min(off) - base) * 1e3:+.1f} us, {(min(off) / base - 1) * 100:+.2f} % of the baseline's best)")
+            print(f"    ban on, n = 3 {fmt(on)}; best {min(on):.4f} ({(min(on) - min(off)) * 1e3:+.1f} us, {(min(on) / min(off) - 1) * 100:+.2f} % over the ban off)")
+
+
 def groups_report(a):
     if not a.baseline_root or not os.path.isdir(os.path.join(a.baseline_root, "uniaudio2_amd")):
         sys.exit("--groups needs --baseline-root DIR: a built checkout of the commit to compare against")
 
-    def spawn(mode, root):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", mode, "--root", root, "--frames", str(a.frames), "--repeats", str(a.repeats)]
-        print(f"[beam_search] measuring: {mode} ...", file=sys.stderr, flush=True)
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=a.child_timeout, cwd=root)
-        if r.returncode != 0:
-            sys.exit(f"the {mode} process ended with {r.returncode}: nothing further is started")
-        return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-
+    spawn = lambda mode, root: _spawn(a, mode, root)
     base_a = spawn("single", a.baseline_root)
     new = spawn("groups", ROOT)
     base_b = spawn("single", a.baseline_root)
@@ -197,13 +254,16 @@ def main():
     ap.add_argument("--groups", action="store_true", help="the batched search against the single search of --baseline-root")
     ap.add_argument("--baseline-root", default=None, help="--groups: a built checkout of the commit to compare against")
     ap.add_argument("--child-timeout", type=int, default=420, help="--groups: seconds one measuring process may take")
-    ap.add_argument("--child", choices=["single", "groups"], default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--ngram", action="store_true", help="the no-repeat-n-gram ban inside the beam against the search of --baseline-root")
+    ap.add_argument("--child", choices=["single", "groups", "ngram-base", "ngram"], default=None, help=argparse.SUPPRESS)
     ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         return child(a)
     if a.groups:
         return groups_report(a)
+    if a.ngram:
+        return ngram_report(a)
     import bench
     dev = torch.device("cuda")
     model = bench.build_model(dev, seed=0)

@@ -108,6 +108,11 @@ class BeamPool(C.Structure):
     _fields_ = [("pool", vp), ("table", i32), ("n_kv", i32), ("head_bytes", i32), ("reserved", i32)]
 
 
+class BeamNgram(C.Structure):
+    """ua2_beam_ngram: the no-repeat-n-gram ban of a beam step (n, the capacity of one history, hist [G][2][8][cap] int32)."""
+    _fields_ = [("n", i32), ("cap", i32), ("hist", vp)]
+
+
 ACT_NONE, ACT_PRELU, ACT_ELU, ACT_TANH, ACT_ROUND9 = 0, 1, 2, 3, 4
 EW_IDENTITY, EW_SILU, EW_SIGMOID, EW_TANH = 0, 1, 2, 3
 
@@ -205,6 +210,8 @@ _EXPORTS = {
     "ua2_beam_step_groups": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
     "ua2_beam_reorder_groups": (C.c_int, [i32, i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),
     "ua2_stage3_set_beam_groups": (C.c_int, [vp, i32, i32, i32, C.POINTER(BeamState), vp, i32]),
+    "ua2_beam_step_groups_ngram": (C.c_int, [vp, i32, i32, i32, i32, i32, C.POINTER(BeamState), C.POINTER(BeamNgram), vp, i32, vp]),
+    "ua2_stage3_set_beam_ngram": (C.c_int, [vp, C.POINTER(BeamNgram)]),
     "ua2_qknorm_rope_kv": (C.c_int, [C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, vp, C.POINTER(KvGeom), vp]),
     "ua2_stage3_scratch_floats": (C.c_size_t, [C.POINTER(Stage3Desc)]),
     "ua2_stage3_create": (C.c_int, [C.POINTER(Stage3Desc), C.POINTER(vp)]),
@@ -224,7 +231,7 @@ _EXPORTS = {
 }
 
 
-ABI_STRUCTS = (KvGeom, LinearArgs, AttnArgs, Conv1dArgs, GptDesc, Stage3Desc, ConvTcArgs)
+ABI_STRUCTS = (KvGeom, LinearArgs, AttnArgs, Conv1dArgs, GptDesc, Stage3Desc, ConvTcArgs, BeamNgram)
 
 
 def exported_symbols():

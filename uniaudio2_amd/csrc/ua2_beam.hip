@@ -15,6 +15,13 @@
 // log records per group); a group reads and writes only its own state, token rows, log and table rows.
 // Nothing is permuted on the device but page-table entries and at most one partial page per pool and slot; the text of a hypothesis
 // is recovered on the host by walking the step log backwards.
+//   ua2_beam_step_groups_ngram  beam_topw_ngram_kernel / beam_select_ngram_kernel: the same step under the no-repeat-n-gram ban
+//                                                  (opt-in).  The step itself needs a slot's text, and walking the log
+//                                                  would be one dependent load per id, so under the ban every group keeps two sets of
+//                                                  8 histories of `cap` ids: a step reads set ctrl[0] & 1 and writes the other one.
+//                                                  The ban is a bitmap over V in shared memory: the logits stay read-only.  The
+//                                                  kernels without the ban are instantiations of the same bodies with the ban
+//                                                  compiled out: their code is what it was.
 //
 // Reproducibility: the workgroup size of beam_topw_kernel (1024) is part of the contract — the sum of exponentials is 1024 strided
 // partial sums (column c goes to thread c % 1024, ascending c) joined by the fixed halving tree below, so a row's log-sum-exp has
@@ -33,16 +40,30 @@ constexpr int kMaxCand = kBeamMaxW * kBeamMaxW + kBeamMaxW;
 __device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
 __device__ __forceinline__ float beam_finite_or_ninf(float x) { return x == x ? x : -INFINITY; }   // a NaN is ordered as -inf
 
+// The no-repeat-n-gram ban of a step (ua2_beam_step_groups_ngram): what the ban variants of the two kernels read besides the state
+struct BeamBan {
+  int n, cap;
+  int32_t* hist;                                  // [G][2][8][cap]: set ctrl[0] & 1 of a group is read by a step, the other one written
+};
+
+// one column of a row as the passes below see it: a NaN is -inf, and under the ban so is a column whose bit is set
+template <bool kBan>
+__device__ __forceinline__ float beam_column(const float* __restrict__ row, int c, const uint32_t* ban) {
+  const float x = beam_finite_or_ninf(row[c]);
+  if constexpr (kBan) return ((ban[c >> 5] >> (c & 31)) & 1u) ? -INFINITY : x;
+  return x;
+}
+
 // fin: 0 live, 1 finished, 2 dead (a slot that holds no hypothesis: slots 1 .. W - 1 before the first step)
-__global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __restrict__ logits, int ld, int V, int W,
-                                                                 const int32_t* __restrict__ fin, float* __restrict__ cand_logp,
-                                                                 int32_t* __restrict__ cand_id) {
+// kBan: `ban` is a bitmap over the V columns in shared memory, filled by the caller (beam_topw_ngram_kernel) behind a barrier; the
+// three passes are the same code for both values, so a banned row owes the bits of the row with -inf in the banned columns
+template <bool kBan>
+__device__ __forceinline__ void beam_topw_row(const float* __restrict__ logits, int ld, int V, int W, int j, const uint32_t* ban,
+                                              float* __restrict__ cand_logp, int32_t* __restrict__ cand_id) {
   __shared__ float red[kTopwThreads];
   __shared__ float wv[kTopwThreads / 64];
   __shared__ int wi[kTopwThreads / 64];
   const int tid = threadIdx.x;
-  const int j = (blockIdx.x / W) * kBeamMaxW + blockIdx.x % W;   // row g * W + slot -> the slot's place in its group's state
-  if (fin[j] != 0) return;                       // the whole workgroup: finished and dead slots produce no candidates from logits
   const float* row = logits + (size_t)blockIdx.x * ld;
   float lv[kBeamMaxW];
   int li[kBeamMaxW];
@@ -56,7 +77,7 @@ __global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __
 #pragma unroll
     for (int u = 0; u < kTopwBatch; ++u) {
       const int c = base + u * kTopwThreads;
-      xs[u] = c < V ? beam_finite_or_ninf(row[c]) : -INFINITY;
+      xs[u] = c < V ? beam_column<kBan>(row, c, ban) : -INFINITY;
     }
 #pragma unroll
     for (int u = 0; u < kTopwBatch; ++u) {
@@ -95,7 +116,7 @@ __global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __
 #pragma unroll
       for (int u = 0; u < kTopwBatch; ++u) {
         const int c = base + u * kTopwThreads;
-        xs[u] = c < V ? beam_finite_or_ninf(row[c]) : -INFINITY;
+        xs[u] = c < V ? beam_column<kBan>(row, c, ban) : -INFINITY;
       }
 #pragma unroll
       for (int u = 0; u < kTopwBatch; ++u)                 // ascending c, one rounded sum per column
@@ -136,7 +157,51 @@ __global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __
   }
 }
 
-__global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, ua2_beam_state st, int32_t* __restrict__ token, int token_ld) {
+__global__ __launch_bounds__(kTopwThreads) void beam_topw_kernel(const float* __restrict__ logits, int ld, int V, int W,
+                                                                 const int32_t* __restrict__ fin, float* __restrict__ cand_logp,
+                                                                 int32_t* __restrict__ cand_id) {
+  const int j = (blockIdx.x / W) * kBeamMaxW + blockIdx.x % W;   // row g * W + slot -> the slot's place in its group's state
+  if (fin[j] != 0) return;                       // the whole workgroup: finished and dead slots produce no candidates from logits
+  beam_topw_row<false>(logits, ld, V, W, j, nullptr, cand_logp, cand_id);
+}
+
+// The step under the no-repeat-n-gram ban.  How the ban is applied: a bitmap over the V columns in shared memory ((V + 31) / 32
+// words: 16 KB at the released vocabulary), so the logits stay read-only.  The workgroup of a live row with L = len ids h[0 .. L) in
+// its group's read set compares the L - n + 1 windows h[i .. i + n - 1) with the prefix h[L - n + 1 .. L), the windows strided over the
+// 1024 threads, and sets the bit of h[i + n - 1] (clamped into [0, V)) where they are equal; then the passes of beam_topw_row run.
+// L < n bans nothing; L > cap is not filtered (the history no longer holds the suffix), like ua2_ngram_filter.
+__global__ __launch_bounds__(kTopwThreads) void beam_topw_ngram_kernel(const float* __restrict__ logits, int ld, int V, int W,
+                                                                       const int32_t* __restrict__ fin, const int32_t* __restrict__ len,
+                                                                       const int32_t* __restrict__ ctrl, BeamBan bn,
+                                                                       float* __restrict__ cand_logp, int32_t* __restrict__ cand_id) {
+  extern __shared__ uint32_t ban[];
+  const int tid = threadIdx.x, g = blockIdx.x / W, slot = blockIdx.x % W;
+  const int j = g * kBeamMaxW + slot;
+  if (fin[j] != 0) return;                       // finished and dead slots read no logits and ban nothing
+  for (int w = tid; w < (V + 31) / 32; w += kTopwThreads) ban[w] = 0u;
+  __syncthreads();
+  const int L = len[j], n = bn.n;
+  if (L >= n && L <= bn.cap) {
+    const int32_t* h = bn.hist + ((size_t)(g * 2 + (ctrl[g * 4] & 1)) * kBeamMaxW + slot) * bn.cap;
+    const int32_t* p = h + (L - n + 1);
+    for (int i = tid; i <= L - n; i += kTopwThreads) {
+      bool same = true;
+      for (int k = 0; k < n - 1; ++k) same = same && h[i + k] == p[k];
+      if (same) {
+        const int c = min(max(h[i + n - 1], 0), V - 1);
+        atomicOr(&ban[c >> 5], 1u << (c & 31));
+      }
+    }
+  }
+  __syncthreads();
+  beam_topw_row<true>(logits, ld, V, W, j, ban, cand_logp, cand_id);
+}
+
+// kBan: behind the selection the whole workgroup writes the histories of the new live slots into the set the step did not read —
+// slot t's = its parent's in the read set plus the new id (two slots may swap parents in one step: hence two sets)
+template <bool kBan>
+__device__ __forceinline__ void beam_select_group(int W, int V, int eos, ua2_beam_state st, int32_t* __restrict__ token, int token_ld,
+                                                  BeamBan bn) {
   __shared__ float cs[kMaxCand];
   __shared__ int cpar[kMaxCand], ctok[kMaxCand], cfin[kMaxCand], clen[kMaxCand], taken[kMaxCand];
   __shared__ float sscore[kBeamMaxW];
@@ -180,27 +245,54 @@ __global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, 
     }
   }
   __syncthreads();
-  if (tid != 0) return;
-  const int step = st.ctrl[0];
-  bool all_fin = true;
-  for (int t = 0; t < W; ++t) {                   // the W best; equal scores in candidate order (a stable descending sort)
-    int best = -1;
-    for (int i = 0; i < n; ++i)
-      if (!taken[i] && (best < 0 || cs[i] > cs[best])) best = i;
-    float s = -INFINITY;
-    int par = t, tok = -1, f = 2, L = 0;          // fewer candidates than slots (never after the first step): a dead slot
-    if (best >= 0) { taken[best] = 1; s = cs[best]; par = cpar[best]; tok = ctok[best]; f = cfin[best]; L = clen[best]; }
-    all_fin = all_fin && f == 1;
-    // every read of the old state is done (the candidates hold copies): write the new one
-    st.score[t] = s; st.fin[t] = f; st.len[t] = L; st.parent[t] = par;
-    token[(size_t)t * token_ld] = f == 0 ? min(max(tok, 0), V - 1) : 0;
-    if (step >= 0 && step < st.log_cap) {
-      int32_t* rec = st.log + ((size_t)step * W + t) * 4;
-      rec[0] = par; rec[1] = f == 0 ? min(max(tok, 0), V - 1) : -1; rec[2] = __float_as_int(s); rec[3] = f;
+  __shared__ int npar[kBeamMaxW], ntok[kBeamMaxW], nfin[kBeamMaxW], nlen[kBeamMaxW], nset;   // the selection, for the copy (kBan)
+  if (!kBan && tid != 0) return;
+  if (tid == 0) {
+    const int step = st.ctrl[0];
+    bool all_fin = true;
+    for (int t = 0; t < W; ++t) {                   // the W best; equal scores in candidate order (a stable descending sort)
+      int best = -1;
+      for (int i = 0; i < n; ++i)
+        if (!taken[i] && (best < 0 || cs[i] > cs[best])) best = i;
+      float s = -INFINITY;
+      int par = t, tok = -1, f = 2, L = 0;          // fewer candidates than slots (never after the first step): a dead slot
+      if (best >= 0) { taken[best] = 1; s = cs[best]; par = cpar[best]; tok = ctok[best]; f = cfin[best]; L = clen[best]; }
+      all_fin = all_fin && f == 1;
+      // every read of the old state is done (the candidates hold copies): write the new one
+      st.score[t] = s; st.fin[t] = f; st.len[t] = L; st.parent[t] = par;
+      token[(size_t)t * token_ld] = f == 0 ? min(max(tok, 0), V - 1) : 0;
+      if (step >= 0 && step < st.log_cap) {
+        int32_t* rec = st.log + ((size_t)step * W + t) * 4;
+        rec[0] = par; rec[1] = f == 0 ? min(max(tok, 0), V - 1) : -1; rec[2] = __float_as_int(s); rec[3] = f;
+      }
+      if constexpr (kBan) { npar[t] = par; ntok[t] = min(max(tok, 0), V - 1); nfin[t] = f; nlen[t] = L; }
+    }
+    if (all_fin && st.ctrl[1] < 0) st.ctrl[1] = step;
+    st.ctrl[0] = step + 1;
+    if constexpr (kBan) nset = step & 1;
+  }
+  if constexpr (kBan) {
+    __syncthreads();
+    int32_t* sets = bn.hist + (size_t)g * 2 * kBeamMaxW * bn.cap;
+    for (int t = 0; t < W; ++t) {
+      if (nfin[t] != 0) continue;                 // finished and dead slots need no history
+      const int Lp = nlen[t] - 1;                 // a live candidate is its parent's text plus one id
+      const int32_t* src = sets + ((size_t)nset * kBeamMaxW + min(max(npar[t], 0), W - 1)) * bn.cap;
+      int32_t* dst = sets + ((size_t)(nset ^ 1) * kBeamMaxW + t) * bn.cap;
+      for (int i = tid; i < min(Lp, bn.cap); i += blockDim.x) dst[i] = src[i];
+      if (tid == 0 && Lp >= 0 && Lp < bn.cap) dst[Lp] = ntok[t];     // nothing at or past cap
     }
   }
-  if (all_fin && st.ctrl[1] < 0) st.ctrl[1] = step;
-  st.ctrl[0] = step + 1;
+}
+
+__global__ __launch_bounds__(64) void beam_select_kernel(int W, int V, int eos, ua2_beam_state st, int32_t* __restrict__ token, int token_ld) {
+  beam_select_group<false>(W, V, eos, st, token, token_ld, BeamBan{});
+}
+
+constexpr int kSelectNgramThreads = 256;           // the copy of up to W * cap words is spread over them; the selection uses the first 64
+__global__ __launch_bounds__(kSelectNgramThreads) void beam_select_ngram_kernel(int W, int V, int eos, ua2_beam_state st,
+                                                                                int32_t* __restrict__ token, int token_ld, BeamBan bn) {
+  beam_select_group<true>(W, V, eos, st, token, token_ld, bn);
 }
 
 struct BeamTables {
@@ -280,6 +372,28 @@ extern "C" int ua2_beam_step_groups(const float* logits, int32_t ld, int32_t V, 
   hipLaunchKernelGGL(beam_topw_kernel, dim3(G * W), dim3(kTopwThreads), 0, s, logits, ld, V, W, st->fin, st->cand_logp, st->cand_id);
   UA2_LAUNCH_CHECK();
   hipLaunchKernelGGL(beam_select_kernel, dim3(G), dim3(64), 0, s, W, V, eos, *st, token, token_ld);
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ua2_beam_step_groups_ngram(const float* logits, int32_t ld, int32_t V, int32_t W, int32_t G, int32_t eos,
+                                          const ua2_beam_state* st, const ua2_beam_ngram* ng, int32_t* token, int32_t token_ld, void* stream) {
+  if (!ng) return ua2_beam_step_groups(logits, ld, V, W, G, eos, st, token, token_ld, stream);
+  UA2_CHECK(ng->n == 0 || (ng->n >= 2 && ng->n <= 16), "ua2_beam_step_groups_ngram: no_repeat_ngram_size must be 0 (off) or in 2..16, got %d", ng->n);
+  UA2_CHECK(ng->cap >= 1, "ua2_beam_step_groups_ngram: history capacity %d", ng->cap);
+  UA2_CHECK(ng->n == 0 || ng->hist, "ua2_beam_step_groups_ngram: NULL history buffer");
+  if (ng->n == 0) return ua2_beam_step_groups(logits, ld, V, W, G, eos, st, token, token_ld, stream);
+  if (int rc = check_state(st, W, G, "ua2_beam_step_groups_ngram")) return rc;
+  UA2_CHECK(logits && token && token_ld >= 1, "ua2_beam_step_groups_ngram: NULL logits / token buffer");
+  UA2_CHECK(V >= W && ld >= V, "ua2_beam_step_groups_ngram: need W <= V <= ld (W=%d V=%d ld=%d)", W, V, ld);
+  const size_t ban_bytes = (size_t)((V + 31) / 32) * sizeof(uint32_t);
+  UA2_CHECK(ban_bytes <= 48 * 1024, "ua2_beam_step_groups_ngram: a vocabulary of %d does not fit the ban bitmap (48 KB)", V);
+  hipStream_t s = (hipStream_t)stream;
+  const BeamBan bn{ng->n, ng->cap, ng->hist};
+  hipLaunchKernelGGL(beam_topw_ngram_kernel, dim3(G * W), dim3(kTopwThreads), ban_bytes, s, logits, ld, V, W, st->fin, st->len, st->ctrl, bn,
+                     st->cand_logp, st->cand_id);
+  UA2_LAUNCH_CHECK();
+  hipLaunchKernelGGL(beam_select_ngram_kernel, dim3(G), dim3(kSelectNgramThreads), 0, s, W, V, eos, *st, token, token_ld, bn);
   UA2_LAUNCH_CHECK();
   return 0;
 }

@@ -39,6 +39,7 @@ extern "C" size_t ua2_struct_size(int which) {
     case 4: return sizeof(ua2_gpt_desc);
     case 5: return sizeof(ua2_stage3_desc);
     case 6: return sizeof(ua2_convtc_args);
+    case 7: return sizeof(ua2_beam_ngram);
     default: return 0;
   }
 }

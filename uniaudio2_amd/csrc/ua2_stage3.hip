@@ -98,6 +98,7 @@ struct ua2_stage3 {
   int32_t beam_W = 0, beam_G = 1, beam_eos = -1, beam_n_pools = 0;
   ua2_beam_state beam{};
   const ua2_beam_pool* beam_pools = nullptr;
+  ua2_beam_ngram beam_ng{};                       // the no-repeat-n-gram ban of the attached beam (ua2_stage3_set_beam_ngram; n == 0 = off)
   // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
   struct W8Twin { const void* q; const int8_t* exp; };
   std::map<const void*, W8Twin> w8;
@@ -868,6 +869,7 @@ extern "C" int ua2_stage3_set_row_streams(ua2_stage3* h, int32_t* row_key, int32
 extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, int32_t eos, const ua2_beam_state* st, const ua2_beam_pool* pools,
                                           int32_t n_pools) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_beam: NULL handle");
+  if (h->beam_ng.n != 0) { drop_graphs(h); h->beam_ng = ua2_beam_ngram{}; }   // the ban belongs to one attachment: set again behind this call
   if (W == 0) {
     if (h->beam_W != 0) drop_graphs(h);
     h->beam_W = 0; h->beam_G = 1;
@@ -886,6 +888,22 @@ extern "C" int ua2_stage3_set_beam_groups(ua2_stage3* h, int32_t W, int32_t G, i
   UA2_CHECK(d.vt >= W, "ua2_stage3_set_beam: vocabulary smaller than the beam");
   if (W != h->beam_W || G != h->beam_G || eos != h->beam_eos || memcmp(st, &h->beam, sizeof(*st)) != 0 || pools != h->beam_pools || n_pools != h->beam_n_pools) drop_graphs(h);   // recorded beam frames bake the state's pointers
   h->beam_W = W; h->beam_G = G; h->beam_eos = eos; h->beam = *st; h->beam_pools = pools; h->beam_n_pools = n_pools;
+  return 0;
+}
+
+extern "C" int ua2_stage3_set_beam_ngram(ua2_stage3* h, const ua2_beam_ngram* ng) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_beam_ngram: NULL handle");
+  ua2_beam_ngram v{};
+  if (ng && ng->n != 0) {
+    UA2_CHECK(h->beam_W >= 1, "ua2_stage3_set_beam_ngram: no beam is attached (ua2_stage3_set_beam)");
+    UA2_CHECK(ng->n >= 2 && ng->n <= 16, "ua2_stage3_set_beam_ngram: no_repeat_ngram_size must be 0 (off) or in 2..16, got %d", ng->n);
+    UA2_CHECK(ng->cap >= 1, "ua2_stage3_set_beam_ngram: history capacity %d", ng->cap);
+    UA2_CHECK(ng->hist != nullptr, "ua2_stage3_set_beam_ngram: NULL history buffer");
+    UA2_CHECK((size_t)((h->d.vt + 31) / 32) * sizeof(uint32_t) <= 48 * 1024, "ua2_stage3_set_beam_ngram: a vocabulary of %d does not fit the ban bitmap (48 KB)", h->d.vt);
+    v = *ng;
+  }
+  if (v.n != h->beam_ng.n || v.cap != h->beam_ng.cap || v.hist != h->beam_ng.hist) drop_graphs(h);   // recorded beam frames bake the step's launches
+  h->beam_ng = v;
   return 0;
 }
 
@@ -1123,7 +1141,9 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
     if (mode < 0) return 0;
     if (beam) {
       const ua2_stage3_desc& d = h->d;
-      if (int rc = ua2_beam_step_groups(h->text_logits, d.vt, d.vt, h->beam_W, h->beam_G, h->beam_eos, &h->beam, d.out_tokens, d.n_cb + 1, st)) return rc;
+      if (h->beam_ng.n != 0) {
+        if (int rc = ua2_beam_step_groups_ngram(h->text_logits, d.vt, d.vt, h->beam_W, h->beam_G, h->beam_eos, &h->beam, &h->beam_ng, d.out_tokens, d.n_cb + 1, st)) return rc;
+      } else if (int rc = ua2_beam_step_groups(h->text_logits, d.vt, d.vt, h->beam_W, h->beam_G, h->beam_eos, &h->beam, d.out_tokens, d.n_cb + 1, st)) return rc;
       int32_t* const tables[3] = {const_cast<int32_t*>(d.und.page_table), const_cast<int32_t*>(d.backbone.page_table), const_cast<int32_t*>(d.gen.page_table)};
       if (int rc = ua2_beam_reorder_groups(h->beam_W, h->beam_G, h->beam.parent, d.row_pos, 1, h->beam_pools, h->beam_n_pools, tables, 3, d.max_batch, d.backbone.max_pages, st)) return rc;
       return feedback_impl(h, R, 1, reason_eos, reason_card, st, 0);   // out_tokens' text column holds the step's ids: the text feedback as it is

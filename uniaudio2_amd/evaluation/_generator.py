@@ -337,9 +337,11 @@ class GeneratorBase:
         return self._text_loop(L, max_frames)
 
     @torch.inference_mode()
-    def _beam_search_text(self, tokens, tokens_mask, beam_width, length_penalty, early_stopping, max_length) -> str:
-        """The loop of generate_asr_beam_search (asr_task.py:438-576) on the device: Model_stage3.beam_search."""
+    def _beam_search_text(self, tokens, tokens_mask, beam_width, length_penalty, early_stopping, max_length, no_repeat_ngram_size=0) -> str:
+        """The loop of generate_asr_beam_search (asr_task.py:438-576) on the device: Model_stage3.beam_search.
+        no_repeat_ngram_size >= 2: under the no-repeat-n-gram ban (the model is called as before when it is 0)."""
         beam_width = int(beam_width)
+        ngram = dict(no_repeat_ngram_size=int(no_repeat_ngram_size)) if no_repeat_ngram_size else {}
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
         st = getattr(self._model, "_st", None)
@@ -349,13 +351,15 @@ class GeneratorBase:
         ids, _, _ = self._model.beam_search(tokens, tokens_mask.bool(), beam_width=beam_width, length_penalty=length_penalty,
                                             max_length=max_length, eos_id=TEXT_EOS, early_stopping=early_stopping,
                                             chunk_frames=self.chunk_frames,
-                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
+                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None, **ngram)
         return self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long))
 
     @torch.inference_mode()
-    def _beam_search_text_batch(self, prompts, beam_width, length_penalty, max_length):
-        """generate_asr_beam_search over several prompts in one frame: Model_stage3.beam_search_batch.  prompts = [(tokens, mask)]."""
+    def _beam_search_text_batch(self, prompts, beam_width, length_penalty, max_length, no_repeat_ngram_size=0):
+        """generate_asr_beam_search over several prompts in one frame: Model_stage3.beam_search_batch.  prompts = [(tokens, mask)].
+        no_repeat_ngram_size: as in _beam_search_text."""
         beam_width, G = int(beam_width), len(prompts)
+        ngram = dict(no_repeat_ngram_size=int(no_repeat_ngram_size)) if no_repeat_ngram_size else {}
         if not 1 <= beam_width <= 8:
             raise ValueError(f"beam_width must be in 1..8, got {beam_width}")
         if G < 1:
@@ -368,7 +372,7 @@ class GeneratorBase:
         self._set_sampling(1, 1.0)
         out = self._model.beam_search_batch([(t, m.bool()) for t, m in prompts], beam_width=beam_width, length_penalty=length_penalty,
                                             max_length=max_length, eos_id=TEXT_EOS, chunk_frames=self.chunk_frames,
-                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None)
+                                            skip_audio_experts=os.environ.get("UA2_KEEP_AUDIO_EXPERTS") is None, **ngram)
         return [self._text_tokenizer.decode(torch.tensor(ids, dtype=torch.long)) for ids, _, _ in out]
 
     @torch.inference_mode()

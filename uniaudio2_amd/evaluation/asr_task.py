@@ -7,6 +7,20 @@ from ._generator import GeneratorBase
 
 
 class Generator(GeneratorBase):
+    # The opt-in of the beam search's no-repeat-n-gram ban (an extension).  False: `no_repeat_ngram_size` is accepted and has no
+    # effect, exactly as in the reference.  True: generate_asr_beam_search[_batch] hand it to the device search.  An
+    # attribute and not a parameter: generate_asr_beam_search keeps the reference's parameter list to the letter.
+    enforce_ngram = False
+
+    def _enforced_ngram(self, no_repeat_ngram_size) -> int:
+        """The n the beam search bans with: 0 unless enforce_ngram is set."""
+        if not self.enforce_ngram:
+            return 0
+        n = int(no_repeat_ngram_size)
+        if n != 0 and not 2 <= n <= 16:
+            raise ValueError(f"enforce_ngram: no_repeat_ngram_size must be 0 (off) or in 2..16, got {n}")
+        return n
+
     @torch.inference_mode()
     def generate_asr(self, task_prompt, task_name, text_token=None, semantic_token=None, reason_token=None,
                      temperature: float = 0.9, topk: int = 200, cfg_scale=1.0) -> str:
@@ -42,23 +56,29 @@ class Generator(GeneratorBase):
         wins.  It runs on the device: the hypotheses are the rows of one frame and fork their K/V page-wise
         (Model_stage3.beam_search; the plan is re-made for 2 * beam_width sequences when it is smaller).
         `no_repeat_ngram_size` is accepted and has no effect, exactly as in the reference, whose `_apply_ngram_constraint`
-        (:610-628) bans an always-empty set.  As for generate_asr_with_ngram_sampling the prefill is generate_asr's
-        (forward_prefix of prompt[:-1]), not the reference's training-mode forward (:476)."""
+        (:610-628) bans an always-empty set.  With the attribute enforce_ngram = True (an extension) it does what that function was
+        meant to do: every step runs under the no-repeat-n-gram ban of DESIGN.md §2 on the device (no_repeat_ngram_size in 2..16;
+        an id that would complete an n-gram the hypothesis already holds counts as -inf before the softmax).  As for
+        generate_asr_with_ngram_sampling the prefill is generate_asr's (forward_prefix of prompt[:-1]), not the reference's
+        training-mode forward (:476)."""
         tokens, mask = self.prepare_asr_task(task_prompt, reason_token, semantic_token)
-        return self._beam_search_text(tokens, mask, beam_width, length_penalty, early_stopping, max_length)
+        return self._beam_search_text(tokens, mask, beam_width, length_penalty, early_stopping, max_length,
+                                      self._enforced_ngram(no_repeat_ngram_size))
 
     @torch.inference_mode()
     def generate_asr_beam_search_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, beam_width: int = 5,
-                                       length_penalty: float = 0.6, max_length: int = 500) -> list:
+                                       length_penalty: float = 0.6, max_length: int = 500, *, no_repeat_ngram_size: int = 3) -> list:
         """generate_asr_beam_search for several utterances at once (an extension: the reference has no batched search).
         reason_tokens / semantic_tokens: lists of (T, 8) tensors, one pair per utterance.  Each prompt is built with
         prepare_asr_task; the utterances' beams are the row groups of one frame (Model_stage3.beam_search_batch), at most
         64 // beam_width utterances; the plan is re-made for 2 * len(reason_tokens) * beam_width sequences when it is smaller.
-        Returns the decoded texts in the order given — each the text generate_asr_beam_search returns for that utterance alone."""
+        Returns the decoded texts in the order given — each the text generate_asr_beam_search returns for that utterance alone.
+        no_repeat_ngram_size (keyword-only): as in generate_asr_beam_search — no effect unless the attribute enforce_ngram is set."""
         if len(reason_tokens) != len(semantic_tokens):
             raise ValueError("one semantic tensor per reason tensor is needed")
         prompts = [self.prepare_asr_task(task_prompt, r, s) for r, s in zip(reason_tokens, semantic_tokens)]
-        return self._beam_search_text_batch(prompts, beam_width, length_penalty, max_length)
+        return self._beam_search_text_batch(prompts, beam_width, length_penalty, max_length,
+                                            self._enforced_ngram(no_repeat_ngram_size))
 
     @torch.inference_mode()
     def generate_asr_batch(self, task_prompt, task_name, reason_tokens, semantic_tokens, temperature: float = 0.9, topk: int = 200,

@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
-from .._lib import BeamPool, BeamState, Stage3Desc, W8Entry, check, lib, vp
+from .._lib import BeamNgram, BeamPool, BeamState, Stage3Desc, W8Entry, check, lib, vp
 from .config import Config as gpt_config
 from .lit_model import GPT
 
@@ -1007,8 +1007,10 @@ class Model_stage3(nn.Module):
             pt = g.kv_cache.page_table
             pt.copy_(torch.arange(pt.numel(), dtype=torch.int32, device=pt.device).view_as(pt))
 
-    def _beam_checks(self, W, G, max_length):
+    def _beam_checks(self, W, G, max_length, no_repeat_ngram_size=0):
         st = self._st
+        if no_repeat_ngram_size != 0 and not 2 <= no_repeat_ngram_size <= 16:
+            raise ValueError(f"no_repeat_ngram_size of a beam search must be 0 (off) or in 2..16, got {no_repeat_ngram_size}")
         if not 1 <= W <= 8:
             raise ValueError(f"beam_width must be in 1..8, got {W}")
         if G * W > 64:
@@ -1024,14 +1026,16 @@ class Model_stage3(nn.Module):
         if self._beam is not None:
             raise ValueError("a beam search is already running (end_beams)")
 
-    def _attach_beams(self, W, G, length_penalty, max_length, eos_id):
+    def _attach_beams(self, W, G, length_penalty, max_length, eos_id, no_repeat_ngram_size=0):
         """The device state of G beams of W slots (include/ua2hip.h: group g at fixed strides from the base pointers), attached to
-        the executor, and the start of the fork for the rows the caller has loaded: every slot of a group gets slot 0's pages."""
+        the executor, and the start of the fork for the rows the caller has loaded: every slot of a group gets slot 0's pages.
+        no_repeat_ngram_size >= 2: the two history sets of every group (ua2_beam_ngram: [G][2][8][max_length] ids) behind the log."""
         st = self._st
         dev = st["device"]
         # state: one int32 buffer carved into the fields of ua2_beam_state (score and cand_logp are fp32 views of their words)
         n_log = max_length * W * 4
-        words = torch.zeros(G * (4 * 8 + 4 + 2 * 64 + n_log), dtype=torch.int32, device=dev)
+        n_hist = 2 * 8 * max_length if no_repeat_ngram_size else 0
+        words = torch.zeros(G * (4 * 8 + 4 + 2 * 64 + n_log + n_hist), dtype=torch.int32, device=dev)
         at = [0]
 
         def f(n):
@@ -1039,6 +1043,7 @@ class Model_stage3(nn.Module):
             return words[at[0] - n:at[0]]
         score, fin, ln, parent, ctrl = f(8 * G).view(torch.float32), f(8 * G), f(8 * G), f(8 * G), f(4 * G)
         cand_logp, cand_id, log = f(64 * G).view(torch.float32), f(64 * G), f(G * n_log)
+        hist = f(G * n_hist)
         score.fill_(float("-inf")); score[::8] = 0.0
         fin.fill_(2); fin[::8] = 0
         ctrl[1::4] = -1
@@ -1062,21 +1067,26 @@ class Model_stage3(nn.Module):
                           len=ln, ctrl=ctrl.view(G, 4), log=log.view(G, max_length, W, 4), lp_inv=lp_inv, pools=pools_dev, state=bs)
         check(lib.ua2_stage3_set_beam_groups(self._h, W, G, int(eos_id), C.byref(bs), pools_dev.data_ptr(), len(pools)),
               "ua2_stage3_set_beam_groups")
+        if no_repeat_ngram_size:                     # (detaching the beam clears it: end_beams_groups)
+            ng = BeamNgram(int(no_repeat_ngram_size), max_length, hist.data_ptr())
+            check(lib.ua2_stage3_set_beam_ngram(self._h, C.byref(ng)), "ua2_stage3_set_beam_ngram")
         # the start of the fork: all parents slot 0 of their group, before the first frame (pos_add 0)
         check(lib.ua2_beam_reorder_groups(W, G, None, st["row_pos"].data_ptr(), 0, pools_dev.data_ptr(), len(pools), tabs, 3, st["B"],
                                           max_pages, ops.stream()), "ua2_beam_reorder_groups")
 
     @torch.inference_mode()
     def begin_beams(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
-                    eos_id: int = 128001):
+                    eos_id: int = 128001, no_repeat_ngram_size: int = 0):
         """Start of a beam search over one prompt: tokens (L, 9), tokens_mask (L, 9).  Prefills prompt[:-1] as sequence 0, loads the
         prompt's last frame into the W = beam_width rows of the decode state, attaches the beam state to the executor and gives every
         slot its view of the prompt's K/V (shared full pages, a copy of the partial one).  Slot 0 starts live with score 0, the others
-        dead.  Run steps with generate_frames(n, W, 3); end_beams() must follow (beam_search does so in a `finally`)."""
+        dead.  Run steps with generate_frames(n, W, 3); end_beams() must follow (beam_search does so in a `finally`).
+        no_repeat_ngram_size = n in 2..16 (0 = off, the reference's behaviour): every step runs under the no-repeat-n-gram ban of
+        DESIGN.md §2 — an id that would complete an n-gram the slot's text already holds counts as -inf before the softmax."""
         self._need()
         st = self._st
-        W, max_length = int(beam_width), int(max_length)
-        self._beam_checks(W, 1, max_length)
+        W, max_length, ng = int(beam_width), int(max_length), int(no_repeat_ngram_size)
+        self._beam_checks(W, 1, max_length, ng)
         dev = st["device"]
         tokens, tokens_mask = tokens.to(dev), tokens_mask.bool().to(dev)
         L = tokens.shape[0]
@@ -1087,21 +1097,22 @@ class Model_stage3(nn.Module):
         self.forward_prefix(tokens[None, :-1], tokens_mask=tokens_mask[None], input_pos=pos[:, :-1])
         self.begin_decode(tokens[-1:].unsqueeze(0).repeat(W, 1, 1), tokens_mask[-1:].unsqueeze(0).repeat(W, 1, 1),
                           torch.tensor([L - 1], device=dev))
-        self._attach_beams(W, 1, length_penalty, max_length, eos_id)
+        self._attach_beams(W, 1, length_penalty, max_length, eos_id, ng)
 
     @torch.inference_mode()
-    def begin_beams_groups(self, prompts, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500, eos_id: int = 128001):
+    def begin_beams_groups(self, prompts, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500, eos_id: int = 128001,
+                           no_repeat_ngram_size: int = 0):
         """Start of G = len(prompts) beam searches in one frame: prompts[g] = (tokens (L_g, 9), mask (L_g, 9)) of any lengths.  Group
         g's slot j is row g * W + j.  Every prompt[:-1] is prefilled in one ragged pass, prompt g as sequence g * W (slot 0 of its
         group then owns the prompt's pages); each prompt's last frame is loaded into its group's W rows at position L_g - 1; one
         start fork gives every slot its view of its own prompt.  Run steps with generate_frames(n, G * W, 3); end_beams_groups()
-        must follow."""
+        must follow.  no_repeat_ngram_size: as in begin_beams, every group under its own histories."""
         self._need()
         st = self._st
-        W, G, max_length = int(beam_width), len(prompts), int(max_length)
+        W, G, max_length, ng = int(beam_width), len(prompts), int(max_length), int(no_repeat_ngram_size)
         if G < 1:
             raise ValueError("beam search over an empty list of prompts")
-        self._beam_checks(W, G, max_length)
+        self._beam_checks(W, G, max_length, ng)
         dev = st["device"]
         prompts = [(t.to(dev), m.bool().to(dev)) for t, m in prompts]
         Ls = [int(t.shape[0]) for t, _ in prompts]
@@ -1117,7 +1128,7 @@ class Model_stage3(nn.Module):
         last_m = torch.stack([m[-1] for _, m in prompts]).repeat_interleave(W, dim=0)
         pos = torch.tensor(Ls, device=dev).repeat_interleave(W) - 1
         self.begin_decode(last_t.unsqueeze(1), last_m.unsqueeze(1), pos)
-        self._attach_beams(W, G, length_penalty, max_length, eos_id)
+        self._attach_beams(W, G, length_penalty, max_length, eos_id, ng)
 
     def beams_all_finished(self) -> int:
         """The step at which every slot of every group had first finished (the last group's latch), -1 while one is live.  One copy of
@@ -1182,27 +1193,29 @@ class Model_stage3(nn.Module):
     @torch.inference_mode()
     def beam_search(self, tokens, tokens_mask, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500,
                     eos_id: int = 128001, early_stopping: bool = True, chunk_frames: int = 16, use_graph: bool = True,
-                    skip_audio_experts: bool = True):
+                    skip_audio_experts: bool = True, no_repeat_ngram_size: int = 0):
         """Beam search over the text continuation of one prompt (the reference's evaluation/asr_task.py:438-576 rule,
         corrected).  tokens / tokens_mask (L, 9).  The W hypotheses run as the W rows of one frame; the search stops when all W are
         finished or after max_length steps.  With all W finished a further step reproduces the beam, so the result does not depend on
         chunk_frames, and stopping there is what early_stopping=False would compute as well (the reference keeps looping over
-        finished beams without changing them).  Returns (best ids, best score, all W hypotheses)."""
-        self.begin_beams(tokens, tokens_mask, beam_width, length_penalty, max_length, eos_id)
+        finished beams without changing them).  no_repeat_ngram_size = n in 2..16 runs every step under the no-repeat-n-gram ban
+        (begin_beams; 0, the default, bans nothing, as the reference does).  Returns (best ids, best score, all W hypotheses)."""
+        self.begin_beams(tokens, tokens_mask, beam_width, length_penalty, max_length, eos_id, no_repeat_ngram_size)
         return self._run_beams(int(beam_width), int(max_length), chunk_frames, use_graph, skip_audio_experts)[0]
 
     @torch.inference_mode()
     def beam_search_batch(self, prompts, beam_width: int = 5, length_penalty: float = 0.6, max_length: int = 500, eos_id: int = 128001,
-                          chunk_frames: int = 16, use_graph: bool = True, skip_audio_experts: bool = True):
+                          chunk_frames: int = 16, use_graph: bool = True, skip_audio_experts: bool = True, no_repeat_ngram_size: int = 0):
         """Beam search over several prompts at once: prompts[g] = (tokens (L_g, 9), mask (L_g, 9)); G * beam_width <= 64 rows, a plan
         of 2 * G * beam_width sequences.  The G beams are the row groups of one frame, so G searches cost about one
         search's frames.  Group g's result is what beam_search returns for prompts[g] alone — on the default (row-invariant) plan bit
         for bit: a group that has finished keeps being stepped as a fixed point beside the live ones, and the loop stops when every
-        group has latched or after max_length steps.  Returns [(best ids, best score, hypotheses)] in the order of prompts."""
+        group has latched or after max_length steps.  no_repeat_ngram_size: as in beam_search, for every group.  Returns
+        [(best ids, best score, hypotheses)] in the order of prompts."""
         prompts = list(prompts)
         if not prompts:
             raise ValueError("beam_search_batch needs at least one prompt")
-        self.begin_beams_groups(prompts, beam_width, length_penalty, max_length, eos_id)
+        self.begin_beams_groups(prompts, beam_width, length_penalty, max_length, eos_id, no_repeat_ngram_size)
         return self._run_beams(len(prompts) * int(beam_width), int(max_length), chunk_frames, use_graph, skip_audio_experts)
 
     def buffer(self, name: str, rows: int):

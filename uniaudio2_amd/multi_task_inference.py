@@ -33,6 +33,10 @@ Differences, all explicit:
     row groups of one frame (Generator.generate_asr_beam_search_batch): the same results file as --batch_size 1 on the default plan,
     in the order of the names, missing files skipped as before.  N * W is at most 64 (ValueError otherwise); the plan holds 2 * N * W
     sequences — 128 sequences at 2048 positions are about 35 GB of K/V at the released sizes (135 kB per position).
+    `--beam_no_repeat_ngram N` (N in 2..16; default 0 = off, the reference's behaviour) runs that search under a no-repeat-n-gram ban
+    on the device: an id that would complete an n-gram the hypothesis already holds counts as -inf before the softmax (the
+    corrected reading of the reference's `_apply_ngram_constraint`, which bans an always-empty set).  It needs --beam_width >= 1 and works
+    with --batch_size; any other value raises ValueError before a model is built.  Its effect on task quality is not measured.
   * `--batch_size N` without --beam_width decodes the understanding tasks in batches too (greedy and --decode_type ngram ASR /
     Yue_ASR, lyric_recognition, audio_caption / music_caption, audio_understanding, speech_s2t): the utterances of --token_dir /
     --audio_dir that exist go into ONE `generate_*_batch` call — one decode session of at most N rows (N is clamped to the number of
@@ -217,10 +221,16 @@ def _check_understanding_decode(args, task):
     bw = int(getattr(args, "beam_width", 0) or 0)
     if bw < 0 or bw > 8:
         raise ValueError(f"--beam_width must be in 0..8 (0 = off), got {bw}")
+    bn = int(getattr(args, "beam_no_repeat_ngram", 0) or 0)
+    if bn != 0 and not 2 <= bn <= 16:
+        raise ValueError(f"--beam_no_repeat_ngram must be 0 (off) or in 2..16, got {bn}")
+    if bn != 0 and bw < 1:
+        raise ValueError(f"--beam_no_repeat_ngram {bn} needs a beam search: --beam_width N with N in 1..8")
     if bw >= 1:
         if args.decode_type == "ngram":
             raise ValueError("--beam_width does not combine with --decode_type ngram: the reference's beam search bans no n-gram "
-                             "(its _apply_ngram_constraint works on an empty set) and its n-gram loop is greedy")
+                             "(its _apply_ngram_constraint works on an empty set) and its n-gram loop is greedy; "
+                             "--beam_no_repeat_ngram N bans repeated n-grams inside the beam")
         if task == "lyric_recognition":
             raise ValueError("--beam_width is not available for lyric_recognition: the reference's lyric Generator "
                              "(evaluation/lyric_asr_task.py) has no generate_asr_beam_search")
@@ -282,6 +292,16 @@ def _load_token_pair(token_dir, name):
     return torch.load(rp, map_location="cpu").transpose(0, 1).long(), torch.load(sp, map_location="cpu").transpose(0, 1).long()
 
 
+def _beam_ngram_kwargs(args, generator):
+    """--beam_no_repeat_ngram N >= 2: the generator's opt-in ban (Generator.enforce_ngram) and its n; nothing otherwise (the
+    generators are called as before)."""
+    n = int(getattr(args, "beam_no_repeat_ngram", 0) or 0)
+    if not n:
+        return {}
+    generator.enforce_ngram = True
+    return dict(no_repeat_ngram_size=n)
+
+
 def _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names, f_out):
     """--beam_width with --batch_size N > 1: the names in their order, in chunks of N that exist (a missing file is skipped and does not
     count), each chunk one generate_asr_beam_search_batch call; one results line per utterance, in the order of names."""
@@ -293,7 +313,7 @@ def _beam_search_in_chunks(args, generator, task, task_prompt, token_dir, names,
             return
         texts = generator.generate_asr_beam_search_batch(task_prompt, task_name=task, reason_tokens=[r for _, r, _ in chunk],
                                                          semantic_tokens=[s for _, _, s in chunk], beam_width=args.beam_width,
-                                                         length_penalty=args.length_penalty)
+                                                         length_penalty=args.length_penalty, **_beam_ngram_kwargs(args, generator))
         if len(texts) != len(chunk):
             raise RuntimeError(f"beam search returned {len(texts)} texts for {len(chunk)} utterances")
         for (name, _, _), text_out in zip(chunk, texts):
@@ -422,7 +442,8 @@ def run_understanding(args):
                                                             temperature=args.temperature, topk=1, cfg_scale=args.cfg_scale)
             elif int(getattr(args, "beam_width", 0) or 0) >= 1:                                     # asr, yue_asr (checked above)
                 text_out = generator.generate_asr_beam_search(task_prompt, task_name=task, reason_token=reason, semantic_token=semantic,
-                                                              beam_width=args.beam_width, length_penalty=args.length_penalty)
+                                                              beam_width=args.beam_width, length_penalty=args.length_penalty,
+                                                              **_beam_ngram_kwargs(args, generator))
             elif args.decode_type == "ngram":                                                       # :316-321: asr, yue_asr
                 text_out = generator.generate_asr_with_ngram_sampling(task_prompt, task_name=task, reason_token=reason,
                                                                       semantic_token=semantic, temperature=args.temperature, topk=1,
@@ -687,6 +708,10 @@ def get_parser():
                         "same results.  Default 0 = off")
     p.add_argument("--length_penalty", type=float, default=0.6,
                    help="--beam_width: exponent of the length normalisation ((5 + length) / 6) ** length_penalty (the reference's default 0.6)")
+    p.add_argument("--beam_no_repeat_ngram", type=int, default=0,
+                   help="--beam_width (extension): N in 2..16 runs the beam search under a no-repeat-n-gram ban on the device — an id that "
+                        "would complete an n-gram the hypothesis already holds counts as -inf before the softmax.  Works with --batch_size.  "
+                        "Default 0 = off: the reference's search, which accepts no_repeat_ngram_size and bans nothing")
     p.add_argument("--batch_size", type=int, default=1,
                    help="utterances decoded together per GPU (extension; 1 = one by one as the reference).  TTS / Yue_TTS / TTA / TTM / LTS / "
                         "InstructTTS with --text_file: at most N live utterances per GPU, waiting ones admitted into freed rows; greedy and sampled output "
