@@ -531,6 +531,65 @@ int ua2_sample_topp_rows(int dtype, int32_t M, const float* logits, int32_t ld, 
                          int32_t* out_tokens, int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset,
                          int32_t C, float* next_h, float top_p, int32_t* keep_count, void* stream);
 
+/* [v10, addition] Repetition penalty over a window of the ids a sampler has produced: the four tails above (top-k / nucleus x shared
+ * stream / per-row streams) behind ONE entry point, each optionally penalised.  Not in the reference (an opt-in extension; its effect on
+ * audio quality is NOT measured: no trained checkpoint ships).  The rule is the CTRL / Hugging Face RepetitionPenaltyLogitsProcessor
+ * rule restricted to a window, stated so that a host can replay it exactly.
+ *
+ * The form of the launch: row_key / row_draw non-NULL = per-row streams (ua2_sample_topk_rows: seed, counter, row_key_shift unused),
+ * else the shared stream (ua2_sample_topk: seed, counter, row_key_shift); 0 < top_p < 1 = the nucleus filter, top_p == 0 = off;
+ * keep_count as in ua2_sample_topp.  Every other field up to keep_count is the argument of that name of the four entries.
+ *
+ * History ring of row m: ring = rep_hist + m * rep_hist_ld (rep_cap int32 slots), n = rep_len[m * rep_len_ld] = the number of ids
+ * appended to the ring so far (a negative n reads as 0).  Entry j (j = 0 the oldest id ever appended) lives in ring[j % rep_cap]; the
+ * entries still stored are j in [max(0, n - rep_cap), n).  An append of id writes ring[n % rep_cap] = id and rep_len becomes n + 1 (it
+ * counts every append and does not saturate; n < 2^31 - 1 is the caller's to keep, by starting the row anew).  A row starts with
+ * rep_len = 0; the slots need no initial value.
+ *
+ * The penalty: S = the set of distinct ids in [0, V) among entries j in [n - min(n, rep_window), n).  For c in S the sampler reads
+ *   l'_c = (l_c < 0) ? l_c * rep_penalty : l_c / rep_penalty
+ * in place of the fp32 logit l_c = logits[m * ld + c]: one IEEE-754 round-to-nearest fp32 multiply or divide, applied ONCE per distinct
+ * id however often it occurs in the window; -0.0, +0.0, -inf and NaN follow from the expression (-0.0 and +0.0 take the divide, NaN
+ * stays NaN).  Columns outside S read l_c.  The penalty comes before the temperature division; everything downstream is the tail of
+ * that form on l' — forbid prefix (a penalised column below it stays forbidden), top-k threshold on key(l' / T), nucleus filter, the
+ * Philox race under the same counters, tie rule, all-NaN rule, embedding gather.  The logits buffer is only read.
+ * After the draw the id written to out_tokens is appended to the row's ring (if 0 <= id < V, which the tail's clamp guarantees).
+ *
+ * Equivalence: the launch on (logits, history) is bit for bit the launch of the same form on logits whose columns in S hold l' — equal
+ * ids, equal gathered next_h rows.  Row invariance: a block reads and writes only its own row's ring and counter, so a row's id depends
+ * on its logits, its key and draw and its own history alone; the two rows of a guidance pair (equal logits, keys, histories) draw and
+ * append equal ids.
+ *
+ * rep_hist == NULL, or rep_penalty == 1: OFF — the call IS the existing launch of that form, and a supplied history is neither read nor
+ * written.  With rep_hist != NULL: rep_penalty must be finite and > 0 and 1 <= rep_window <= 512; when penalised also V <= 131072 (the
+ * V-bit membership set in LDS: 16 KB), rep_len != NULL, rep_cap >= rep_window, rep_hist_ld >= rep_cap, rep_len_ld >= 1.  Anything else is
+ * an error and nothing is launched.  One 1024-thread workgroup per row: the set is filled with LDS atomic ORs (which de-duplicates), and
+ * every pass of the tail reads its logit through the same helper. */
+typedef struct {
+  int32_t dtype, M;
+  const float* logits;
+  int32_t ld, V, topk;
+  float temperature;
+  const int32_t* forbid;
+  uint64_t seed;                    /* shared stream */
+  const int32_t* counter;
+  int32_t row_key_shift, stream_id;
+  const int32_t *row_key, *row_draw;   /* per-row streams: both non-NULL */
+  int32_t* out_tokens;
+  int32_t out_ld, out_col;
+  const void* emb;
+  int32_t emb_row_offset, C;
+  float* next_h;
+  float top_p;
+  int32_t reserved;
+  int32_t* keep_count;
+  float rep_penalty;                /* theta; 1 = off */
+  int32_t rep_window, rep_cap, rep_hist_ld, rep_len_ld, reserved2;
+  int32_t* rep_hist;                /* NULL = off */
+  int32_t* rep_len;
+} ua2_sample_args;
+int ua2_sample_penalized(const ua2_sample_args* a, void* stream);
+
 /* n-gram repeat filter of the text loop (evaluation/asr_task.py:329-432 generate_asr_with_ngram_sampling, :407-432).  Row r
  * (r < R): candidate c = out[r * ld], generated ids H = hist[r * cap ...], L = hist_len[r] of them.  c is replaced by `fallback`
  * when the n-gram (last n - 1 ids of H, c) already occurs in H; the final id is appended to H when L < cap and hist_len[r] becomes
@@ -975,6 +1034,18 @@ int ua2_stage3_set_row_streams(ua2_stage3* h, int32_t* row_key, int32_t* row_dra
  * (topk == 1, the per-id tables and the arg-max fold with them), ua2_stage3_text_flush and beam frames ignore it.  top_p's bits select
  * the captured graph next to topk / temperature: a changed value never replays a frame recorded under another. */
 int ua2_stage3_set_top_p(ua2_stage3* h, float top_p);
+/* [v10, addition] Repetition penalty of the heads' samplers (ua2_sample_penalized above; not in the reference, effect on audio quality NOT
+ * measured).  hist [max_batch][1 + n_cb][window] int32 and len [max_batch][1 + n_cb] int32 are device buffers owned by the caller, alive
+ * while set: the ring of row m and sampler stream s (0 = the text head, 1 + i = audio codebook i) is hist + (m * (1 + n_cb) + s) * window
+ * (rep_cap = rep_window = window) and its counter len[m * (1 + n_cb) + s], with the layout stated there.  The caller zeroes the counters
+ * of a row that starts.  While set and topk > 1, EVERY sampler launch of a frame — the text sampler of any mode that runs it and the n_cb
+ * audio samplers, shared stream or per-row streams, with or without the nucleus filter, guided pairs included (ua2_cfg_mix comes first:
+ * the guided logits are penalised) — runs penalised against its own stream's history and appends its id.  Greedy frames (topk == 1: the
+ * per-id tables, the arg-max fold, the partials of the GEMM epilogue), ua2_stage3_text_flush, beam frames (mode 3) and ua2_stage3_score
+ * ignore it and leave the histories alone.  penalty must be finite and > 0, 1 <= window <= 512, and the heads' vocabularies at most
+ * 131072 columns; penalty == 1 or NULL buffers clear it.  penalty's bits and window select the captured graph next to top_p's; the
+ * buffer pointers are baked into recorded frames, so a change of either drops them. */
+int ua2_stage3_set_rep_penalty(ua2_stage3* h, float penalty, int32_t window, int32_t* hist, int32_t* len);
 /* Row groups (ua2_attn_args.group_*; device tables owned by the caller, alive until replaced) for the attention of the
  * NEXT ua2_stage3_trunk call (they are cleared when it returns): prefill rows of one sequence then share LDS-staged K/V
  * pages on the MFMA flash kernel.  ua2_stage3_frame (decode) never uses groups. */

@@ -113,6 +113,15 @@ class BeamNgram(C.Structure):
     _fields_ = [("n", i32), ("cap", i32), ("hist", vp)]
 
 
+class SampleArgs(C.Structure):
+    """ua2_sample_args: one sampler launch of any of the four forms, optionally under the repetition penalty (ua2_sample_penalized)."""
+    _fields_ = [("dtype", i32), ("M", i32), ("logits", vp), ("ld", i32), ("V", i32), ("topk", i32), ("temperature", f32), ("forbid", vp),
+                ("seed", C.c_uint64), ("counter", vp), ("row_key_shift", i32), ("stream_id", i32), ("row_key", vp), ("row_draw", vp),
+                ("out_tokens", vp), ("out_ld", i32), ("out_col", i32), ("emb", vp), ("emb_row_offset", i32), ("C", i32), ("next_h", vp),
+                ("top_p", f32), ("reserved", i32), ("keep_count", vp), ("rep_penalty", f32), ("rep_window", i32), ("rep_cap", i32),
+                ("rep_hist_ld", i32), ("rep_len_ld", i32), ("reserved2", i32), ("rep_hist", vp), ("rep_len", vp)]
+
+
 ACT_NONE, ACT_PRELU, ACT_ELU, ACT_TANH, ACT_ROUND9 = 0, 1, 2, 3, 4
 EW_IDENTITY, EW_SILU, EW_SIGMOID, EW_TANH = 0, 1, 2, 3
 
@@ -203,6 +212,8 @@ _EXPORTS = {
     "ua2_sample_topp": (C.c_int, [C.c_int, i32, vp, i32, i32, i32, f32, vp, C.c_uint64, vp, i32, vp, i32, i32, vp, i32, i32, vp, i32, f32, vp, vp]),
     "ua2_sample_topp_rows": (C.c_int, [C.c_int, i32, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, f32, vp, vp]),
     "ua2_stage3_set_top_p": (C.c_int, [vp, f32]),
+    "ua2_sample_penalized": (C.c_int, [C.POINTER(SampleArgs), vp]),
+    "ua2_stage3_set_rep_penalty": (C.c_int, [vp, f32, i32, vp, vp]),
     "ua2_ngram_filter": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, i32, vp]),
     "ua2_beam_step": (C.c_int, [vp, i32, i32, i32, i32, C.POINTER(BeamState), vp, i32, vp]),
     "ua2_beam_reorder": (C.c_int, [i32, vp, vp, i32, vp, i32, C.POINTER(vp), i32, i32, i32, vp]),

@@ -17,6 +17,12 @@
 // threshold value is found by a second, WEIGHTED 4-pass radix select on the same keys (256 buckets of uint64 mass per pass), and the
 // race then runs over key >= max(k-th key, threshold key).  Ties at the threshold value are all kept, like the top-k filter's.
 // The filter is a template parameter: the top-k-only kernels are the code they were.
+//
+// Repetition penalty (include/ua2hip.h ua2_sample_penalized has the contract; not in the reference): the columns named by the last
+// min(len, W) ids of the row's history ring read l' = (l < 0) ? l * theta : l / theta in place of l, once per distinct id, before the
+// temperature division; the drawn id is appended to the ring.  The distinct ids are a V-bit set in LDS (16 KB at V = 131072) filled
+// with LDS atomic ORs; every pass reads its logit through one helper (lv), so the select, the maximum, the nucleus masses and the race
+// see one value.  One more template parameter: the four kernels above it keep their code, and the set exists in the penalised ones only.
 #include "ua2_common.h"
 
 namespace {
@@ -39,16 +45,27 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// The repetition penalty of a penalised launch (ua2_sample_args.rep_*): row m's ring is hist + m * hist_ld, its counter len[m * len_ld]
+struct RepArgs {
+  float theta;
+  int window, cap;
+  int32_t* hist;
+  int hist_ld;
+  int32_t* len;
+  int len_ld;
+};
+
 // One row of the tail: block m of either kernel below.  (draw, row_part, seed) is the row's random stream — Philox counter
 // (column, draw, row_part, stream_id) under the 64-bit key `seed`; everything else is the row's data.
 // TOPP: the nucleus form — nucleus != 0 filters with P = floor(top_p * 2^32); keep_count (optional) [M] = columns that entered the race
-template <int DT, bool TOPP = false>
+// REP: the penalised form — the columns of the ring's last min(len, window) ids are read penalised, and the id is appended
+template <int DT, bool TOPP = false, bool REP = false>
 __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits, int ld, int V, int topk, float temperature,
                                                 const int32_t* __restrict__ forbid, unsigned long long seed, unsigned draw,
                                                 unsigned row_part, int stream_id, int32_t* __restrict__ out_tokens, int out_ld,
                                                 int out_col, const void* __restrict__ emb, int emb_off, int C,
                                                 float* __restrict__ next_h, int nucleus = 0, unsigned long long P = 0ull,
-                                                int32_t* __restrict__ keep_count = nullptr) {
+                                                int32_t* __restrict__ keep_count = nullptr, RepArgs rep = RepArgs{}) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sel_prefix, sel_remaining;
   __shared__ float red_v[16];
@@ -57,6 +74,29 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   const int m = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const float* row = logits + (size_t)m * ld;
   const int fb = forbid ? max(forbid[m], 0) : 0;
+  // lv(c): the logit of column c as the sampler reads it — row[c], or its penalised value when c is in the set
+  [[maybe_unused]] unsigned* rep_set = nullptr;
+  [[maybe_unused]] int rep_n = 0;
+  if constexpr (REP) {
+    __shared__ unsigned rep_bits[(1 << 17) / 32];          // bit c: column c is among the last min(len, window) ids (V <= 131072: the launcher checks)
+    rep_set = rep_bits;
+    const int32_t* ring = rep.hist + (size_t)m * rep.hist_ld;
+    rep_n = max(rep.len[(size_t)m * rep.len_ld], 0);
+    for (int i = tid; i < (V + 31) / 32; i += nt) rep_bits[i] = 0u;
+    __syncthreads();
+    for (int j = rep_n - min(rep_n, rep.window) + tid; j < rep_n; j += nt) {
+      const int id = ring[j % rep.cap];                    // entry j of the history lives in slot j % cap
+      if (id >= 0 && id < V) atomicOr(&rep_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+  }
+  auto lv = [&](int c) -> float {
+    const float l = row[c];
+    if constexpr (REP) {
+      if ((rep_set[c >> 5] >> (c & 31)) & 1u) return l < 0.f ? l * rep.theta : l / rep.theta;
+    }
+    return l;
+  };
   // ---- exact k-th largest key among columns [fb, V) -------------------------------------------
   if (tid == 0) { sel_prefix = 0u; sel_remaining = (unsigned)topk; }
   for (int pass = 3; pass >= 0; --pass) {
@@ -65,7 +105,7 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     const unsigned prefix = sel_prefix, shift = pass * 8;
     const unsigned mask_hi = (pass == 3) ? 0u : (0xffffffffu << (shift + 8));
     for (int c = fb + tid; c < V; c += nt) {
-      const unsigned k = key_of(row[c] / temperature);
+      const unsigned k = key_of(lv(c) / temperature);
       if ((k & mask_hi) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -84,7 +124,7 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   const unsigned kth = sel_prefix;               // key of the k-th largest scaled logit
   // ---- exponential race among the kept columns ------------------------------------------------
   float mx = -INFINITY;
-  for (int c = fb + tid; c < V; c += nt) mx = fmaxf(mx, row[c] / temperature);
+  for (int c = fb + tid; c < V; c += nt) mx = fmaxf(mx, lv(c) / temperature);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
   if ((tid & 63) == 0) red_v[tid >> 6] = mx;
@@ -112,7 +152,7 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
       int rb = -1;
       unsigned long long rs = 0ull;
       for (int c = fb + tid; c < V; c += nt) {
-        const float l = row[c] / temperature;
+        const float l = lv(c) / temperature;
         const unsigned k = key_of(l);
         if (k < kth || (k & mask_hi) != prefix) continue;
         const float e = expf(l - mx);
@@ -178,7 +218,7 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   float bv = -INFINITY;
   int bi = UA2_TOK_NONE;
   for (int c = fb + tid; c < V; c += nt) {
-    const float l = row[c] / temperature;
+    const float l = lv(c) / temperature;
     if (key_of(l) < thr) continue;               // removed: strictly below the k-th value (and, TOPP, below the nucleus threshold)
     if constexpr (TOPP) ++kept;
     unsigned r[4];
@@ -193,6 +233,12 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
   // every kept column scored NaN (a NaN or all -inf row): the lowest column the row may sample (ua2_row_token)
   const int tok = ua2_row_token(bv, bi, V, red_v, red_i, &tok_s, [&] { return (tid == 0 && fb < V) ? fb : UA2_TOK_NONE; });
   if (tid == 0) out_tokens[(size_t)m * out_ld + out_col] = tok;
+  if constexpr (REP) {
+    if (tid == 0 && tok >= 0 && tok < V) {       // every thread read the ring and the counter before the barriers of ua2_row_token
+      rep.hist[(size_t)m * rep.hist_ld + rep_n % rep.cap] = tok;
+      rep.len[(size_t)m * rep.len_ld] = rep_n + 1;
+    }
+  }
   if constexpr (TOPP) {
     if (keep_count) {                            // red_i is free again: ua2_row_token's last reader is behind its barriers
 #pragma unroll
@@ -267,6 +313,29 @@ __global__ __launch_bounds__(1024) void sample_topp_rows_kernel(const float* __r
   const unsigned long long seed = (unsigned long long)(unsigned)row_key[2 * m] | ((unsigned long long)(unsigned)row_key[2 * m + 1] << 32);
   sample_topk_row<DT, true>(logits, ld, V, topk, temperature, forbid, seed, (unsigned)row_draw[m], 0u, stream_id, out_tokens, out_ld, out_col,
                             emb, emb_off, C, next_h, nucleus, P, keep_count);
+}
+
+// the four kernels above under the repetition penalty (sample_topk_row<DT, TOPP, true>), as one template: ROWS picks the per-row streams
+// (row_key / row_draw) over the shared one (seed / counter / row_key_shift); the streams, the filters and the race are theirs
+template <int DT, bool TOPP, bool ROWS>
+__global__ __launch_bounds__(1024) void sample_pen_kernel(const float* __restrict__ logits, int ld, int V, int topk, float temperature,
+                                                          const int32_t* __restrict__ forbid, unsigned long long seed,
+                                                          const int32_t* __restrict__ counter, int row_key_shift,
+                                                          const int32_t* __restrict__ row_key, const int32_t* __restrict__ row_draw,
+                                                          int stream_id, int32_t* __restrict__ out_tokens, int out_ld, int out_col,
+                                                          const void* __restrict__ emb, int emb_off, int C, float* __restrict__ next_h,
+                                                          int nucleus, unsigned long long P, int32_t* __restrict__ keep_count, RepArgs rep) {
+  const int m = blockIdx.x;
+  unsigned draw, row_part;
+  if constexpr (ROWS) {
+    seed = (unsigned long long)(unsigned)row_key[2 * m] | ((unsigned long long)(unsigned)row_key[2 * m + 1] << 32);
+    draw = (unsigned)row_draw[m]; row_part = 0u;
+  } else {
+    seed += (unsigned long long)(unsigned)counter[1] | ((unsigned long long)(unsigned)counter[2] << 32);
+    draw = (unsigned)counter[0]; row_part = (unsigned)(m >> row_key_shift);
+  }
+  sample_topk_row<DT, TOPP, true>(logits, ld, V, topk, temperature, forbid, seed, draw, row_part, stream_id, out_tokens, out_ld, out_col, emb,
+                                  emb_off, C, next_h, nucleus, P, keep_count, rep);
 }
 
 // row_draw[0 .. R) += 1: the per-row form of the executor's one draw-index bump per sampled frame
@@ -385,6 +454,68 @@ extern "C" int ua2_sample_topp_rows(int dtype, int32_t M, const float* logits, i
                        row_draw, stream_id, out_tokens, out_ld, out_col, emb, emb_row_offset, C, next_h, nucleus, P, keep_count);
   else {
     ua2_set_error("ua2_sample_topp_rows: bad dtype %d", dtype);
+    return -1;
+  }
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int DT>
+static void launch_penalized(const ua2_sample_args& a, bool topp, bool rows, int nucleus, unsigned long long P, const RepArgs& rep, hipStream_t s) {
+#define UA2_PEN_LAUNCH(TOPP, ROWS)                                                                                                         \
+  hipLaunchKernelGGL((sample_pen_kernel<DT, TOPP, ROWS>), dim3(a.M), dim3(1024), 0, s, a.logits, a.ld, a.V, a.topk, a.temperature, a.forbid, \
+                     (unsigned long long)a.seed, a.counter, a.row_key_shift, a.row_key, a.row_draw, a.stream_id, a.out_tokens, a.out_ld,    \
+                     a.out_col, a.emb, a.emb_row_offset, a.C, a.next_h, nucleus, P, a.keep_count, rep)
+  if (topp && rows) UA2_PEN_LAUNCH(true, true);
+  else if (topp) UA2_PEN_LAUNCH(true, false);
+  else if (rows) UA2_PEN_LAUNCH(false, true);
+  else UA2_PEN_LAUNCH(false, false);
+#undef UA2_PEN_LAUNCH
+}
+
+extern "C" int ua2_sample_penalized(const ua2_sample_args* a, void* stream) {
+  UA2_CHECK(a != nullptr, "ua2_sample_penalized: NULL arguments");
+  const bool rows = a->row_key || a->row_draw;
+  bool penal = false;
+  if (a->rep_hist) {                             // every range is checked before any launch, the off value of theta included
+    UA2_CHECK(a->rep_penalty > 0.f && a->rep_penalty < INFINITY, "ua2_sample_penalized: rep_penalty must be finite and > 0 (1 = off), got %g",
+              (double)a->rep_penalty);
+    UA2_CHECK(a->rep_window >= 1 && a->rep_window <= 512, "ua2_sample_penalized: rep_window must be in 1..512, got %d", a->rep_window);
+    penal = a->rep_penalty != 1.f;
+  }
+  if (!penal) {                                  // off: the existing launch, and the history is left alone
+    const bool topp = a->top_p != 0.f || a->keep_count;
+    if (rows && topp)
+      return ua2_sample_topp_rows(a->dtype, a->M, a->logits, a->ld, a->V, a->topk, a->temperature, a->forbid, a->row_key, a->row_draw, a->stream_id,
+                                  a->out_tokens, a->out_ld, a->out_col, a->emb, a->emb_row_offset, a->C, a->next_h, a->top_p, a->keep_count, stream);
+    if (rows)
+      return ua2_sample_topk_rows(a->dtype, a->M, a->logits, a->ld, a->V, a->topk, a->temperature, a->forbid, a->row_key, a->row_draw, a->stream_id,
+                                  a->out_tokens, a->out_ld, a->out_col, a->emb, a->emb_row_offset, a->C, a->next_h, stream);
+    if (topp)
+      return ua2_sample_topp(a->dtype, a->M, a->logits, a->ld, a->V, a->topk, a->temperature, a->forbid, a->seed, a->counter, a->stream_id,
+                             a->out_tokens, a->out_ld, a->out_col, a->emb, a->emb_row_offset, a->C, a->next_h, a->row_key_shift, a->top_p,
+                             a->keep_count, stream);
+    return ua2_sample_topk(a->dtype, a->M, a->logits, a->ld, a->V, a->topk, a->temperature, a->forbid, a->seed, a->counter, a->stream_id,
+                           a->out_tokens, a->out_ld, a->out_col, a->emb, a->emb_row_offset, a->C, a->next_h, a->row_key_shift, stream);
+  }
+  UA2_CHECK(a->V <= (1 << 17), "ua2_sample_penalized: V = %d: the membership set of the penalty is sized for V <= 131072", a->V);
+  UA2_CHECK(a->rep_len && a->rep_cap >= a->rep_window && a->rep_hist_ld >= a->rep_cap && a->rep_len_ld >= 1,
+            "ua2_sample_penalized: the history needs rep_len, rep_cap >= rep_window, rep_hist_ld >= rep_cap and rep_len_ld >= 1");
+  int nucleus = 0;
+  unsigned long long P = 0ull;
+  if (int rc = topp_arguments("ua2_sample_penalized", a->V, a->top_p, &nucleus, &P)) return rc;
+  UA2_CHECK(a->M > 0 && a->logits && a->V > 0 && a->out_tokens, "ua2_sample_penalized: bad arguments");
+  UA2_CHECK(rows ? (a->row_key && a->row_draw) : (a->counter && a->row_key_shift >= 0 && a->row_key_shift <= 1),
+            "ua2_sample_penalized: row_key and row_draw go together; the shared stream needs counter and row_key_shift in 0..1");
+  UA2_CHECK(a->temperature > 0.f, "temperature must be > 0");
+  UA2_CHECK(a->topk >= 1 && a->topk <= a->V, "topk must be in 1..%d", a->V);
+  UA2_CHECK(!a->emb || a->next_h, "ua2_sample_penalized: next_h is NULL");
+  const RepArgs rep{a->rep_penalty, a->rep_window, a->rep_cap, a->rep_hist, a->rep_hist_ld, a->rep_len, a->rep_len_ld};
+  const bool topp = nucleus || a->keep_count;
+  if (a->dtype == UA2_BF16) launch_penalized<UA2_BF16>(*a, topp, rows, nucleus, P, rep, (hipStream_t)stream);
+  else if (a->dtype == UA2_F32) launch_penalized<UA2_F32>(*a, topp, rows, nucleus, P, rep, (hipStream_t)stream);
+  else {
+    ua2_set_error("ua2_sample_penalized: bad dtype %d", a->dtype);
     return -1;
   }
   UA2_LAUNCH_CHECK();

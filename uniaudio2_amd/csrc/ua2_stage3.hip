@@ -19,10 +19,10 @@
 
 namespace {
 // What a recorded frame bakes in beyond the plan's own state (the setters drop the graphs with theirs).  mode: without its flag bits;
-// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only; row_streams, topp_bits: top-k frames only (topp_bits 0 = off)
+// defer_slots: frame slots of the stash ring, 0 = not deferring; ngram_n: mode 1 only; row_streams, topp_bits, rep_bits, rep_window: top-k frames only (topp_bits 0 / rep_window 0 = off)
 struct FrameKey {
-  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits;
-  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits); }
+  int rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits, rep_bits, rep_window;
+  auto tied() const { return std::tie(rows, mode, skip_text, skip_experts, defer_slots, ngram_n, eos, card, topk, temp_bits, cfg_bits, row_streams, topp_bits, rep_bits, rep_window); }
   bool operator<(const FrameKey& o) const { return tied() < o.tied(); }
 };
 }  // namespace
@@ -81,6 +81,10 @@ struct ua2_stage3 {
   int32_t topk = 1;            // 1 = greedy (fused arg-max partials); > 1 = ua2_sample_topk
   float temperature = 1.f;
   float top_p = 0.f;           // 0 < top_p < 1 with topk > 1: the samplers run the nucleus tail (ua2_sample_topp); 0 / 1 = off
+  // repetition penalty of the samplers (ua2_stage3_set_rep_penalty; rep_window == 0 = off): caller-owned device rings [max_batch][1 + n_cb][rep_window]
+  float rep_penalty = 1.f;
+  int32_t rep_window = 0;
+  int32_t *rep_hist = nullptr, *rep_len = nullptr;
   hipStream_t cap_stream = nullptr;                 // capture-only stream (the caller's may be the null stream, which cannot capture)
   float cfg_scale = 1.f;       // > 1: classifier-free guidance over a (conditional, unconditional) row pair
   int32_t order_free_rows = 0; // > 0 (bf16 plans): GPT launches (trunk and depth decoder) of at least this many rows take UA2_SUM_ORDER_FREE (ua2_stage3_set_order_free_rows)
@@ -790,6 +794,21 @@ extern "C" int ua2_stage3_set_top_p(ua2_stage3* h, float top_p) {
   return 0;
 }
 
+extern "C" int ua2_stage3_set_rep_penalty(ua2_stage3* h, float penalty, int32_t window, int32_t* hist, int32_t* len) {
+  UA2_CHECK(h != nullptr, "ua2_stage3_set_rep_penalty: NULL handle");
+  UA2_CHECK(penalty > 0.f && penalty < INFINITY, "ua2_stage3_set_rep_penalty: penalty must be finite and > 0 (1 = off), got %g", (double)penalty);
+  if (penalty == 1.f || (!hist && !len)) {   // off: the frame graphs key on (penalty, window), so the penalised ones stay valid for the same buffers
+    h->rep_penalty = 1.f; h->rep_window = 0;
+    return 0;
+  }
+  UA2_CHECK(window >= 1 && window <= 512, "ua2_stage3_set_rep_penalty: window must be in 1..512, got %d", window);
+  UA2_CHECK(hist && len, "ua2_stage3_set_rep_penalty: hist and len go together");
+  UA2_CHECK(h->d.va <= (1 << 17) && h->d.vt <= (1 << 17), "ua2_stage3_set_rep_penalty: the penalised samplers serve vocabularies up to 131072 columns");
+  if (hist != h->rep_hist || len != h->rep_len) drop_graphs(h);   // recorded top-k frames bake the samplers' arguments
+  h->rep_penalty = penalty; h->rep_window = window; h->rep_hist = hist; h->rep_len = len;
+  return 0;
+}
+
 extern "C" int ua2_stage3_set_prefill_groups(ua2_stage3* h, const int32_t* group_rows, const int32_t* group_seq, const int32_t* group_nkeys,
                                              int32_t n_groups, int32_t group_q_tiles) {
   UA2_CHECK(h != nullptr, "ua2_stage3_set_prefill_groups: NULL handle");
@@ -984,6 +1003,18 @@ static int heads_impl(ua2_stage3* h, int32_t R, bool text_only, void* stream, bo
   // seed and draw index with the row index in the key
   const bool nucleus = h->top_p > 0.f && h->top_p < 1.f;
   auto sample = [&](const float* logits, int ld, int V, int topk, const int32_t* forbid, int stream_id, const void* emb, int emb_off, float* next_h) -> int {
+    if (h->rep_window > 0) {             // penalised: every form behind the one entry, against the ring of (row, stream_id)
+      UA2_CHECK(R <= d.max_batch, "ua2_stage3_heads: the repetition histories hold %d rows, R=%d", d.max_batch, R);
+      ua2_sample_args a{};
+      a.dtype = d.dtype; a.M = R; a.logits = logits; a.ld = ld; a.V = V; a.topk = topk; a.temperature = h->temperature; a.forbid = forbid;
+      a.stream_id = stream_id; a.out_tokens = d.out_tokens; a.out_ld = w; a.out_col = stream_id; a.emb = emb; a.emb_row_offset = emb_off; a.C = C;
+      a.next_h = next_h; a.top_p = nucleus ? h->top_p : 0.f;
+      if (h->row_streams) { a.row_key = h->row_key; a.row_draw = h->row_draw; }
+      else { a.counter = d.counters + 1; a.row_key_shift = key_shift; }
+      a.rep_penalty = h->rep_penalty; a.rep_window = a.rep_cap = h->rep_window; a.rep_hist_ld = w * h->rep_window; a.rep_len_ld = w;
+      a.rep_hist = h->rep_hist + (size_t)stream_id * h->rep_window; a.rep_len = h->rep_len + stream_id;
+      return ua2_sample_penalized(&a, s);
+    }
     if (nucleus && h->row_streams)
       return ua2_sample_topp_rows(d.dtype, R, logits, ld, V, topk, h->temperature, forbid, h->row_key, h->row_draw, stream_id, d.out_tokens, w,
                                   stream_id, emb, emb_off, C, next_h, h->top_p, nullptr, s);
@@ -1161,6 +1192,7 @@ extern "C" int ua2_stage3_frame(ua2_stage3* h, int32_t R, int32_t mode, int32_t 
   memcpy(&key.temp_bits, &h->temperature, sizeof(int)); memcpy(&key.cfg_bits, &h->cfg_scale, sizeof(int));
   key.row_streams = (h->row_streams && h->topk != 1) ? 1 : 0;     // greedy frames neither read nor advance the streams
   if (h->topk != 1 && h->top_p > 0.f && h->top_p < 1.f) memcpy(&key.topp_bits, &h->top_p, sizeof(int));   // (0 < top_p < 1: never the bits of 0)
+  if (h->topk != 1 && h->rep_window > 0) { memcpy(&key.rep_bits, &h->rep_penalty, sizeof(int)); key.rep_window = h->rep_window; }
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     hipGraph_t graph = nullptr;

@@ -77,6 +77,10 @@ class GeneratorBase:
     # samples (topk > 1): the audio loops, single and batched (row seeds, admission, guided pairs), and the text loops; greedy loops
     # ignore it.  Pure nucleus sampling is topk = the audio vocabulary width.
     top_p = 0.0
+    # Repetition penalty of every sampled loop (CLI --repetition_penalty / --repetition_window; Model_stage3.set_repetition_penalty; not in
+    # the reference, effect on audio quality not measured): 1.0 = off.  It applies where top_p does; greedy loops and beam search ignore it.
+    repetition_penalty = 1.0
+    repetition_window = 64
 
     def __init__(self, model, train_args, audio_tokenizer_config=None, audio_model_path=None,
                  text_tokenizer_path=None, is_cfg=False):
@@ -195,6 +199,11 @@ class GeneratorBase:
         if top_p != 0.0 or getattr(self, "_top_p_set", 0.0) != 0.0:
             self._model.set_top_p(top_p)
             self._top_p_set = top_p
+        # repetition penalty (Model_stage3.set_repetition_penalty): the same rule
+        rep = (float(self.repetition_penalty), int(self.repetition_window))
+        if rep[0] != 1.0 or getattr(self, "_rep_set", (1.0, 64))[0] != 1.0:
+            self._model.set_repetition_penalty(*rep)
+            self._rep_set = rep
 
     def _prefill(self, rows_tokens, rows_mask):
         """rows_*: list of (L, 9) prompts of equal length (1, or 2 with CFG; tts_task.py:228-245)."""

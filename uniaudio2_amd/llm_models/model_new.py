@@ -14,6 +14,7 @@ ua2_stage3_*): one C call per prefill chunk / per frame, hipGraph replay for the
 with the sample -> next-input feedback, forbid_prefix switch and frame log all on device.
 """
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -263,6 +264,7 @@ class Model_stage3(nn.Module):
         self.weight_dtype = None       # torch.float8_e4m3fn: every bf16 plan setup_caches builds computes with the fp8 weight-only forms W' and streams fp8 images in its few-row launches (CLI --weight_dtype)
         self.order_free_rows = 0       # > 0: every plan setup_caches builds opts its many-row launches into the order-free GEMM (CLI --order_free_rows)
         self.top_p = 0.0               # set_top_p: nucleus filter of the sampled heads (0 = off), re-applied to every plan setup_caches builds
+        self.repetition_penalty = (1.0, 64)   # set_repetition_penalty: (penalty, window) of the sampled heads (1.0 = off), re-applied likewise
 
     # ---- caches / device plan ----------------------------------------------------------------
     def setup_caches(self, max_batch_size: int, dtype: Optional[torch.dtype] = None, max_seq_length: int = 2048,
@@ -356,6 +358,8 @@ class Model_stage3(nn.Module):
             self.set_order_free_rows(self.order_free_rows)
         if getattr(self, "top_p", 0.0) > 0.0:
             self.set_top_p(self.top_p)         # a new plan starts with the filter off: re-apply what set_top_p remembered
+        if getattr(self, "repetition_penalty", (1.0, 64))[0] != 1.0:
+            self.set_repetition_penalty(*self.repetition_penalty)
         if weight_dtype is not None:
             for g in (self.audio_understanding_expert, self.backbone, self.audio_generation_expert, self.decoder):
                 w8 += g.plan["w8"]
@@ -466,6 +470,8 @@ class Model_stage3(nn.Module):
         if "ngram_len" in st:                      # rows that start here start with an empty n-gram history
             st["ngram_len"][:R].zero_()
             self._ngram_hi = 0                     # (every row: a session starts here)
+        if "rep_len" in st:                        # ... and with empty repetition histories
+            st["rep_len"][:R].zero_()
         return R
 
     def _run_chunks(self, tk, mk, ps, sq, chunk, groups, after=None):
@@ -671,6 +677,38 @@ class Model_stage3(nn.Module):
         self.top_p = top_p
         if self._h is not None:
             check(lib.ua2_stage3_set_top_p(self._h, top_p), "ua2_stage3_set_top_p")
+
+    def set_repetition_penalty(self, penalty: float = 1.0, window: int = 64):
+        """Repetition penalty of the sampled heads (include/ua2hip.h ua2_sample_penalized / ua2_stage3_set_rep_penalty; the CTRL /
+        Hugging Face rule over a window; not in the reference): with set_sampling(topk > 1, ...) and penalty != 1 every sampler reads
+        the logits of the distinct ids among the last `window` ids ITS stream has produced for the row (0 = text head, 1 + i = audio
+        codebook i; prompt tokens do not count) as l * penalty if l < 0 else l / penalty, before the temperature, and appends the id
+        it draws.  The histories (st["rep_hist"] [B, 1 + n_cb, window], st["rep_len"] [B, 1 + n_cb]) are allocated on first use (and
+        again for a new window), start empty for every row that begin_decode / begin_ragged / admit_rows starts, and travel with
+        retire_rows.  penalty = 1.0 (the default) clears it.  Greedy frames, beam search and scoring ignore it.  The value is
+        remembered and re-applied to every plan setup_caches builds.  Its effect on audio quality is not measured: no trained
+        checkpoint ships."""
+        penalty, window = float(penalty), int(window)
+        if not (math.isfinite(penalty) and penalty > 0.0):
+            raise ValueError(f"repetition penalty must be finite and > 0 (1 = off), got {penalty}")
+        if not 1 <= window <= 512:
+            raise ValueError(f"repetition window must be in 1..512, got {window}")
+        self.repetition_penalty = (penalty, window)
+        if self._h is None:
+            return
+        st = self._st
+        if penalty == 1.0:
+            check(lib.ua2_stage3_set_rep_penalty(self._h, 1.0, window, None, None), "ua2_stage3_set_rep_penalty")
+            return
+        if max(st["va"], self.backbone.config.padded_vocab_size) > 131072:
+            raise ValueError("the repetition penalty serves vocabularies up to 131072 columns")
+        if "rep_hist" not in st or st["rep_hist"].shape[2] != window:
+            with torch.inference_mode(False):      # decode state like the rest of st: written in and out of inference mode
+                i32 = dict(dtype=torch.int32, device=st["device"])
+                st["rep_hist"] = torch.zeros(st["B"], st["ncb"] + 1, window, **i32)
+                st["rep_len"] = torch.zeros(st["B"], st["ncb"] + 1, **i32)      # a new history: every row starts empty
+        check(lib.ua2_stage3_set_rep_penalty(self._h, penalty, window, st["rep_hist"].data_ptr(), st["rep_len"].data_ptr()),
+              "ua2_stage3_set_rep_penalty")
 
     def set_row_seeds(self, seeds, rows=None):
         """Per-row sampler streams (include/ua2hip.h ua2_stage3_set_row_streams): row rows[i] (default i) of the decode state draws
@@ -889,7 +927,7 @@ class Model_stage3(nn.Module):
         return len(keep)
 
     # the per-row decode state: what retire_rows permutes and admit_rows keeps across its prefill
-    _ROW_STATE = ("tokens", "mask", "row_pos", "forbid", "out_tokens", "ngram_hist", "ngram_len", "row_key", "row_draw")
+    _ROW_STATE = ("tokens", "mask", "row_pos", "forbid", "out_tokens", "ngram_hist", "ngram_len", "row_key", "row_draw", "rep_hist", "rep_len")
 
     @torch.inference_mode()
     def admit_rows(self, prompts, batch: int, seeds=None):
@@ -921,7 +959,7 @@ class Model_stage3(nn.Module):
         if self._row_streams and (seeds is None or len(seeds) != n):
             raise ValueError(f"row streams are on (set_row_seeds): admit_rows needs one seed per prompt, got {seeds}")
         # the prefill loads its chunks through rows 0.. of these (_load_rows): whole copies, the live rows among them
-        saved = {k: st[k].clone() for k in ("tokens", "mask", "row_pos", "row_seq", "ngram_len") if k in st}
+        saved = {k: st[k].clone() for k in ("tokens", "mask", "row_pos", "row_seq", "ngram_len", "rep_len") if k in st}
         ngram_rows = list(self._ngram_rows)
         pre = [i for i in range(n) if Ls[i] > 1]
         if pre:
@@ -938,6 +976,8 @@ class Model_stage3(nn.Module):
         st["forbid"][new] = 0
         if "ngram_len" in st:
             st["ngram_len"][new] = 0
+        if "rep_len" in st:
+            st["rep_len"][new] = 0
         if self._row_streams:
             self.set_row_seeds(seeds, rows=range(batch, batch + n))
         self._pos_hi = max(self._pos_hi, max(Ls) - 1)

@@ -20,6 +20,12 @@ Differences, all explicit:
   * `--top_p P` (default 0 = off) adds the nucleus filter of the reference's llm_utils/sampling.py sample_top_p to every sampled loop,
     on the device, after the --topk threshold; ties at the threshold value are all kept.  Pure nucleus sampling is --topk = the audio
     vocabulary width (--topk 0 stays refused).  Outside [0, 1] it raises ValueError before a model is built.
+  * `--repetition_penalty P` (default 1 = off) with `--repetition_window W` (default 64, 1..512) adds a repetition penalty to every sampled
+    loop, on the device inside the samplers: each stream (text head, every audio codebook) of each utterance reads the logits of the distinct
+    ids among the last W ids it has produced as l * P if l < 0 else l / P, before the temperature (the CTRL / Hugging Face rule over a
+    window; prompt tokens do not count).  Not in the reference, and its effect on audio quality is not measured (no trained checkpoint
+    ships).  It routes where --top_p routes; the greedy understanding tasks ignore it; a bad value, or P != 1 with --topk 1 on a generation
+    task or with --beam_width, raises ValueError before a model is built.
   * --decode_type ngram (ASR / Yue_ASR: generate_asr_with_ngram_sampling, greedy, n = 3, as the reference's :310-322) runs the
     n-gram filter on the device; its prefill is generate_asr's (the reference's trains-mode prefill leaves the experts' caches
     empty, evaluation/asr_task.py).  lyric_recognition + ngram raises ValueError (the reference's lyric Generator has no such
@@ -59,6 +65,7 @@ Differences, all explicit:
 import argparse
 import glob
 import json
+import math
 import os
 import random
 
@@ -203,6 +210,35 @@ def _apply_top_p(args, generator):
     top_p = _check_top_p(args)
     if top_p != 0.0:
         generator.top_p = top_p
+    return generator
+
+
+def _check_repetition(args, generation):
+    """--repetition_penalty / --repetition_window: 1.0 = off; refused before a model is built: a penalty that is not finite or not > 0, a
+    window outside 1..512, a penalty != 1 with --topk 1 on a generation task (a greedy frame has no logits pass to penalise) or with
+    --beam_width (beam search ranks the logits itself).  -> (penalty, window)."""
+    penalty = getattr(args, "repetition_penalty", None)
+    penalty = 1.0 if penalty is None else float(penalty)
+    window = getattr(args, "repetition_window", None)
+    window = 64 if window is None else int(window)
+    if not (math.isfinite(penalty) and penalty > 0.0):
+        raise ValueError(f"--repetition_penalty must be finite and > 0 (1 = off), got {penalty}")
+    if not 1 <= window <= 512:
+        raise ValueError(f"--repetition_window must be in 1..512, got {window}")
+    if penalty != 1.0:
+        if generation and int(getattr(args, "topk", 50) or 0) == 1:
+            raise ValueError("--repetition_penalty needs a sampled loop: with --topk 1 the frame is greedy and has no logits pass to penalise")
+        if int(getattr(args, "beam_width", 0) or 0) >= 1:
+            raise ValueError("--repetition_penalty does not combine with --beam_width: beam search ranks the logits itself "
+                             "(--beam_no_repeat_ngram N bans repeated n-grams inside the beam)")
+    return penalty, window
+
+
+def _apply_repetition(args, generator, generation):
+    """As _apply_top_p: the generator hears of the penalty only when it is on."""
+    penalty, window = _check_repetition(args, generation)
+    if penalty != 1.0:
+        generator.repetition_penalty, generator.repetition_window = penalty, window
     return generator
 
 
@@ -386,6 +422,7 @@ def run_understanding(args):
     task = args.task.strip().lower()
     _check_understanding_decode(args, task)
     _check_top_p(args)
+    _check_repetition(args, False)
     raw_audio = _has_raw_audio(args)
     if raw_audio:
         token_dir, names = args.output_dir, []
@@ -402,6 +439,7 @@ def run_understanding(args):
                                            audio_model_path=args.audio_model_path, text_tokenizer_path=args.text_tokenizer_path,
                                            is_cfg=args.use_cfg)
     _apply_top_p(args, generator)
+    _apply_repetition(args, generator, False)
     if raw_audio:
         token_dir, names = _encode_audio_to_tokens(args, generator, args.output_dir, "pass --reason_pt + --semantic_pt or --token_dir")
     beam_batch = int(getattr(args, "batch_size", 1) or 1) if int(getattr(args, "beam_width", 0) or 0) >= 1 else 1
@@ -463,6 +501,7 @@ def run_generation_stage1(args):
     task = args.task.strip().lower()
     _check_decode(args)
     _check_top_p(args)
+    _check_repetition(args, True)
     os.makedirs(args.output_dir, exist_ok=True)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():
@@ -472,6 +511,7 @@ def run_generation_stage1(args):
                                            audio_model_path=args.audio_model_path, text_tokenizer_path=args.text_tokenizer_path,
                                            is_cfg=args.use_cfg)
     _apply_top_p(args, generator)
+    _apply_repetition(args, generator, True)
     tok = generator._text_tokenizer
     task_prompt = _get_prompt_tensor(args, tok, args.task)
     if task == "speech_s2s":
@@ -670,6 +710,14 @@ def get_parser():
         p.add_argument(f"--{name}", type=str, default=None)
     p.add_argument("--text", type=str, default="")
     p.add_argument("--output_dir", type=str, default="./multi_task_out")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="repetition penalty of the sampled loops (extension, not in the reference; the CTRL / Hugging Face rule over a window): "
+                        "every sampler reads the logits of the distinct ids among the last --repetition_window ids its own stream (text head, each "
+                        "audio codebook) has produced for the utterance as l * penalty if l < 0 else l / penalty, before --temperature.  1 = off "
+                        "(default); prompt tokens do not count.  It acts where --top_p does: the sampled audio loops (single, --batch_size, "
+                        "--use_cfg) and speech_s2t; the greedy understanding tasks ignore it, and it is refused with --topk 1 on a generation task "
+                        "and with --beam_width.  Its effect on audio quality is not measured: no trained checkpoint ships")
+    p.add_argument("--repetition_window", type=int, default=64, help="ids of history the repetition penalty looks back over, per stream (1..512)")
     p.add_argument("--use_cfg", type=str2bool, default=False)
     p.add_argument("--temperature", type=float, default=0.9)
     p.add_argument("--topk", type=int, default=50)
@@ -729,6 +777,7 @@ def main(argv=None):
     args = get_parser().parse_args(argv)
     _check_top_p(args)
     task = args.task.strip().lower()
+    _check_repetition(args, task not in [t.lower() for t in UNDERSTANDING_TASKS])
     if task in [t.lower() for t in UNDERSTANDING_TASKS]:
         has_input = ((args.audio and os.path.isfile(args.audio)) or (args.audio_dir and os.path.isdir(args.audio_dir)) or
                      (args.reason_pt and args.semantic_pt and os.path.isfile(args.reason_pt) and os.path.isfile(args.semantic_pt)) or
