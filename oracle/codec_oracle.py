@@ -216,13 +216,17 @@ def audio2token(orig_samples, fetch_codes_batch, mel_fn=None, sample_rate: int =
     return reason[:, :output_len_reason, :].transpose(1, 2), rec[:, :output_len, :].transpose(1, 2)
 
 
-# ---- torchaudio.functional.resample (reason_tokenizer.py:383-385) — PARITY UNPINNED: torchaudio is not installed ---------
+# ---- torchaudio.functional.resample (reason_tokenizer.py:383-385) — torchaudio is not installed; pinned instead by two independent
+# statements in tests/test_frontend_refs_host.py: the plain double sum over the windowed sinc, and analytic tones ---------
 
 def resample(waveform, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
     """Restatement of torchaudio's published sinc_interp_hann algorithm (`_get_sinc_resample_kernel` +
     `_apply_sinc_resample_kernel`) with its defaults, as the reference calls it: float64 index grid, clamp to the filter
     width, Hann window cos^2, sinc, scale; then a strided conv1d of the (width, width + orig) padded signal.
-    waveform (C, L) fp32 -> (C, ceil(new * L / orig))."""
+    waveform (C, L) fp32 -> (C, ceil(new * L / orig)).
+    Parity with the package itself cannot be run (it is not installed).  In its place tests/test_frontend_refs_host.py holds this
+    function to (1) tests/frontend_refs.py `resample_direct`, the interpolation y[j] = sum_i x[i] h(j / new - i / orig) written
+    without frames, padding or phases, within the filter bank's fp32 rounding, and (2) analytic 1 kHz / 3 kHz tones within 2e-3."""
     import math
     if int(orig_freq) == int(new_freq):
         return waveform

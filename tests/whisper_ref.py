@@ -140,21 +140,25 @@ def _ln(x, w, b, eps=1e-5):
     return xc * torch.rsqrt((xc * xc).mean(-1, keepdim=True) + eps) * w + b
 
 
-def encoder_ref(sd, cfg, mels, plain=False):
-    """mels [B, 80, 2 P] -> (last_hidden_state [B, P, d], stem output [B, P, d] after the positional add), computed in the dtype
-    of `sd` / `mels`.  plain=True: the same network through torch's own fused ops (F.conv1d, F.layer_norm, F.gelu, SDPA) — the
-    form a PyTorch user would write, for timing comparisons."""
+def encoder_ref(sd, cfg, mels, plain=False, rnd=None):
+    """mels [B, 80, T] -> (last_hidden_state [B, P, d], stem output [B, P, d] after the positional add), P = (T - 1) // 2 + 1, computed
+    in the dtype of `sd` / `mels`.  plain=True: the same network through torch's own fused ops (F.conv1d, F.layer_norm, F.gelu, SDPA) —
+    the form a PyTorch user would write, for timing comparisons.  rnd (default off; not with plain): a rounding applied to both
+    operands of every matrix product and to the cached k, v — kernel_refs.bf16_once makes this the model of the bf16 plan (bf16
+    operands, wide accumulation, everything between the products left in the working dtype)."""
     F = torch.nn.functional
     heads, d = cfg["encoder_attention_heads"], cfg["d_model"]
     hd = d // heads
     B = mels.shape[0]
+    assert not (plain and rnd is not None)
+    r = rnd if rnd is not None else (lambda t: t)
     if plain:
         h = F.gelu(F.conv1d(mels, sd["conv1.weight"], sd["conv1.bias"], padding=1))
         h = F.gelu(F.conv1d(h, sd["conv2.weight"], sd["conv2.bias"], stride=2, padding=1)).permute(0, 2, 1)
     else:
         tm = lambda w: w.permute(0, 2, 1).reshape(w.shape[0], -1)
-        h = _gelu(_taps(mels.transpose(1, 2), 1) @ tm(sd["conv1.weight"]).t() + sd["conv1.bias"])
-        h = _gelu(_taps(h, 2) @ tm(sd["conv2.weight"]).t() + sd["conv2.bias"])
+        h = _gelu(r(_taps(mels.transpose(1, 2), 1)) @ r(tm(sd["conv1.weight"])).t() + sd["conv1.bias"])
+        h = _gelu(r(_taps(h, 2)) @ r(tm(sd["conv2.weight"])).t() + sd["conv2.bias"])
     h = h + sd["embed_positions.weight"]
     stem = h
     P = h.shape[1]
@@ -165,20 +169,21 @@ def encoder_ref(sd, cfg, mels, plain=False):
             x = F.layer_norm(h, (d,), g("self_attn_layer_norm.weight"), g("self_attn_layer_norm.bias"))
         else:
             x = _ln(h, g("self_attn_layer_norm.weight"), g("self_attn_layer_norm.bias"))
-        q = (x @ g("self_attn.q_proj.weight").t() + g("self_attn.q_proj.bias")).view(B, P, heads, hd).transpose(1, 2)
-        k = (x @ g("self_attn.k_proj.weight").t()).view(B, P, heads, hd).transpose(1, 2)
-        v = (x @ g("self_attn.v_proj.weight").t() + g("self_attn.v_proj.bias")).view(B, P, heads, hd).transpose(1, 2)
+        x = r(x)
+        q = (x @ r(g("self_attn.q_proj.weight")).t() + g("self_attn.q_proj.bias")).view(B, P, heads, hd).transpose(1, 2)
+        k = r((x @ r(g("self_attn.k_proj.weight")).t()).view(B, P, heads, hd).transpose(1, 2))
+        v = r((x @ r(g("self_attn.v_proj.weight")).t() + g("self_attn.v_proj.bias")).view(B, P, heads, hd).transpose(1, 2))
         if plain:
             o = F.scaled_dot_product_attention(q, k, v)
         else:
-            o = torch.softmax((q @ k.transpose(-1, -2)) * (1.0 / math.sqrt(hd)), dim=-1) @ v
+            o = r(torch.softmax((r(q) @ k.transpose(-1, -2)) * (1.0 / math.sqrt(hd)), dim=-1)) @ v
         o = o.transpose(1, 2).reshape(B, P, d)
-        h = h + (o @ g("self_attn.out_proj.weight").t() + g("self_attn.out_proj.bias"))
+        h = h + (r(o) @ r(g("self_attn.out_proj.weight")).t() + g("self_attn.out_proj.bias"))
         if plain:
             x = F.gelu(F.linear(F.layer_norm(h, (d,), g("final_layer_norm.weight"), g("final_layer_norm.bias")), g("fc1.weight"), g("fc1.bias")))
         else:
-            x = _gelu(_ln(h, g("final_layer_norm.weight"), g("final_layer_norm.bias")) @ g("fc1.weight").t() + g("fc1.bias"))
-        h = h + (x @ g("fc2.weight").t() + g("fc2.bias"))
+            x = _gelu(r(_ln(h, g("final_layer_norm.weight"), g("final_layer_norm.bias"))) @ r(g("fc1.weight")).t() + g("fc1.bias"))
+        h = h + (r(x) @ r(g("fc2.weight")).t() + g("fc2.bias"))
     if plain:
         return F.layer_norm(h, (d,), sd["layer_norm.weight"], sd["layer_norm.bias"]), stem
     return _ln(h, sd["layer_norm.weight"], sd["layer_norm.bias"]), stem

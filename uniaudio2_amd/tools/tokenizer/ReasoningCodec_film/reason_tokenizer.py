@@ -98,9 +98,11 @@ def crossfade_concat(segments, wav_window, wav_ovlp, target_len):
 
 def resample_kernel(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     """Filter bank of `torchaudio.functional.resample` (sinc_interp_hann, the defaults reason_tokenizer.py:383-385 uses):
-    [new/gcd, 2*width + orig/gcd] fp32 + width.  torchaudio is not installed here (parity with the package UNPINNED,
-    SURVEY.md §8d config 1); this follows its published algorithm: float64 index grid, clamp to the filter width,
-    Hann window cos^2, sinc, scale by base_freq / orig."""
+    [new/gcd, 2*width + orig/gcd] fp32 + width.  torchaudio is not installed here; this follows its published algorithm:
+    float64 index grid, clamp to the filter width, Hann window cos^2, sinc, scale by base_freq / orig.  In the package's
+    place two independent statements pin it (tests/frontend_refs.py, tests/test_frontend_refs_host.py): the polyphase form with
+    this bank equals the plain double sum y[j] = sum_i x[i] h(j / new - i / orig) to the bank's fp32 rounding, and carries
+    1 kHz / 3 kHz tones to the new rate within 2e-3 (a one-sample slip: >= 0.258)."""
     g = math.gcd(int(orig_freq), int(new_freq))
     o, n = int(orig_freq) // g, int(new_freq) // g
     base = min(o, n) * rolloff
@@ -116,11 +118,20 @@ def resample_kernel(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     return kernels.to(torch.float32).view(n, -1), width, o, n
 
 
-def resample(wav, orig_freq, new_freq):
+RESAMPLE_MAX_ROWS = 1 << 20     # GEMM rows per launch of `resample`
+
+
+def resample(wav, orig_freq, new_freq, max_rows=RESAMPLE_MAX_ROWS):
     """wav (C, L) fp32 on the device -> (C, ceil(new * L / orig)).  The polyphase FIR is one exact-fp32 GEMM: frames of
-    2*width + orig samples every `orig` samples (a strided view of the padded signal) x the [new, taps] filter bank."""
+    2*width + orig samples every `orig` samples (a strided view of the padded signal) x the [new, taps] filter bank.
+    The GEMM has one row per frame, so its M grows with the file `tokenize` hands over, and ua2_linear's forms size their grids
+    by M: the skinny form puts ceil(M / 64) workgroups on grid y (65 535 at most: 4.19 M rows, 175 s at 48 kHz), and which form
+    serves a launch is a cost model's choice.  The rows therefore go through in chunks of `max_rows` — data movement only: a
+    row's bits do not depend on the rows beside it (tests/test_gpu_frontend_parity.py) — which also bounds the staged operand."""
     if int(orig_freq) == int(new_freq):
         return wav
+    if max_rows < 1:
+        raise ValueError(f"resample: max_rows = {max_rows}")
     kern, width, o, n = resample_kernel(orig_freq, new_freq)
     C_, L = wav.shape
     taps = kern.shape[1]
@@ -132,11 +143,13 @@ def resample(wav, orig_freq, new_freq):
     for c in range(C_):
         x = torch.nn.functional.pad(wav[c].float(), (width, width + o))
         frames = x.unfold(0, taps, o)                                  # [n_frames, taps] strided view (data movement only)
-        fr = torch.zeros(frames.shape[0], kp, dtype=torch.float32, device=wav.device)
-        fr[:, :taps] = frames
-        y = torch.empty(fr.shape[0], n, dtype=torch.float32, device=wav.device)
-        ws = ops.linear_workspace(torch.float32, fr.shape[0], kp, wav.device)
-        ops.linear(dtype=torch.float32, M=fr.shape[0], N=n, K=kp, w0=wp, x=fr, y=y, workspace=ws)
+        y = torch.empty(frames.shape[0], n, dtype=torch.float32, device=wav.device)
+        for r0 in range(0, frames.shape[0], max_rows):
+            m = min(max_rows, frames.shape[0] - r0)
+            fr = torch.zeros(m, kp, dtype=torch.float32, device=wav.device)
+            fr[:, :taps] = frames[r0:r0 + m]
+            ws = ops.linear_workspace(torch.float32, m, kp, wav.device)
+            ops.linear(dtype=torch.float32, M=m, N=n, K=kp, w0=wp, x=fr, y=y[r0:r0 + m], workspace=ws)
         outs.append(y.reshape(-1)[:math.ceil(n * L / o)])
     return torch.stack(outs)
 
