@@ -248,6 +248,20 @@ def test_kernel_identity_local_attention_prologue():
         _assert_same(_identity_case(_lib.PRO_LOCAL_ATTN, _lib.EPI_RESIDUAL, 1, N, K, heads=heads, handover=True), (N, K))
 
 
+@pytest.mark.parametrize("M", [1, 5])
+def test_kernel_identity_where_the_fp8_and_13_bit_groups_disagree(M):
+    """K = 192 is 6 chunks: whole fp8 groups (2 chunks), no whole 13-bit group (4), so the one K class where the form function answers
+    differently per form.  The launcher gives it 4 waves x 4 chunks in a single round, which the fp8 fall-back form serves (a load per chunk):
+    one gemv_w8 launch, no gemv launch (_identity_case counts both), the twin's bits.  The 13-bit side of this K:
+    test_gpu_l13.py test_no_image_for_k_not_a_multiple_of_128."""
+    import ctypes as C
+    from uniaudio2_amd import _lib
+    w, c, mr = C.c_int32(), C.c_int32(), C.c_int32()
+    assert _lib.lib.ua2_debug_gemv_geometry(_lib.UA2_BF16, 32, 192, 1, C.byref(w), C.byref(c), C.byref(mr)) == 0
+    assert (w.value, c.value, mr.value) == (4, 4, 0)
+    _assert_same(_identity_case(_lib.PRO_CAST, _lib.EPI_STORE, M, 32, 192), (M, 32, 192))
+
+
 def test_direct_launch_refuses_what_the_fp8_kernel_does_not_serve():
     """Return codes only: more rows than the launchers give the decode kernel, an fp32 launch, a GELU epilogue."""
     from uniaudio2_amd import _lib, ops

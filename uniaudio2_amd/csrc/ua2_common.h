@@ -214,21 +214,30 @@ struct Ua2EnvInt {
   bool set() { load(); return present; }
 };
 
-// fp8 (OCP e4m3fn) weight-only twins of a launch's w0 / w1 (include/ua2hip.h ua2_pack_linear_w8): image + per-column exponents.
-// strict: the caller asked for an fp8 kernel by name — a launch it does not serve is an error, never the bf16 twin: the decode kernel
-// (ua2_linear_w8), or with `many` the weights-stationary kernel (ua2_linear_w8_many).
-struct Ua2W8 {
-  const void *q0 = nullptr, *q1 = nullptr;
-  const int8_t *e0 = nullptr, *e1 = nullptr;
-  bool strict = false, many = false;
-  // l13: q0 / q1 are lossless 13-bit images of a.w0 / a.w1 (ua2_pack_linear_l13) and e0 / e1 their per-tile base bytes: the decode kernel
-  // alone streams them (ua2_linear_l13; the executor's images), every other kernel reads a.w0 / a.w1 — the very same weights
-  bool l13 = false;
+// What a kernel that streams a weight image of a launch's w0 / w1 takes (by value): the images (q) and their side arrays (e) — int8_t
+// per-column exponents of an fp8 image, uint8_t per-tile base bytes of a 13-bit one.
+struct Ua2WImage {
+  const void *q0 = nullptr, *q1 = nullptr, *e0 = nullptr, *e1 = nullptr;
+};
+// What the host passes around.  form: UA2_W_FP8 = fp8 (OCP e4m3fn) weight-only twins (include/ua2hip.h ua2_pack_linear_w8; a.w0 / a.w1 hold
+// W'), which the decode kernel and the weights-stationary kernel stream; UA2_W_L13 = lossless 13-bit images of a.w0 / a.w1 themselves
+// (ua2_pack_linear_l13), which the decode kernel alone streams — every other kernel reads a.w0 / a.w1, the very same weights.
+// demand: OFFERED = stream the image where a kernel has a form for the launch, a.w0 / a.w1 elsewhere (the executor); DECODE / STATIONARY =
+// the caller asked for the decode kernel (ua2_linear_w8, ua2_linear_l13) or the weights-stationary kernel (ua2_linear_w8_many) by name:
+// a launch it does not serve is an error, never another kernel or a.w0 / a.w1 in its place.
+enum Ua2WForm { UA2_W_FP8, UA2_W_L13 };
+enum Ua2WDemand { UA2_W_OFFERED, UA2_W_DECODE, UA2_W_STATIONARY };
+struct Ua2Weights {
+  Ua2WImage img;
+  Ua2WForm form = UA2_W_FP8;
+  Ua2WDemand demand = UA2_W_OFFERED;
+  bool by_name() const { return demand != UA2_W_OFFERED; }
+  bool complete(int epilogue) const { return img.q0 && img.e0 && (epilogue != UA2_EPI_SWIGLU || (img.q1 && img.e1)); }   // every pointer the launch reads
 };
 // internal launchers used by both the op-level ABI and the frame executor
-// w8 != NULL: launches that the decode kernel or the weights-stationary kernel (6 .. UA2_SKINNY_W8_MAX_ROWS rows) serves stream the fp8
-// image instead of a.w0 / a.w1 (the same bits: a.w0 / a.w1 hold W')
-int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
+// w != NULL: launches that the decode kernel or (fp8) the weights-stationary kernel (6 .. UA2_SKINNY_W8_MAX_ROWS rows) serves stream the
+// image instead of a.w0 / a.w1 (the same bits)
+int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nullptr);
 int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_attn_local_launch(const ua2_attn_args& a, hipStream_t s);
 int ua2_gemv_rows_per_tile(int dtype, int K);   // rows one decode-kernel workgroup holds in LDS (ua2_gemv.hip)
@@ -264,7 +273,7 @@ int ua2_argmax_embed_launch(int dtype, int32_t M, int32_t n_part, int32_t limit,
                             int32_t out_ld, int32_t out_col, const void* emb, int32_t emb_row_offset, int32_t C, float* next_h, hipStream_t s);
 int ua2_kv_rows_extract(const void* k_pool, const void* v_pool, const int32_t* pos, int n, int n_kv, int hs, int esz, void* out_k, void* out_v, hipStream_t s);
 // decode-regime specialisation; returns 1 when the problem is outside its regime
-int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr);
+int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nullptr);
 // does the decode kernel have an fp8-weight form for this launch (bf16, K % 64 == 0, a (prologue, epilogue) pair of the decode frame, a geometry it tiles)?
 bool ua2_gemv_w8_ok(const ua2_linear_args& a);
 // ... and a form on the lossless 13-bit image (bf16, K % 128 == 0, the same pairs, a geometry whose wave ranges are whole groups of 4 chunks or

@@ -1184,7 +1184,7 @@ bool prefers_skinny2(const ua2_linear_args& a, int nt, int force) {
 }
 
 template <int DT>
-int launch_dt(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8) {
+int launch_dt(const ua2_linear_args& a, hipStream_t s, int force, const Ua2Weights* w8) {
   const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
   const ua2_gemv_geometry geo = ua2_pick_gemv_geometry(a.dtype, a.N, a.K, nt);
   if (a.x_packed) {
@@ -1213,7 +1213,7 @@ int launch_dt(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w
   const bool old_skinny = skinny_ok && (force == 4 || (force != 5 && choose_skinny(a, nt)));
   if (prefer2 || old_skinny)
     if (const int rc = ua2_skinny2_try_launch(a, geo, s, w8); rc <= 0) return rc;
-  if (w8 && w8->strict) return 1;                  // asked for by name: never another kernel on the twin in its place
+  if (w8 && w8->by_name()) return 1;                  // asked for by name: never another kernel on the twin in its place
   if (old_skinny) {
     switch (a.epilogue) {
       case UA2_EPI_STORE: launch_skinny<DT, UA2_EPI_STORE>(a, geo, s); break;
@@ -1255,14 +1255,14 @@ static bool gemm_takes(const ua2_linear_args& a, int force) {
   return force || a.M > ua2_gemv_rows_preferred(a.dtype, a.K);
 }
 
-bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2W8& w8) {
+bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2Weights& w8) {
   if (a.dtype != UA2_BF16 || a.M <= 0 || a.N <= 0 || a.K <= 0 || a.K % 64 || a.sum_order == UA2_SUM_ORDER_FREE || a.y_ln_w) return false;
   const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
   if (!gemm_takes(a, 0) || !prefers_skinny2(a, nt, 0)) return false;
   return ua2_skinny2_try_launch(a, ua2_pick_gemv_geometry(a.dtype, a.N, a.K, nt), nullptr, &w8, true) == 0;
 }
 
-int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8) {
+int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2Weights* w8) {
   if (!gemm_takes(a, force)) return 1;
   if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s, force, w8);
   return launch_dt<UA2_F32>(a, s, force, w8);

@@ -199,7 +199,7 @@ __device__ __forceinline__ typename WFrag<W8>::type weight_load(const u32x4* wp,
 // their registers (the CPW = 16 forms sit at the 128-register limit of a 16-wave workgroup).
 template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0, bool FOLD = false>
 __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, const int a_stride, const int red_off, const int rt,
-                                          const int bx, const int by, const Ua2W8* w8 = nullptr) {
+                                          const int bx, const int by, const Ua2WImage* w8 = nullptr) {
   constexpr int KC = Elem<DT>::KC, EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
   constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
   static_assert(W8 == 0 || DT == UA2_BF16, "fp8 weights and 13-bit images are bf16-plan options");
@@ -286,16 +286,16 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
 #pragma unroll
   for (int t = 0; t < NT; ++t) wexp[t] = 0;
   if constexpr (FP8) {
-    wexp[0] = w8->e0[bx * 16 + (tid & 15)];
-    if constexpr (NT == 2) wexp[1] = w8->e1[bx * 16 + (tid & 15)];
+    wexp[0] = static_cast<const int8_t*>(w8->e0)[bx * 16 + (tid & 15)];
+    if constexpr (NT == 2) wexp[1] = static_cast<const int8_t*>(w8->e1)[bx * 16 + (tid & 15)];
   }
   // 13-bit image: the tile's base byte (workgroup-uniform, needed at decode time only), spread to the four bytes of a dword
   unsigned base4[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) base4[t] = 0u;
   if constexpr (L13) {
-    base4[0] = (unsigned)reinterpret_cast<const unsigned char*>(w8->e0)[bx] * 0x01010101u;
-    if constexpr (NT == 2) base4[1] = (unsigned)reinterpret_cast<const unsigned char*>(w8->e1)[bx] * 0x01010101u;
+    base4[0] = (unsigned)static_cast<const uint8_t*>(w8->e0)[bx] * 0x01010101u;
+    if constexpr (NT == 2) base4[1] = (unsigned)static_cast<const uint8_t*>(w8->e1)[bx] * 0x01010101u;
   }
 
   WF wf[NT][NL];
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_kernel(const u
 // the same launch on the fp8 image of its weight(s): bf16 activations in LDS, bf16 MFMA, half the weight bytes
 template <int PRO, int EPI, int CPW, bool MR, int W8>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_w8_kernel(const ua2_linear_args a, const int a_stride,
-                                                                 const int red_off, const int rt, const Ua2W8 w8) {
+                                                                 const int red_off, const int rt, const Ua2WImage w8) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
 }
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_w8_kernel(cons
 // ... and on the lossless 13-bit image of the bf16 weights themselves (W8 = 3 / 4): 13/16 of the bytes, the same bits
 template <int PRO, int EPI, int CPW, bool MR, int W8>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_l13_kernel(const ua2_linear_args a, const int a_stride,
-                                                                  const int red_off, const int rt, const Ua2W8 w8) {
+                                                                  const int red_off, const int rt, const Ua2WImage w8) {
   static_assert(W8 == 3 || W8 == 4, "the 13-bit forms");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
@@ -715,142 +715,38 @@ Geometry pick_geometry(int nchunks, int blocks, int nt) {
   return Geometry{w, c};
 }
 
-template <int DT, int PRO, int EPI, int CPW, bool MR, bool FOLD = false>
-void launch_one(const ua2_linear_args& a, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
-  constexpr auto kern = gemv_kernel<DT, PRO, EPI, CPW, MR, FOLD>;
-  ua2_allow_big_lds<kern>();
-  hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt);
-  ua2_count_launch(UA2_CNT_GEMV);
+// grid, workgroup and LDS carve of a launch: a function of (N, K, M, dtype), the same whatever the weight stream
+struct Launch {
+  dim3 grid;
+  int waves, a_stride, red_off, rt;
+  size_t smem;
+  hipStream_t s;
+};
+
+// One launch of a decode-kernel instantiation.  extra: the weight image of gemv_w8_kernel / gemv_l13_kernel; counters: the families it counts in.
+template <auto Kern, class... Extra>
+void launch_one(std::initializer_list<int> counters, const ua2_linear_args& a, const Launch& l, const Extra&... extra) {
+  ua2_allow_big_lds<Kern>();
+  hipLaunchKernelGGL(Kern, l.grid, dim3(l.waves * 64), l.smem, l.s, a, l.a_stride, l.red_off, l.rt, extra...);
+  for (const int c : counters) ua2_count_launch(c);
 }
 
-template <int PRO, int EPI, int CPW, bool MR, int W8>
-void launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
-  constexpr auto kern = gemv_w8_kernel<PRO, EPI, CPW, MR, W8>;
-  ua2_allow_big_lds<kern>();
-  hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt, w8);
-  ua2_count_launch(UA2_CNT_GEMV_W8);
-}
+// chunks one load (set) of an image form carries: a K that is no whole number of them has no image
+constexpr int image_group(Ua2WForm form) { return form == UA2_W_L13 ? 4 : 2; }
 
-template <int PRO, int EPI, int CPW, bool MR, int W8>
-void launch_one_l13(const ua2_linear_args& a, const Ua2W8& w8, dim3 grid, int waves, int a_stride, int red_off, size_t smem, hipStream_t s, int rt) {
-  constexpr auto kern = gemv_l13_kernel<PRO, EPI, CPW, MR, W8>;
-  ua2_allow_big_lds<kern>();
-  hipLaunchKernelGGL(kern, grid, dim3(waves * 64), smem, s, a, a_stride, red_off, rt, w8);
-  ua2_count_launch(UA2_CNT_GEMV);       // bf16 weights through the decode kernel: a "gemv" launch as well (the counter's readers count launches of the frame)
-  ua2_count_launch(UA2_CNT_GEMV_L13);
-}
-
-// Which fp8 form serves a geometry: 1 = every wave's range is whole rounds of cpw chunks; 2 = ranges of up to 4 chunks in one
-// single-burst round of 4 (the small-K fall-back geometries); 0 = none (the launch stays on the bf16 twin).
-int w8_form(int nchunks, const Geometry& geo) {
-  if (nchunks % 2) return 0;
+// Which form of the image serves a geometry: 1 = every wave's range is whole rounds of cpw chunks (it then starts on a group: cpw >= 4);
+// 2 = ranges of up to 4 chunks in one single-burst round of 4 (the small-K fall-back geometries), a load (set) per chunk; 0 = none (an
+// offered image then stays unused: the launch reads a.w0 / a.w1).
+int image_form(Ua2WForm form, int nchunks, const Geometry& geo) {
+  if (nchunks % image_group(form)) return 0;
   if (nchunks % geo.waves == 0 && (nchunks / geo.waves) % geo.cpw == 0) return 1;
   const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
   if (!mr && geo.cpw == 4 && ua2_ceil_div(nchunks, geo.waves) <= 4) return 2;
   return 0;
 }
 
-// ... and which 13-bit form: 1 = whole rounds (a wave's range then starts on a group of 4 chunks: cpw >= 4), 2 = the small-K fall-back
-// geometries, a load set per chunk
-int l13_form(int nchunks, const Geometry& geo) {
-  if (nchunks % 4) return 0;
-  if (nchunks % geo.waves == 0 && (nchunks / geo.waves) % geo.cpw == 0) return 1;
-  const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
-  if (!mr && geo.cpw == 4 && ua2_ceil_div(nchunks, geo.waves) <= 4) return 2;
-  return 0;
-}
-
-template <int DT, int PRO, int EPI>
-int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr) {
-  constexpr int KC = Elem<DT>::KC, BYTES = Elem<DT>::BYTES;
-  constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
-  const int nchunks = ua2_ceil_div(a.K, KC);
-  const int ntiles = ua2_ceil_div(a.N, 16);
-  const int gx = ntiles;
-  // rows per workgroup and launch geometry depend on (N, K, dtype) only — never on M — so that a row
-  // sees the same instruction stream and summation order whatever the batch around it
-  const Geometry geo = pick_geometry(nchunks, gx, NT);
-  // +16 B per row: breaks the power-of-two row stride (LDS bank conflicts across rows)
-  const int a_stride = nchunks * KC + 16 / BYTES;
-  const int rt = rows_per_tile(a.dtype, a.K);
-  const int mtiles = ua2_ceil_div(a.M, rt);
-  // LDS is sized for the rows actually present (occupancy: two single-row workgroups share a CU);
-  // the size changes nothing a row computes
-  const int red_off = (int)(((size_t)(a.M < rt ? a.M : rt) * a_stride * BYTES + 255) & ~(size_t)255);
-  const size_t smem = (size_t)red_off + (size_t)(kMaxWaves * NT * 256 + 2 * kMaxWaves * 16 + 32) * sizeof(float);
-  const dim3 grid(gx, mtiles);
-  const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
-  if constexpr (DT == UA2_BF16 && (EPI == UA2_EPI_QKV_ROPE || EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_STORE || EPI == UA2_EPI_RESIDUAL) &&
-                !(PRO == UA2_PRO_CAST && (EPI == UA2_EPI_SWIGLU || EPI == UA2_EPI_QKV_ROPE))) {
-    if (w8 && w8->l13) {
-      const int form = l13_form(nchunks, geo);
-      if (form == 2) {
-        launch_one_l13<PRO, EPI, 4, false, 4>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else if (form == 1 && mr) {
-        if (geo.cpw == 4) launch_one_l13<PRO, EPI, 4, true, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one_l13<PRO, EPI, 8, true, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else if (form == 1) {
-        if (geo.cpw == 4) launch_one_l13<PRO, EPI, 4, false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else if (geo.cpw == 8 || NT == 2) launch_one_l13<PRO, EPI, 8, false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one_l13<PRO, EPI, (NT == 1 ? 16 : 8), false, 3>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else {
-        return 1;
-      }
-      UA2_LAUNCH_CHECK();
-      return 0;
-    }
-    if (w8) {     // the same grid, waves, LDS carve and chunk ranges: only the weight stream differs
-      const int form = w8_form(nchunks, geo);
-      if (form == 2) {
-        launch_one_w8<PRO, EPI, 4, false, 2>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else if (form == 1 && mr) {
-        if (geo.cpw == 4) launch_one_w8<PRO, EPI, 4, true, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one_w8<PRO, EPI, 8, true, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else if (form == 1) {
-        if (geo.cpw == 4) launch_one_w8<PRO, EPI, 4, false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else if (geo.cpw == 8 || NT == 2) launch_one_w8<PRO, EPI, 8, false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one_w8<PRO, EPI, (NT == 1 ? 16 : 8), false, 1>(a, *w8, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else {
-        return 1;
-      }
-      UA2_LAUNCH_CHECK();
-      return 0;
-    }
-  } else {
-    if (w8) return 1;
-  }
-  if constexpr (PRO == UA2_PRO_LOCAL_ATTN && EPI == UA2_EPI_RESIDUAL) {
-    if (a.fold.part_max) {     // ua2_argmax_fold: the geometries of attention-wide K (rounds of 4 or 8 chunks); fp8 twins are refused above
-      if (a.M != 1 || geo.cpw > 8) return 1;
-      if (mr) {
-        if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, true, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one<DT, PRO, EPI, 8, true, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      } else {
-        if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, false, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one<DT, PRO, EPI, 8, false, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-      }
-      UA2_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (mr) {
-    if (geo.cpw == 4) launch_one<DT, PRO, EPI, 4, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-    else launch_one<DT, PRO, EPI, 8, true>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-  } else {
-    switch (geo.cpw) {
-      case 4: launch_one<DT, PRO, EPI, 4, false>(a, grid, geo.waves, a_stride, red_off, smem, s, rt); break;
-      case 8: launch_one<DT, PRO, EPI, 8, false>(a, grid, geo.waves, a_stride, red_off, smem, s, rt); break;
-      default:
-        if constexpr (NT == 1) launch_one<DT, PRO, EPI, 16, false>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-        else launch_one<DT, PRO, EPI, 8, false>(a, grid, geo.waves, a_stride, red_off, smem, s, rt);
-    }
-  }
-  UA2_LAUNCH_CHECK();
-  return 0;
-}
-
-// the (prologue, epilogue) pairs of the bf16 decode frame: the ones with an fp8-weight instantiation
-bool w8_pair(int pro, int epi) {
+// the (prologue, epilogue) pairs of the bf16 decode frame: the ones with image instantiations
+constexpr bool w8_pair(int pro, int epi) {
   switch (pro) {
     case UA2_PRO_NORM: case UA2_PRO_SCALED: return epi == UA2_EPI_QKV_ROPE || epi == UA2_EPI_SWIGLU || epi == UA2_EPI_STORE;
     case UA2_PRO_CAST: return epi == UA2_EPI_RESIDUAL || epi == UA2_EPI_STORE;
@@ -859,44 +755,100 @@ bool w8_pair(int pro, int epi) {
   }
 }
 
-template <int DT>
-int launch_dt(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8 = nullptr) {
-  if (w8) {       // fp8 weights: only the pairs above (each instantiation below is compiled for exactly those)
-    if (DT != UA2_BF16 || !w8_pair(a.prologue, a.epilogue) || a.fold.part_max) return 1;
-    if (a.prologue == UA2_PRO_NORM) {
-      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s, w8);
-      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s, w8);
-      return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_STORE>(a, s, w8);
-    } else if (a.prologue == UA2_PRO_CAST) {
-      if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_RESIDUAL>(a, s, w8);
-      return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_STORE>(a, s, w8);
-    } else if (a.prologue == UA2_PRO_LOCAL_ATTN) {
-      return launch_cpw<DT, UA2_PRO_LOCAL_ATTN, UA2_EPI_RESIDUAL>(a, s, w8);
-    } else if constexpr (DT == UA2_BF16) {
-      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_QKV_ROPE>(a, s, w8);
-      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_SWIGLU>(a, s, w8);
-      return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_STORE>(a, s, w8);
-    }
-    return 1;
+// The one place a geometry becomes the compile-time (CPW, multi-round) pair of an instantiation: f(integral_constant<int, CPW>,
+// bool_constant<MR>).  Rounds of 16 chunks exist as a single burst of one matrix (NT == 1); every other geometry above 4 runs rounds of 8.
+template <int NT, class F>
+void with_rounds(const Geometry& geo, bool mr, F&& f) {
+  using std::integral_constant;
+  if (geo.cpw == 4) return mr ? f(integral_constant<int, 4>{}, std::true_type{}) : f(integral_constant<int, 4>{}, std::false_type{});
+  if (mr) return f(integral_constant<int, 8>{}, std::true_type{});
+  if constexpr (NT == 1)
+    if (geo.cpw != 8) return f(integral_constant<int, 16>{}, std::false_type{});
+  return f(integral_constant<int, 8>{}, std::false_type{});
+}
+
+template <int DT, int PRO, int EPI>
+int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nullptr) {
+  constexpr int KC = Elem<DT>::KC, BYTES = Elem<DT>::BYTES;
+  constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
+  const int nchunks = ua2_ceil_div(a.K, KC);
+  const int ntiles = ua2_ceil_div(a.N, 16);
+  const int gx = ntiles;
+  // rows per workgroup and launch geometry depend on (N, K, dtype) only — never on M — so that a row
+  // sees the same instruction stream and summation order whatever the batch around it
+  const Geometry geo = pick_geometry(nchunks, gx, NT);
+  Launch l;
+  l.waves = geo.waves; l.s = s;
+  // +16 B per row: breaks the power-of-two row stride (LDS bank conflicts across rows)
+  l.a_stride = nchunks * KC + 16 / BYTES;
+  l.rt = rows_per_tile(a.dtype, a.K);
+  // LDS is sized for the rows actually present (occupancy: two single-row workgroups share a CU);
+  // the size changes nothing a row computes
+  l.red_off = (int)(((size_t)(a.M < l.rt ? a.M : l.rt) * l.a_stride * BYTES + 255) & ~(size_t)255);
+  l.smem = (size_t)l.red_off + (size_t)(kMaxWaves * NT * 256 + 2 * kMaxWaves * 16 + 32) * sizeof(float);
+  l.grid = dim3(gx, ua2_ceil_div(a.M, l.rt));
+  const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
+  // What is instantiated beyond the plain kernels: image forms for the bf16 pairs of w8_pair, the arg-max fold for the O-projection of the
+  // local attention in rounds of 4 or 8 chunks (attention-wide K).  A new weight form adds its rows here.
+  constexpr bool IMAGE = DT == UA2_BF16 && w8_pair(PRO, EPI), FOLD = PRO == UA2_PRO_LOCAL_ATTN && EPI == UA2_EPI_RESIDUAL;
+  int w8 = 0;     // gemv_body's W8: the same grid, waves, LDS carve and chunk ranges whatever it is, only the weight stream differs
+  if (w) {
+    const int form = IMAGE ? image_form(w->form, nchunks, geo) : 0;
+    if (!form) return 1;
+    w8 = (w->form == UA2_W_L13 ? 2 : 0) + form;
   }
+  const bool fold = FOLD && a.fold.part_max;     // ua2_argmax_fold (never with an image: launch_dt)
+  if (fold && (a.M != 1 || geo.cpw > 8)) return 1;
+  int rc = 1;
+  with_rounds<NT>(geo, mr, [&](auto cpw, auto multi) {
+    constexpr int CPW = decltype(cpw)::value;
+    constexpr bool MR = decltype(multi)::value;
+    rc = 0;
+    if constexpr (IMAGE) {
+      constexpr bool FALLBACK = CPW == 4 && !MR;     // the only geometry of forms 2 / 4 (image_form)
+      switch (w8) {
+        case 1: return launch_one<gemv_w8_kernel<PRO, EPI, CPW, MR, 1>>({UA2_CNT_GEMV_W8}, a, l, w->img);
+        // bf16 weights through the decode kernel: a "gemv" launch as well (the counter's readers count launches of the frame)
+        case 3: return launch_one<gemv_l13_kernel<PRO, EPI, CPW, MR, 3>>({UA2_CNT_GEMV, UA2_CNT_GEMV_L13}, a, l, w->img);
+        case 2:
+          if constexpr (FALLBACK) return launch_one<gemv_w8_kernel<PRO, EPI, 4, false, 2>>({UA2_CNT_GEMV_W8}, a, l, w->img);
+          rc = 1; return;
+        case 4:
+          if constexpr (FALLBACK) return launch_one<gemv_l13_kernel<PRO, EPI, 4, false, 4>>({UA2_CNT_GEMV, UA2_CNT_GEMV_L13}, a, l, w->img);
+          rc = 1; return;
+      }
+    }
+    if constexpr (FOLD && CPW <= 8)
+      if (fold) return launch_one<gemv_kernel<DT, PRO, EPI, CPW, MR, true>>({UA2_CNT_GEMV}, a, l);
+    launch_one<gemv_kernel<DT, PRO, EPI, CPW, MR>>({UA2_CNT_GEMV}, a, l);
+  });
+  if (rc) return rc;
+  UA2_LAUNCH_CHECK();
+  return 0;
+}
+
+template <int DT>
+int launch_dt(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nullptr) {
+  // a weight image: a bf16 launch of the pairs of w8_pair without an arg-max fold (launch_cpw instantiates the image kernels for exactly those)
+  if (w && (DT != UA2_BF16 || !w8_pair(a.prologue, a.epilogue) || a.fold.part_max)) return 1;
   if (a.prologue == UA2_PRO_NORM) {
-    if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s);
-    if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s);
-    if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_STORE>(a, s);
-    if (a.epilogue == UA2_EPI_GELU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_GELU>(a, s);
+    if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_QKV_ROPE>(a, s, w);
+    if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s, w);
+    if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_STORE>(a, s, w);
+    if (a.epilogue == UA2_EPI_GELU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_GELU>(a, s, w);
   } else if (a.prologue == UA2_PRO_CAST) {
-    if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_RESIDUAL>(a, s);
-    if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_STORE>(a, s);
-    if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_SWIGLU>(a, s);     // codec GLU (no norm in front)
-    if (a.epilogue == UA2_EPI_GELU) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_GELU>(a, s);
-    if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_QKV_ROPE>(a, s);
+    if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_RESIDUAL>(a, s, w);
+    if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_STORE>(a, s, w);
+    if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_SWIGLU>(a, s, w);     // codec GLU (no norm in front)
+    if (a.epilogue == UA2_EPI_GELU) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_GELU>(a, s, w);
+    if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_QKV_ROPE>(a, s, w);
   } else if (a.prologue == UA2_PRO_LOCAL_ATTN) {
-    if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_LOCAL_ATTN, UA2_EPI_RESIDUAL>(a, s);
+    if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_LOCAL_ATTN, UA2_EPI_RESIDUAL>(a, s, w);
   } else if (a.prologue == UA2_PRO_SCALED) {
     if constexpr (DT == UA2_BF16) {
-      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_QKV_ROPE>(a, s);
-      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_SWIGLU>(a, s);
-      if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_STORE>(a, s);
+      if (a.epilogue == UA2_EPI_QKV_ROPE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_QKV_ROPE>(a, s, w);
+      if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_SWIGLU>(a, s, w);
+      if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_SCALED, UA2_EPI_STORE>(a, s, w);
     }
   }
   return 1;  // combination not specialised here: the caller falls back to the general kernel
@@ -978,29 +930,24 @@ extern "C" int ua2_debug_gemv_geometry(int dtype, int32_t N, int32_t K, int32_t 
   return 0;
 }
 
+// does the decode kernel have a form on an image of this kind for the launch (ua2_common.h: ua2_gemv_w8_ok / ua2_gemv_l13_ok)?
+static bool image_ok(Ua2WForm form, const ua2_linear_args& a) {
+  if (a.dtype != UA2_BF16 || a.K % (32 * image_group(form)) || a.N <= 0 || !w8_pair(a.prologue, a.epilogue) || rows_per_tile(a.dtype, a.K) < 1) return false;
+  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
+  return image_form(form, a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
+}
+bool ua2_gemv_w8_ok(const ua2_linear_args& a) { return image_ok(UA2_W_FP8, a); }
+bool ua2_gemv_l13_ok(const ua2_linear_args& a) { return !a.fold.part_max && image_ok(UA2_W_L13, a); }
+
 // Returns 0 if launched, 1 if this problem is outside the decode regime (caller uses the general
 // kernel), negative on error.
-bool ua2_gemv_w8_ok(const ua2_linear_args& a) {
-  if (a.dtype != UA2_BF16 || a.K % 64 || a.N <= 0 || !w8_pair(a.prologue, a.epilogue) || rows_per_tile(a.dtype, a.K) < 1) return false;
-  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
-  return w8_form(a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
-}
-
-bool ua2_gemv_l13_ok(const ua2_linear_args& a) {
-  if (a.dtype != UA2_BF16 || a.K % 128 || a.N <= 0 || !w8_pair(a.prologue, a.epilogue) || a.fold.part_max || rows_per_tile(a.dtype, a.K) < 1) return false;
-  const int nt = a.epilogue == UA2_EPI_SWIGLU ? 2 : 1;
-  return l13_form(a.K / 32, pick_geometry(a.K / 32, ua2_ceil_div(a.N, 16), nt)) != 0;
-}
-
-int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
+int ua2_gemv_try_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w) {
   if (rows_per_tile(a.dtype, a.K) < 1) return 1;   // a single row does not fit the LDS budget
-  if (w8 && w8->l13) {                             // images of a.w0 / a.w1: where the decode kernel has no form for them the launch reads the weights themselves
-    if (w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && ua2_gemv_l13_ok(a)) return launch_dt<UA2_BF16>(a, s, w8);
-    if (w8->strict) return 1;
-    w8 = nullptr;
-  }
-  if (w8 && w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && ua2_gemv_w8_ok(a)) return launch_dt<UA2_BF16>(a, s, w8);
-  if (w8 && w8->strict) return 1;                  // asked for by name: never the bf16 twin in its place
+  if (w) {
+    const bool ok = w->form == UA2_W_L13 ? ua2_gemv_l13_ok(a) : ua2_gemv_w8_ok(a);
+    if (w->complete(a.epilogue) && ok) return launch_dt<UA2_BF16>(a, s, w);
+    if (w->by_name()) return 1;                    // asked for by name: never a.w0 / a.w1 in its place
+  }                                                // an offered image the decode kernel has no form for: the launch reads a.w0 / a.w1 (the same bits)
   if (a.dtype == UA2_BF16) return launch_dt<UA2_BF16>(a, s);
   if (a.dtype == UA2_F32) return launch_dt<UA2_F32>(a, s);
   return 1;

@@ -172,24 +172,29 @@ __global__ __launch_bounds__(256) void l13_pack_kernel(const u32x4* __restrict__
 
 static int g_force_general = 0;
 
-int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) {
-  const bool w8_many = w8 && w8->strict && w8->many;
-  const bool l13 = w8 && w8->l13;                                     // images of a.w0 / a.w1 for the decode kernel alone
-  const bool w8_strict = w8 && w8->strict && !w8->many && !l13;
-  const Ua2W8* const w8_gemm = l13 ? nullptr : w8;                    // what the many-row kernels may stream
-  if (l13 && w8->strict)
-    UA2_CHECK(a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_l13_ok(a),
-              "ua2_linear_l13: not a launch the decode kernel serves on a 13-bit image (UA2_BF16, K %% 128 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed, no argmax fold)",
-              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
-  if (w8_many)
-    UA2_CHECK(ua2_gemm_w8_serves(a, *w8),
-              "ua2_linear_w8_many: not a launch the fp8 weights-stationary kernel serves (UA2_BF16, K %% 64 == 0, %d to %d rows [UA2_SKINNY_W8_MAX_ROWS], "
-              "a released Linear geometry with a STORE / RESIDUAL / SWIGLU / QKV_ROPE epilogue, workspace or x_packed, a built variant)",
-              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) + 1 : 0, ua2_skinny_w8_max_rows());
-  if (w8_strict)
-    UA2_CHECK(a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_w8_ok(a),
-              "ua2_linear_w8: not a launch the fp8 decode kernel serves (UA2_BF16, K %% 64 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed)",
-              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
+int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w8) {
+  const Ua2WDemand demand = w8 ? w8->demand : UA2_W_OFFERED;
+  const bool w8_many = demand == UA2_W_STATIONARY;
+  const auto decode_rows = [&] { return a.dtype == UA2_BF16 && !a.x_packed && a.K > 0 && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K); };
+  switch (demand) {      // a kernel asked for by name: the launch is one it serves, or an error
+    case UA2_W_OFFERED: break;
+    case UA2_W_STATIONARY:
+      UA2_CHECK(ua2_gemm_w8_serves(a, *w8),
+                "ua2_linear_w8_many: not a launch the fp8 weights-stationary kernel serves (UA2_BF16, K %% 64 == 0, %d to %d rows [UA2_SKINNY_W8_MAX_ROWS], "
+                "a released Linear geometry with a STORE / RESIDUAL / SWIGLU / QKV_ROPE epilogue, workspace or x_packed, a built variant)",
+                a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) + 1 : 0, ua2_skinny_w8_max_rows());
+      break;
+    case UA2_W_DECODE:
+      if (w8->form == UA2_W_L13)
+        UA2_CHECK(decode_rows() && ua2_gemv_l13_ok(a),
+                  "ua2_linear_l13: not a launch the decode kernel serves on a 13-bit image (UA2_BF16, K %% 128 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed, no argmax fold)",
+                  a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
+      else
+        UA2_CHECK(decode_rows() && ua2_gemv_w8_ok(a),
+                  "ua2_linear_w8: not a launch the fp8 decode kernel serves (UA2_BF16, K %% 64 == 0, up to %d rows, a prologue / epilogue pair of the decode frame, no x_packed)",
+                  a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
+      break;
+  }
   UA2_CHECK(a.M > 0 && a.N > 0 && a.K > 0, "ua2_linear: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   UA2_CHECK(a.w0 != nullptr, "ua2_linear: w0 is NULL");
   const int epl = a.dtype == UA2_BF16 ? 8 : 4;
@@ -234,7 +239,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
   if (a.x_packed) {   // operand handed over in fragment order by its producer: only the many-row kernels read it
     UA2_CHECK((a.prologue == UA2_PRO_CAST || a.prologue == UA2_PRO_SCALED) && g_force_general != 2,
               "ua2_linear: x_packed needs PRO_CAST / PRO_SCALED and the many-row kernels");
-    const int rc = ua2_gemm_try_launch(a, s, w8_many ? 0 : (g_force_general >= 4 ? g_force_general : 3), w8_gemm);
+    const int rc = ua2_gemm_try_launch(a, s, w8_many ? 0 : (g_force_general >= 4 ? g_force_general : 3), w8);
     UA2_CHECK(rc <= 0, "%s: x_packed launch not applicable", w8_many ? "ua2_linear_w8_many" : "ua2_linear");
     return rc;
   }
@@ -282,8 +287,8 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2W8* w8) 
     UA2_CHECK(rc <= 0, "ua2_linear_w8_many: the fp8 weights-stationary kernel did not take the launch");
     return rc;
   }
-  if (g_force_general != 2 && !w8_strict && !(l13 && w8->strict)) {
-    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8_gemm);  // many rows: packed operand, 128-row tiles
+  if (g_force_general != 2 && demand != UA2_W_DECODE) {
+    const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8);  // many rows: packed operand, 128-row tiles
     if (rc <= 0) return rc;
   }
   const int rc = ua2_gemv_try_launch(a, s, w8);  // decode regime: LDS-staged activations, all loads up front
@@ -303,23 +308,54 @@ extern "C" int ua2_linear(const ua2_linear_args* a, void* stream) {
   return ua2_linear_launch(*a, (hipStream_t)stream);
 }
 
+// The event-timed loop of the *_chain_timed exports: launch(0) .. launch(n - 1) back to back, iters times.  The events are destroyed on
+// every path (a refused launch, a failed HIP call).
+template <class LaunchFn>
+static int chain_timed(int32_t n, int32_t iters, hipStream_t s, float* ms_out, LaunchFn&& launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const auto run = [&]() -> int {
+    UA2_HIP(hipEventCreate(&e0));
+    UA2_HIP(hipEventCreate(&e1));
+    UA2_HIP(hipEventRecord(e0, s));
+    for (int it = 0; it < iters; ++it)
+      for (int i = 0; i < n; ++i)
+        if (int rc = launch(i)) return rc;
+    UA2_HIP(hipEventRecord(e1, s));
+    UA2_HIP(hipEventSynchronize(e1));
+    UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
+    return 0;
+  };
+  const int rc = run();
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  return rc;
+}
+
 extern "C" int ua2_linear_chain_timed(const ua2_linear_args* args, int32_t n, int32_t iters, void* stream,
                                       float* ms_out) {
   UA2_CHECK(args && n > 0 && iters > 0 && ms_out, "ua2_linear_chain_timed: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipEvent_t e0, e1;
-  UA2_HIP(hipEventCreate(&e0));
-  UA2_HIP(hipEventCreate(&e1));
-  UA2_HIP(hipEventRecord(e0, s));
-  for (int it = 0; it < iters; ++it)
-    for (int i = 0; i < n; ++i)
-      if (int rc = ua2_linear_launch(args[i], s)) return rc;
-  UA2_HIP(hipEventRecord(e1, s));
-  UA2_HIP(hipEventSynchronize(e1));
-  UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return 0;
+  return chain_timed(n, iters, s, ms_out, [&](int i) { return ua2_linear_launch(args[i], s); });
+}
+
+// A launch on weight images asked for by name (`name`: the entry point; `what`: what its messages call an image).  Ref = ua2_w8_ref /
+// ua2_l13_ref: the image and its side array.
+template <class Ref>
+static int linear_by_name(const char* name, const char* what, Ua2WForm form, Ua2WDemand demand, const ua2_linear_args* a, const Ref* w0,
+                          const Ref* w1, hipStream_t s) {
+  Ua2Weights w;
+  w.form = form; w.demand = demand;
+  if (w0) { const auto& [q, e] = *w0; w.img.q0 = q; w.img.e0 = e; }
+  if (w1) { const auto& [q, e] = *w1; w.img.q1 = q; w.img.e1 = e; }
+  UA2_CHECK(a != nullptr && w.complete(UA2_EPI_STORE), "%s: NULL args or %s of w0", name, what);
+  UA2_CHECK(w.complete(a->epilogue), "%s: SWIGLU needs the %s of w1", name, what);
+  return ua2_linear_launch(*a, s, &w);
+}
+static int linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, hipStream_t s) {
+  return linear_by_name("ua2_linear_w8_many", "fp8 twin", UA2_W_FP8, UA2_W_STATIONARY, a, w0, w1, s);
+}
+static int linear_l13(const ua2_linear_args* a, const ua2_l13_ref* w0, const ua2_l13_ref* w1, hipStream_t s) {
+  return linear_by_name("ua2_linear_l13", "image", UA2_W_L13, UA2_W_DECODE, a, w0, w1, s);
 }
 
 extern "C" size_t ua2_packed_elems(int dtype, int64_t N, int64_t K) {
@@ -380,13 +416,7 @@ extern "C" int ua2_pack_linear_w8(const void* src, int src_dtype, int transposed
 }
 
 extern "C" int ua2_linear_w8(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream) {
-  UA2_CHECK(a != nullptr && w0 != nullptr && w0->q && w0->exp, "ua2_linear_w8: NULL args or fp8 twin of w0");
-  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->q && w1->exp), "ua2_linear_w8: SWIGLU needs the fp8 twin of w1");
-  Ua2W8 w8;
-  w8.q0 = w0->q; w8.e0 = w0->exp;
-  if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
-  w8.strict = true;
-  return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
+  return linear_by_name("ua2_linear_w8", "fp8 twin", UA2_W_FP8, UA2_W_DECODE, a, w0, w1, (hipStream_t)stream);
 }
 
 extern "C" size_t ua2_packed_bytes_l13(int64_t N, int64_t K) {
@@ -408,46 +438,14 @@ extern "C" int ua2_pack_linear_l13(const void* packed_bf16, int64_t N, int64_t K
 }
 
 extern "C" int ua2_linear_l13(const ua2_linear_args* a, const ua2_l13_ref* w0, const ua2_l13_ref* w1, void* stream) {
-  UA2_CHECK(a != nullptr && w0 != nullptr && w0->image && w0->base, "ua2_linear_l13: NULL args or image of w0");
-  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->image && w1->base), "ua2_linear_l13: SWIGLU needs the image of w1");
-  Ua2W8 w8;
-  w8.q0 = w0->image; w8.e0 = reinterpret_cast<const int8_t*>(w0->base);
-  if (w1) { w8.q1 = w1->image; w8.e1 = reinterpret_cast<const int8_t*>(w1->base); }
-  w8.strict = w8.l13 = true;
-  return ua2_linear_launch(*a, (hipStream_t)stream, &w8);
+  return linear_l13(a, w0, w1, (hipStream_t)stream);
 }
 
 extern "C" int ua2_linear_l13_chain_timed(const ua2_linear_args* args, const ua2_l13_ref* w0, const ua2_l13_ref* w1, int32_t n, int32_t iters,
                                           void* stream, float* ms_out) {
   UA2_CHECK(args && w0 && n > 0 && iters > 0 && ms_out, "ua2_linear_l13_chain_timed: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipEvent_t e0, e1;
-  UA2_HIP(hipEventCreate(&e0));
-  UA2_HIP(hipEventCreate(&e1));
-  UA2_HIP(hipEventRecord(e0, s));
-  for (int it = 0; it < iters; ++it)
-    for (int i = 0; i < n; ++i)
-      if (int rc = ua2_linear_l13(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s)) {
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        return rc;
-      }
-  UA2_HIP(hipEventRecord(e1, s));
-  UA2_HIP(hipEventSynchronize(e1));
-  UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return 0;
-}
-
-static int linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, hipStream_t s) {
-  UA2_CHECK(a != nullptr && w0 != nullptr && w0->q && w0->exp, "ua2_linear_w8_many: NULL args or fp8 twin of w0");
-  UA2_CHECK(a->epilogue != UA2_EPI_SWIGLU || (w1 && w1->q && w1->exp), "ua2_linear_w8_many: SWIGLU needs the fp8 twin of w1");
-  Ua2W8 w8;
-  w8.q0 = w0->q; w8.e0 = w0->exp;
-  if (w1) { w8.q1 = w1->q; w8.e1 = w1->exp; }
-  w8.strict = w8.many = true;
-  return ua2_linear_launch(*a, s, &w8);
+  return chain_timed(n, iters, s, ms_out, [&](int i) { return linear_l13(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s); });
 }
 
 extern "C" int ua2_linear_w8_many(const ua2_linear_args* a, const ua2_w8_ref* w0, const ua2_w8_ref* w1, void* stream) {
@@ -458,17 +456,5 @@ extern "C" int ua2_linear_w8_many_chain_timed(const ua2_linear_args* args, const
                                               void* stream, float* ms_out) {
   UA2_CHECK(args && w0 && n > 0 && iters > 0 && ms_out, "ua2_linear_w8_many_chain_timed: bad arguments");
   hipStream_t s = (hipStream_t)stream;
-  hipEvent_t e0, e1;
-  UA2_HIP(hipEventCreate(&e0));
-  UA2_HIP(hipEventCreate(&e1));
-  UA2_HIP(hipEventRecord(e0, s));
-  for (int it = 0; it < iters; ++it)
-    for (int i = 0; i < n; ++i)
-      if (int rc = linear_w8_many(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s)) return rc;
-  UA2_HIP(hipEventRecord(e1, s));
-  UA2_HIP(hipEventSynchronize(e1));
-  UA2_HIP(hipEventElapsedTime(ms_out, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return 0;
+  return chain_timed(n, iters, s, ms_out, [&](int i) { return linear_w8_many(&args[i], &w0[i], w1 ? &w1[i] : nullptr, s); });
 }

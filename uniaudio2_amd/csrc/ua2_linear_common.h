@@ -14,13 +14,13 @@ int ua2_gemv_rows_per_tile(int dtype, int K);
 // large-M path; returns 1 when not applicable (no workspace, ATTN prologue, few rows)
 // force: 0 = only when M spans more than one row tile; 3 = whenever possible; 4 / 5 = likewise, skinny / tiled form
 // w8: fp8 twins of the launch's weights, handed on to the weights-stationary kernel (the other many-row kernels read a.w0 / a.w1 = W')
-int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2W8* w8 = nullptr);
+int ua2_gemm_try_launch(const ua2_linear_args& a, hipStream_t s, int force, const Ua2Weights* w8 = nullptr);
 // batched-decode form (ua2_skinny.hip): 0 = launched, 1 = shape outside its table (the older skinny kernel serves it)
 // w8: streams the fp8 image where its fp8 form takes the launch; dry: launches nothing, 0 = the fp8 form would take it
-int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2W8* w8 = nullptr, bool dry = false);
+int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2Weights* w8 = nullptr, bool dry = false);
 int ua2_skinny_w8_max_rows();                      // UA2_SKINNY_W8_MAX_ROWS (default 64; 0 = never)
 // would ua2_linear_launch hand this launch to skinny2_kernel<W8 = true, ...>?  (the whole chain: many-row path, weights-stationary kernel, an fp8 form)
-bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2W8& w8);
+bool ua2_gemm_w8_serves(const ua2_linear_args& a, const Ua2Weights& w8);
 // order-free form (ua2_gemm2.hip: 256-row tiles, one chain over K): 0 = launched, 1 = launch outside its forms; operand already packed
 int ua2_gemm2_try_launch(const ua2_linear_args& a, hipStream_t s);
 

@@ -53,7 +53,7 @@ constexpr int kRsrcFlags = 0x00020000;   // raw buffer, dword data format (gfx9 
 // form on W' and of the decode kernel on the image.
 // (W8 leads the parameter list: the tail stays SC, WD, RPW, which is how the compiled instantiations are told apart by name.)
 template <bool W8, int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0, int RPW = 1>
-__global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linear_args a, const u32x4* __restrict__ apack, const int passes, const Ua2W8 w8) {
+__global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linear_args a, const u32x4* __restrict__ apack, const int passes, const Ua2WImage w8) {
   constexpr int DT = UA2_BF16;
   constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;   // weight matrices
   constexpr int NS = NM * CT;                           // weight streams per wave: stream s = matrix s / CT, column tile s % CT
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(NWV / RPW * 64) void skinny2_kernel(const ua2_linea
   if constexpr (W8) {
 #pragma unroll
     for (int s = 0; s < NS; ++s)
-      wexp[s] = ((s / CT) ? w8.e1 : w8.e0)[min((int)blockIdx.x * CT + s % CT, ntiles - 1) * 16 + (tid & 15)];
+      wexp[s] = static_cast<const int8_t*>((s / CT) ? w8.e1 : w8.e0)[min((int)blockIdx.x * CT + s % CT, ntiles - 1) * 16 + (tid & 15)];
   }
 
   // Issue order: a wave's loads retire in order, so the first operand chunks (L2 hits, needed first) go out BEFORE the weight
@@ -444,13 +444,13 @@ int launch_one(const ua2_linear_args& a, int passes, hipStream_t s) {
   ua2_allow_big_lds<kern>();
   const int mtiles = ua2_ceil_div(a.M, 16), ntiles = ua2_ceil_div(a.N, 16);
   const dim3 grid(ua2_ceil_div(ntiles, CT), ua2_ceil_div(mtiles, MT * passes));
-  hipLaunchKernelGGL(kern, grid, dim3(NWV / RPW * 64), smem, s, a, reinterpret_cast<const u32x4*>(a.x_packed ? a.x_packed : a.workspace), passes, Ua2W8{});
+  hipLaunchKernelGGL(kern, grid, dim3(NWV / RPW * 64), smem, s, a, reinterpret_cast<const u32x4*>(a.x_packed ? a.x_packed : a.workspace), passes, Ua2WImage{});
   ua2_count_launch(UA2_CNT_SKINNY2);
   return 0;
 }
 
 template <int EPI, int CT, int MT, int CH, int NWV, int LA, bool SC, int WD = 0>
-int launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, int passes, hipStream_t s, bool dry) {
+int launch_one_w8(const ua2_linear_args& a, const Ua2WImage& w8, int passes, hipStream_t s, bool dry) {
   constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
   constexpr auto kern = skinny2_kernel<true, EPI, CT, MT, CH, NWV, LA, SC, WD>;
   constexpr size_t red_bytes = (size_t)NWV * NM * CT * MT * 1024;
@@ -469,7 +469,7 @@ int launch_one_w8(const ua2_linear_args& a, const Ua2W8& w8, int passes, hipStre
 // bf16 launch gets), each with and without the scaled consumer, and nothing of the experiment table beyond them.  An odd ring has no fp8
 // form (two chunks per load).
 template <int EPI, int CH, int NWV>
-int launch_variant_w8(const ua2_linear_args& a, const Ua2W8& w8, const Variant& v, hipStream_t s, bool dry) {
+int launch_variant_w8(const ua2_linear_args& a, const Ua2WImage& w8, const Variant& v, hipStream_t s, bool dry) {
   constexpr int NM = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
   if (v.rpw != 1) return 1;
 #define UA2_SK8(CT_, MT_, LA_, WD_)                                                                                              \
@@ -591,9 +591,9 @@ int ua2_skinny_w8_max_rows() {
 // Returns 0 when launched, 1 when this problem is outside the kernel's table (the caller uses the older skinny kernel).
 // w8: fp8 twins of the launch's weight(s) — streamed instead of a.w0 / a.w1 when the launch is one the fp8 form takes (more rows than the
 // launchers give the decode kernel, up to ua2_skinny_w8_max_rows(), K % 64 == 0, a form of the table below); otherwise the launch reads the
-// bf16 twin as without them, except for a caller that asked for the fp8 kernel by name (w8->strict): 1, never the twin in its place.
+// bf16 twin as without them, except for a caller that asked for the fp8 kernel by name (w8->by_name()): 1, never the twin in its place.
 // dry (with w8): launch nothing, answer only whether the fp8 form would take the launch.
-int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2W8* w8, bool dry) {
+int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipStream_t s, const Ua2Weights* w8, bool dry) {
   if (a.dtype != UA2_BF16) return 1;
   if (a.K % 32) return 1;
   const int nchunks = a.K / 32;
@@ -601,8 +601,8 @@ int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipS
   // the packed operand is addressed through one buffer resource (32-bit size / offsets): past 4 GiB the loads would wrap
   // and return zeros — leave such a problem to the tiled kernel
   if ((uint64_t)ua2_ceil_div(a.M, 16) * (uint64_t)nchunks * 1024ull >= (1ull << 32)) return 1;
-  const bool strict = w8 && w8->strict;
-  const bool use_w8 = w8 && w8->q0 && w8->e0 && (a.epilogue != UA2_EPI_SWIGLU || (w8->q1 && w8->e1)) && a.K % 64 == 0 &&
+  const bool strict = w8 && w8->by_name();
+  const bool use_w8 = w8 && w8->form == UA2_W_FP8 && w8->complete(a.epilogue) && a.K % 64 == 0 &&
                       a.M > ua2_gemv_rows_preferred(a.dtype, a.K) && a.M <= ua2_skinny_w8_max_rows();
   if ((strict || dry) && !use_w8) return 1;
   if (getenv("UA2_SKINNY2") == nullptr && !strict && !dry)   // a forced variant means the sweep tool is measuring skinny2_kernel itself
@@ -628,7 +628,7 @@ int ua2_skinny2_try_launch(const ua2_linear_args& a, ua2_gemv_geometry geo, hipS
   UA2_GEO(UA2_EPI_SWIGLU, 8, 8) UA2_GEO(UA2_EPI_STORE, 8, 8)
   if (use_w8) {                                           // the same table: only the weight stream differs
 #define UA2_GEO(EPI_, CH_, NWV_) \
-    if (a.epilogue == EPI_ && ch == CH_ && geo.waves == NWV_) rc = launch_variant_w8<EPI_, CH_, NWV_>(a, *w8, v, s, dry);
+    if (a.epilogue == EPI_ && ch == CH_ && geo.waves == NWV_) rc = launch_variant_w8<EPI_, CH_, NWV_>(a, w8->img, v, s, dry);
     UA2_GEOS
 #undef UA2_GEO
     if (dry) return rc;

@@ -103,15 +103,15 @@ struct ua2_stage3 {
   ua2_beam_state beam{};
   const ua2_beam_pool* beam_pools = nullptr;
   ua2_beam_ngram beam_ng{};                       // the no-repeat-n-gram ban of the attached beam (ua2_stage3_set_beam_ngram; n == 0 = off)
+  // a weight's image and its side array (fp8: exponents; 13-bit: base bytes), keyed by the packed bf16 pointer in the two maps below
+  struct WImage { const void *q, *side; };
   // fp8 twins of the plan's weights (ua2_stage3_set_w8): packed bf16 pointer -> (fp8 image, exponents); empty = a plain bf16 / fp32 plan
-  struct W8Twin { const void* q; const int8_t* exp; };
-  std::map<const void*, W8Twin> w8;
+  std::map<const void*, WImage> w8;
   // Lossless 13-bit images (include/ua2hip.h ua2_pack_linear_l13) of the Linear weights a decode frame streams, packed when a bf16 plan is
   // created: packed bf16 pointer -> (image, base bytes), escape-free matrices only.  One allocation, owned by the handle.  The few-row
   // launches the decode kernel serves stream the image instead of the bf16 form — the same bits, 13/16 of the bytes; fp8 twins, when
   // attached, take precedence.  ua2_stage3_set_lossless / UA2_NO_LOSSLESS=1 (read at creation: no images are packed)
-  struct L13Img { const void* image; const uint8_t* base; };
-  std::map<const void*, L13Img> l13;
+  std::map<const void*, WImage> l13;
   void* l13_mem = nullptr;
   bool lossless = false;
   ua2_lossless_info l13_info{};
@@ -227,31 +227,28 @@ bool l13_pays(const ua2_linear_args& a) {
   return !(g.cpw == 16 && ua2_ceil_div(a.N, 16) < 160);
 }
 
-int lin(const ua2_stage3* h, const ua2_linear_args& a, hipStream_t s) {
-  if (h->w8.empty()) {
-    if (h->lossless && !a.x_packed && !a.fold.part_max && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_l13_ok(a) && l13_pays(a)) {
-      const auto i0 = h->l13.find(a.w0);
-      const auto i1 = a.epilogue == UA2_EPI_SWIGLU ? h->l13.find(a.w1) : i0;
-      if (i0 != h->l13.end() && i1 != h->l13.end()) {
-        Ua2W8 w;
-        w.l13 = true;
-        w.q0 = i0->second.image; w.e0 = reinterpret_cast<const int8_t*>(i0->second.base);
-        if (a.epilogue == UA2_EPI_SWIGLU) { w.q1 = i1->second.image; w.e1 = reinterpret_cast<const int8_t*>(i1->second.base); }
-        return ua2_linear_launch(a, s, &w);
-      }
-    }
-    return ua2_linear_launch(a, s);
-  }
-  const auto t0 = h->w8.find(a.w0);
-  if (t0 == h->w8.end()) return ua2_linear_launch(a, s);
-  Ua2W8 w;
-  w.q0 = t0->second.q; w.e0 = t0->second.exp;
+// The images the plan offers a launch: fp8 twins when attached (they take precedence), otherwise the 13-bit images where the decode kernel
+// serves the launch on them and they pay.  false: none, or not of every weight the launch reads.
+bool offered(const ua2_stage3* h, const ua2_linear_args& a, Ua2Weights& w) {
+  const bool fp8 = !h->w8.empty();
+  if (!fp8 && !(h->lossless && !a.x_packed && !a.fold.part_max && a.M <= ua2_gemv_rows_preferred(a.dtype, a.K) && ua2_gemv_l13_ok(a) && l13_pays(a)))
+    return false;
+  const auto& images = fp8 ? h->w8 : h->l13;
+  w.form = fp8 ? UA2_W_FP8 : UA2_W_L13;
+  const auto i0 = images.find(a.w0);
+  if (i0 == images.end()) return false;
+  w.img.q0 = i0->second.q; w.img.e0 = i0->second.side;
   if (a.epilogue == UA2_EPI_SWIGLU) {
-    const auto t1 = h->w8.find(a.w1);
-    if (t1 == h->w8.end()) return ua2_linear_launch(a, s);
-    w.q1 = t1->second.q; w.e1 = t1->second.exp;
+    const auto i1 = images.find(a.w1);
+    if (i1 == images.end()) return false;
+    w.img.q1 = i1->second.q; w.img.e1 = i1->second.side;
   }
-  return ua2_linear_launch(a, s, &w);
+  return true;
+}
+
+int lin(const ua2_stage3* h, const ua2_linear_args& a, hipStream_t s) {
+  Ua2Weights w;
+  return ua2_linear_launch(a, s, offered(h, a, w) ? &w : nullptr);
 }
 
 // local = the depth decoder: positions < kLocalCtx, short-context attention (fused into the O-projection when R == 1)
@@ -603,7 +600,7 @@ int build_l13(ua2_stage3* h) {
     info.image_bytes_per_frame += (ok ? ib + (m.N + 15) / 16 : bf) * m.per_frame;
     if (ok) {
       ++info.with_image;
-      h->l13[m.w] = ua2_stage3::L13Img{static_cast<char*>(h->l13_mem) + m.img_off, reinterpret_cast<const uint8_t*>(static_cast<char*>(h->l13_mem) + m.base_off)};
+      h->l13[m.w] = ua2_stage3::WImage{static_cast<char*>(h->l13_mem) + m.img_off, static_cast<char*>(h->l13_mem) + m.base_off};
     } else {
       ++info.without_image;
       if (have && ib) ++info.with_escapes;
@@ -828,7 +825,7 @@ extern "C" int ua2_stage3_set_order_free_rows(ua2_stage3* h, int32_t rows) {
 extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32_t n) {
   UA2_CHECK(h != nullptr && n >= 0 && (n == 0 || table), "ua2_stage3_set_w8: NULL handle / table or n < 0");
   UA2_CHECK(n == 0 || h->d.dtype == UA2_BF16, "ua2_stage3_set_w8: fp8 weights are an option of UA2_BF16 plans");
-  std::map<const void*, ua2_stage3::W8Twin> m;
+  std::map<const void*, ua2_stage3::WImage> m;
   for (int i = 0; i < n; ++i) {
     const ua2_w8_entry& e = table[i];
     UA2_CHECK(e.w && e.q && e.exp, "ua2_stage3_set_w8: entry %d has a NULL pointer", i);
@@ -838,7 +835,7 @@ extern "C" int ua2_stage3_set_w8(ua2_stage3* h, const ua2_w8_entry* table, int32
       for (int k = 0; k < 5 && !mine; ++k)
         for (const void* p : h->ptrs[gi][k]) mine = mine || p == e.w;
     UA2_CHECK(mine, "ua2_stage3_set_w8: entry %d is not a weight of this plan", i);
-    m[e.w] = ua2_stage3::W8Twin{e.q, e.exp};
+    m[e.w] = ua2_stage3::WImage{e.q, e.exp};
   }
   drop_graphs(h);                                    // recorded frames bake the kernels and the weight pointers
   h->w8.swap(m);

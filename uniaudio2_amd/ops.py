@@ -93,19 +93,26 @@ def pack_linear_w8(weight, transposed=False, rope_head_size=0):
     return q, exp, twin
 
 
+def _image_refs(Ref, images):
+    """The (r0, r1) ctypes arrays of `Ref` (W8Ref / L13Ref) that the launches on weight images take: images[i] = ((image, side array) of
+    w0, the same of w1 or None).  r1 is None when no launch has a w1."""
+    def ref(t):
+        return Ref(ptr(t[0]), ptr(t[1])) if t is not None else Ref()
+    n = len(images)
+    r0 = (Ref * n)(*[ref(t[0]) for t in images])
+    r1 = (Ref * n)(*[ref(t[1]) for t in images]) if any(t[1] is not None for t in images) else None
+    return r0, r1
+
+
 def linear_w8(args, w0, w1=None):
     """ua2_linear_w8: the launch `args` (ops.linear(..., launch=False); w0 / w1 = the bf16 twins) on the fp8 twins w0, w1 = (q, exp)."""
-    r0 = _lib.W8Ref(ptr(w0[0]), ptr(w0[1]))
-    r1 = _lib.W8Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
-    check(lib.ua2_linear_w8(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8")
+    check(lib.ua2_linear_w8(C.byref(args), *_image_refs(_lib.W8Ref, [(w0, w1)]), stream()), "ua2_linear_w8")
 
 
 def linear_w8_many(args, w0, w1=None):
     """ua2_linear_w8_many: the many-row launch `args` (6 .. UA2_SKINNY_W8_MAX_ROWS rows, a workspace or x_packed; w0 / w1 = the bf16 twins)
     on the fp8 twins w0, w1 = (q, exp) through the weights-stationary kernel; raises where that kernel does not serve the launch."""
-    r0 = _lib.W8Ref(ptr(w0[0]), ptr(w0[1]))
-    r1 = _lib.W8Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
-    check(lib.ua2_linear_w8_many(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_w8_many")
+    check(lib.ua2_linear_w8_many(C.byref(args), *_image_refs(_lib.W8Ref, [(w0, w1)]), stream()), "ua2_linear_w8_many")
 
 
 def pack_linear_l13(packed, N, K):
@@ -126,9 +133,7 @@ def pack_linear_l13(packed, N, K):
 def linear_l13(args, w0, w1=None):
     """ua2_linear_l13: the launch `args` (ops.linear(..., launch=False); w0 / w1 = the packed bf16 weights) on their 13-bit images
     w0, w1 = (image, base)."""
-    r0 = _lib.L13Ref(ptr(w0[0]), ptr(w0[1]))
-    r1 = _lib.L13Ref(ptr(w1[0]), ptr(w1[1])) if w1 is not None else None
-    check(lib.ua2_linear_l13(C.byref(args), C.byref(r0), C.byref(r1) if r1 is not None else None, stream()), "ua2_linear_l13")
+    check(lib.ua2_linear_l13(C.byref(args), *_image_refs(_lib.L13Ref, [(w0, w1)]), stream()), "ua2_linear_l13")
 
 
 def kv_geom(k_pool, v_pool, page_table, n_head, n_kv, head_size, ring_pages=0):
@@ -201,9 +206,7 @@ def linear_l13_chain_timed(args_list, images, iters):
     linear_chain_timed (same host path).  images[i] = ((image, base) of w0, (image, base) of w1 or None)."""
     n = len(args_list)
     arr = (LinearArgs * n)(*args_list)
-    r0 = (_lib.L13Ref * n)(*[_lib.L13Ref(ptr(t[0][0]), ptr(t[0][1])) for t in images])
-    has1 = any(t[1] is not None for t in images)
-    r1 = (_lib.L13Ref * n)(*[_lib.L13Ref(ptr(t[1][0]), ptr(t[1][1])) if t[1] is not None else _lib.L13Ref() for t in images]) if has1 else None
+    r0, r1 = _image_refs(_lib.L13Ref, images)
     ms = C.c_float(0.0)
     check(lib.ua2_linear_l13_chain_timed(arr, r0, r1, n, iters, stream(), C.byref(ms)), "ua2_linear_l13_chain_timed")
     return ms.value / (n * iters)
@@ -214,9 +217,7 @@ def linear_w8_many_chain_timed(args_list, twins, iters):
     linear_chain_timed (same host path).  twins[i] = ((q, exp) of w0, (q, exp) of w1 or None)."""
     n = len(args_list)
     arr = (LinearArgs * n)(*args_list)
-    r0 = (_lib.W8Ref * n)(*[_lib.W8Ref(ptr(t[0][0]), ptr(t[0][1])) for t in twins])
-    has1 = any(t[1] is not None for t in twins)
-    r1 = (_lib.W8Ref * n)(*[_lib.W8Ref(ptr(t[1][0]), ptr(t[1][1])) if t[1] is not None else _lib.W8Ref() for t in twins]) if has1 else None
+    r0, r1 = _image_refs(_lib.W8Ref, twins)
     ms = C.c_float(0.0)
     check(lib.ua2_linear_w8_many_chain_timed(arr, r0, r1, n, iters, stream(), C.byref(ms)), "ua2_linear_w8_many_chain_timed")
     return ms.value / (n * iters)
