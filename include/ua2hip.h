@@ -250,7 +250,14 @@ typedef struct ua2_linear_args {
      16-column tile, added in a fixed butterfly order (xor 1, 2, 4, 8; the first level fused: an even column c contributes
      fma(y_c, y_c, RN(y_{c+1}^2))) — the same tree in every kernel, so a row's statistic does not depend on the row count.  N % 32 == 0 (the launcher enforces it: whole bf16 MFMA chunks of the consumer).
      Consumer side — UA2_PRO_SCALED: x_h (M <= the decode kernel's row tile) or x_packed, and x_ssq [M, K / 16]; eps as
-     for UA2_PRO_NORM.  rstd[m] = rsqrt(sum_j x_ssq[m][j] / K + eps), j summed as 16 interleaved chains + butterfly. */
+     for UA2_PRO_NORM.  rstd[m] = rsqrt(sum_j x_ssq[m][j] / K + eps), j summed as 16 interleaved chains + butterfly.
+     [v10, addition] bf16 operand rows without a norm (UA2_BF16, launches the decode kernel serves: up to ua2_gemv_rows_preferred rows).
+     Producer side — UA2_EPI_SWIGLU with y_h != NULL (no y_norm_w): the result, rounded RNE to bf16, row-major [M, ldy] (y's stride, not ldh); y may then be
+     NULL (the fp32 store disappears where nobody reads it).  Consumer side — UA2_PRO_CAST with x_h != NULL ([M, ldx] bf16: x's stride; K % 32 == 0,
+     ldx % 8 == 0, x_h 16-byte aligned; x is not read): the operand row(s) are copied into the kernel's LDS tile as they are, instead of every
+     workgroup loading the fp32 row and rounding it — the same RNE of the same value, done once: bit-identical to the launch on fp32 x.
+     RESIDUAL and STORE epilogues; bf16 weights, their 13-bit images and fp8 twins.  Any other launch with these fields set (more rows,
+     UA2_F32, another epilogue, x_packed beside x_h) is refused with a message. */
   const float* y_norm_w;
   void* y_h;
   int32_t ldh;            /* row stride (elements) of y_h / x_h */
@@ -393,6 +400,10 @@ typedef struct ua2_attn_args {
   int32_t flags;               /* [v8] UA2_ATTN_BF16_QP: the grouped form may round q and the softmax weights to bf16 once (no hi / lo
                                   split) — what torch SDPA under bf16 autocast computes (the codec's DiT, reason_tokenizer.py:265); half the
                                   matrix work.  Served at head size 64, 8 query tiles; ignored (the fp32-grade form runs) elsewhere. */
+  void* y_h;                   /* [v10, addition] optional (ua2_attn's row-by-row form, UA2_BF16): the output rounded RNE to bf16, row-major
+                                  [R, ldh] — the x_h of an O-projection of one row tile (ua2_linear_args.x_h under UA2_PRO_CAST).  y and
+                                  y_packed may then both be NULL.  The grouped form, ua2_attn_local and ua2_attn_relbias refuse it. */
+  int32_t ldh;                 /* row stride (elements) of y_h, >= n_head*head_size */
 } ua2_attn_args;
 #define UA2_ATTN_BF16_QP 1
 

@@ -58,7 +58,7 @@ class LinearArgs(C.Structure):
 class AttnArgs(C.Structure):
     _fields_ = [("dtype", i32), ("R", i32), ("q", vp), ("row_pos", vp), ("row_seq", vp), ("kv", KvGeom), ("y", vp),
                 ("window", i32), ("y_packed", vp), ("group_rows", vp), ("group_seq", vp), ("group_nkeys", vp), ("n_groups", i32),
-                ("group_q_tiles", i32), ("flags", i32)]
+                ("group_q_tiles", i32), ("flags", i32), ("y_h", vp), ("ldh", i32)]
 
 
 class Conv1dArgs(C.Structure):

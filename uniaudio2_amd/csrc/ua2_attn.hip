@@ -242,6 +242,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_kerne
 #pragma unroll 8
     for (int w = 0; w < NS; ++w) acc += wgt[w * kMaxG + h] * st_o[((size_t)w * G + h) * HS + d];
     if (a.y) a.y[((size_t)r * a.kv.n_head + (size_t)kvh * G + h) * HS + d] = acc;
+    if (a.y_h) store_elem<DT>(a.y_h, (size_t)r * a.ldh + (size_t)(kvh * G + h) * HS + d, acc);   // the O-projection's x_h (one row tile)
     if (a.y_packed) store_packed_operand<DT>(a.y_packed, r, (kvh * G + h) * HS + d, a.kv.n_head * HS / Elem<DT>::KC, acc);
   }
 }
@@ -592,8 +593,11 @@ int launch_local(const ua2_attn_args& a, hipStream_t s) {
 
 int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s) {
   UA2_CHECK(a.R > 0, "ua2_attn: R=%d", a.R);
-  UA2_CHECK(a.q && a.row_pos && (a.y || a.y_packed) && a.kv.k_pool && a.kv.v_pool && a.kv.page_table,
+  UA2_CHECK(a.q && a.row_pos && (a.y || a.y_packed || a.y_h) && a.kv.k_pool && a.kv.v_pool && a.kv.page_table,
             "ua2_attn: NULL pointer argument");
+  // y_h: written by the row-by-row kernel only (the decode form whose O-projection is a launch of one row tile)
+  UA2_CHECK(!a.y_h || (a.dtype == UA2_BF16 && a.ldh >= a.kv.n_head * a.kv.head_size && !(a.group_rows && a.n_groups > 0 && a.window <= 0)),
+            "ua2_attn: y_h needs UA2_BF16, ldh >= n_head*head_size and the row-by-row form (no row groups)");
   UA2_CHECK(a.kv.n_kv > 0 && a.kv.n_head % a.kv.n_kv == 0 && a.kv.n_head / a.kv.n_kv <= kMaxG,
             "ua2_attn: n_head=%d n_kv=%d not supported (group size <= %d)", a.kv.n_head, a.kv.n_kv, kMaxG);
   UA2_CHECK(a.kv.ring_pages == 0 || (a.window > 0 && a.kv.ring_pages <= a.kv.max_pages && a.window <= (a.kv.ring_pages - 1) * UA2_PAGE + 1 &&
@@ -612,6 +616,7 @@ int ua2_attn_launch(const ua2_attn_args& a, hipStream_t s) {
 
 int ua2_attn_local_launch(const ua2_attn_args& a, hipStream_t s) {
   UA2_CHECK(a.R > 0 && a.q && a.row_pos && (a.y || a.y_packed) && a.kv.k_pool && a.kv.v_pool && a.kv.page_table, "ua2_attn_local: bad arguments");
+  UA2_CHECK(!a.y_h, "ua2_attn_local: y_h is an output of ua2_attn's row-by-row form");
   UA2_CHECK(a.kv.n_kv > 0 && a.kv.n_head % a.kv.n_kv == 0 && a.kv.n_head % (128 / std::max(a.kv.head_size, 1)) == 0,
             "ua2_attn_local: n_head=%d n_kv=%d head_size=%d not supported", a.kv.n_head, a.kv.n_kv, a.kv.head_size);
   if (a.dtype == UA2_BF16) return launch_local<UA2_BF16>(a, s);

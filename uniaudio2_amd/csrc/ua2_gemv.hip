@@ -24,6 +24,10 @@ namespace {
 
 constexpr int kMaxWaves = 16;
 
+// gemv_body's form of UA2_PRO_CAST with the operand handed over as bf16 rows (ua2_linear_args.x_h; never an ABI value: a.prologue stays
+// UA2_PRO_CAST).  An instantiation of its own, so that the fp32-operand forms keep their registers.
+constexpr int kProRowH = 5;
+
 // UA2_PRO_LOCAL_ATTN: this wave's share of the row's short-context attention, written straight into the LDS
 // operand row.  `burst` issues the wave's weight loads; it is called after the first pass's small loads are out
 // (a wave's loads return in order: q / K / V must not queue behind the weight stream).
@@ -246,12 +250,16 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   // the epilogue needs goes out BEFORE the weight burst (it then completes in one L2 round trip
   // while the weights are still streaming), never behind it.
   constexpr int XPT = 2;  // float4 per thread kept in registers on the single-row fast path
-  const bool one = (PRO != UA2_PRO_LOCAL_ATTN) && (PRO != UA2_PRO_SCALED) && (rows == 1) && (a.K <= XPT * 4 * nthreads);
+  constexpr bool ROWH = PRO == UA2_PRO_SCALED || PRO == kProRowH;     // the operand arrives as bf16 rows (a.x_h)
+  const bool one = (PRO != UA2_PRO_LOCAL_ATTN) && !ROWH && (rows == 1) && (a.K <= XPT * 4 * nthreads);
   // UA2_PRO_SCALED: the operand row(s) arrive already rounded (RNE_bf16(x (.) w), written by the producer of x): a 16-byte
   // copy into the LDS tile — no statistics, no conversion, one barrier.  The first row's piece goes out before the weights.
+  // kProRowH (UA2_PRO_CAST with x_h): the same copy of RNE_bf16(x), rounded once by x's producer instead of in every workgroup —
+  // half the operand bytes in front of the burst; no statistics and no row scale.
   u32x4 xh0 = u32x4{0u, 0u, 0u, 0u};
-  if constexpr (PRO == UA2_PRO_SCALED) {
-    if (tid * 8 < a.K) xh0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)m0 * a.ldh + tid * 8);
+  const int ldxh = (PRO == kProRowH) ? a.ldx : a.ldh;              // x_h in x's place: x's stride
+  if constexpr (ROWH) {
+    if (tid * 8 < a.K) xh0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)m0 * ldxh + tid * 8);
   }
   float4 xv[XPT], nv[XPT], nb[XPT];
   const bool ln = (PRO == UA2_PRO_NORM) && a.norm_kind == UA2_NORM_LAYERNORM;
@@ -342,15 +350,17 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   };
   if constexpr (PRO == UA2_PRO_LOCAL_ATTN) {
     // operand row already in LDS
-  } else if constexpr (PRO == UA2_PRO_SCALED) {
-    static_assert(DT == UA2_BF16 || PRO != UA2_PRO_SCALED, "scaled hand-over is a bf16 contract");
+  } else if constexpr (ROWH) {
+    static_assert(DT == UA2_BF16 || !ROWH, "bf16 operand rows are a bf16 contract");
     const int kpad = nchunks * KC;                               // K % 32 == 0 (checked by the launcher): kpad == K
-    for (int r0 = 0; r0 < rows; ++r0) {
-      const unsigned short* xr = reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)(m0 + r0) * a.ldh;
-      for (int k = tid * 8; k < kpad; k += nthreads * 8) {
-        const u32x4 v = (r0 == 0 && k == tid * 8) ? xh0 : *reinterpret_cast<const u32x4*>(xr + k);
-        *reinterpret_cast<u32x4*>(a_lds + ((size_t)r0 * a_stride + k) * BYTES) = v;
-      }
+    // The piece requested before the burst is written in straight-line code: its wait then counts the loads issued behind it and lets
+    // the burst stay in flight.  Inside the loop below it shared one wait with the pieces loaded there, and that wait is for EVERY
+    // outstanding load: the LDS write, the barrier and the first MFMA stood behind the last weight fragment (the ISA showed vmcnt(0)).
+    if (tid * 8 < kpad) *reinterpret_cast<u32x4*>(a_lds + (size_t)tid * 8 * BYTES) = xh0;
+    for (int r0 = 0; r0 < rows; ++r0) {        // what is left: further pieces of a long row, further rows (they queue behind the burst)
+      const unsigned short* xr = reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)(m0 + r0) * ldxh;
+      for (int k = (r0 == 0 ? nthreads : 0) * 8 + tid * 8; k < kpad; k += nthreads * 8)
+        *reinterpret_cast<u32x4*>(a_lds + ((size_t)r0 * a_stride + k) * BYTES) = *reinterpret_cast<const u32x4*>(xr + k);
     }
   } else if (one) {
     NormStat st{0.f, 1.f, 0.f};
@@ -545,7 +555,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     // fp8 weights: the column's scale 2^e, once, on the reduced sum (exact: e in [-117, 120] keeps 2^e a normal float)
     if constexpr (FP8) v[t] = __fmul_rn(s, __uint_as_float((unsigned)(wexp[t] + 127) << 23));
   }
-  linear_epilogue<DT, EPI, NT>(a, v, tile, row, col, pre, m0, rows);
+  linear_epilogue<DT, EPI, NT, true, true>(a, v, tile, row, col, pre, m0, rows);
 }
 
 template <int DT, int PRO, int EPI, int CPW, bool MR, bool FOLD = false>
@@ -749,7 +759,7 @@ int image_form(Ua2WForm form, int nchunks, const Geometry& geo) {
 constexpr bool w8_pair(int pro, int epi) {
   switch (pro) {
     case UA2_PRO_NORM: case UA2_PRO_SCALED: return epi == UA2_EPI_QKV_ROPE || epi == UA2_EPI_SWIGLU || epi == UA2_EPI_STORE;
-    case UA2_PRO_CAST: return epi == UA2_EPI_RESIDUAL || epi == UA2_EPI_STORE;
+    case UA2_PRO_CAST: case kProRowH: return epi == UA2_EPI_RESIDUAL || epi == UA2_EPI_STORE;
     case UA2_PRO_LOCAL_ATTN: return epi == UA2_EPI_RESIDUAL;
     default: return false;
   }
@@ -836,6 +846,11 @@ int launch_dt(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nul
     if (a.epilogue == UA2_EPI_SWIGLU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_SWIGLU>(a, s, w);
     if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_STORE>(a, s, w);
     if (a.epilogue == UA2_EPI_GELU) return launch_cpw<DT, UA2_PRO_NORM, UA2_EPI_GELU>(a, s, w);
+  } else if (a.prologue == UA2_PRO_CAST && a.x_h) {      // bf16 operand rows (the launcher has checked: UA2_BF16, K % 32 == 0, ldx % 8 == 0)
+    if constexpr (DT == UA2_BF16) {
+      if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, kProRowH, UA2_EPI_RESIDUAL>(a, s, w);
+      if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, kProRowH, UA2_EPI_STORE>(a, s, w);
+    }
   } else if (a.prologue == UA2_PRO_CAST) {
     if (a.epilogue == UA2_EPI_RESIDUAL) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_RESIDUAL>(a, s, w);
     if (a.epilogue == UA2_EPI_STORE) return launch_cpw<DT, UA2_PRO_CAST, UA2_EPI_STORE>(a, s, w);
@@ -877,6 +892,7 @@ bool ua2_gemv_rider_ok(const ua2_linear_args& a, const ua2_linear_args& r) {
   static Ua2EnvInt off{"UA2_NO_RIDER", 0};
   if (off.set()) return false;
   if (a.dtype != UA2_BF16 || a.K % 32 || a.x_packed) return false;
+  if (a.x_h ? (a.ldx % 8 != 0 || a.ldx < a.K || (reinterpret_cast<uintptr_t>(a.x_h) & 15)) : !a.x) return false;     // the host's operand: bf16 rows (16-byte pieces) or fp32 x
   const int nch = a.K / 32, gx = ua2_ceil_div(a.N, 16);
   const Geometry geo = pick_geometry(nch, gx, 1);
   if (geo.waves * geo.cpw != nch || gx >= 256 || rider_host_form(a, geo) < 0) return false;
@@ -904,7 +920,8 @@ int ua2_gemv_launch_with_rider(const ua2_linear_args& a, const ua2_linear_args& 
   };
 #define UA2_RIDER(PRO_, EPI_, CPW_) { constexpr auto kern = gemv_rider_kernel<PRO_, EPI_, CPW_, 12>; ua2_allow_big_lds<kern>(); go(kern); }
   if (form != 0) return 1;
-  UA2_RIDER(UA2_PRO_CAST, UA2_EPI_RESIDUAL, 16)
+  if (a.x_h) UA2_RIDER(kProRowH, UA2_EPI_RESIDUAL, 16)       // the host's operand as bf16 rows (ua2_gemv_rider_ok has checked them)
+  else UA2_RIDER(UA2_PRO_CAST, UA2_EPI_RESIDUAL, 16)
 #undef UA2_RIDER
   ua2_count_launch(UA2_CNT_GEMV);
   UA2_LAUNCH_CHECK();

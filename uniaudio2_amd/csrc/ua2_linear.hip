@@ -236,6 +236,17 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights*
     UA2_CHECK(a.epilogue != UA2_EPI_QKV_ROPE || a.rope_mode != UA2_ROPE_NONE,
               "ua2_linear: UA2_PRO_SCALED with a QKV_ROPE epilogue needs a rotation mode (UA2_ROPE_NONE is served by the NORM / CAST prologues)");
   }
+  // bf16 operand rows without a norm (include/ua2hip.h, beside y_norm_w): the decode kernel's launches only, or an error
+  const bool x_rows = a.prologue == UA2_PRO_CAST && a.x_h, y_rows = a.epilogue == UA2_EPI_SWIGLU && a.y_h;
+  if (x_rows)
+    UA2_CHECK(decode_rows() && a.K % 32 == 0 && a.ldx % 8 == 0 && a.ldx >= a.K && (reinterpret_cast<uintptr_t>(a.x_h) & 15) == 0 &&
+                  (a.epilogue == UA2_EPI_RESIDUAL || a.epilogue == UA2_EPI_STORE) && !w8_many,
+              "ua2_linear: UA2_PRO_CAST with x_h needs UA2_BF16, up to %d rows, K %% 32 == 0, ldx %% 8 == 0, ldx >= K, a 16-byte aligned x_h, "
+              "no x_packed and a RESIDUAL / STORE epilogue", a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
+  if (y_rows)
+    UA2_CHECK(decode_rows() && !a.y_norm_w && a.ldy >= a.N && !w8_many && (a.prologue == UA2_PRO_NORM || a.prologue == UA2_PRO_SCALED || a.prologue == UA2_PRO_CAST),
+              "ua2_linear: UA2_EPI_SWIGLU with y_h needs UA2_BF16, up to %d rows, ldy >= N, no y_norm_w and no x_packed",
+              a.K > 0 ? ua2_gemv_rows_preferred(UA2_BF16, a.K) : 0);
   if (a.x_packed) {   // operand handed over in fragment order by its producer: only the many-row kernels read it
     UA2_CHECK((a.prologue == UA2_PRO_CAST || a.prologue == UA2_PRO_SCALED) && g_force_general != 2,
               "ua2_linear: x_packed needs PRO_CAST / PRO_SCALED and the many-row kernels");
@@ -250,7 +261,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights*
     return rc;
   }
   UA2_CHECK(a.prologue == UA2_PRO_CAST || a.prologue == UA2_PRO_NORM, "ua2_linear: bad prologue %d", a.prologue);
-  UA2_CHECK(a.x != nullptr && a.ldx % 4 == 0, "ua2_linear: x NULL or ldx %% 4 != 0");
+  UA2_CHECK(x_rows || (a.x != nullptr && a.ldx % 4 == 0), "ua2_linear: x NULL or ldx %% 4 != 0");
   if (a.prologue == UA2_PRO_NORM)
     UA2_CHECK(a.norm_w != nullptr && (a.norm_kind != UA2_NORM_LAYERNORM || a.norm_b != nullptr) && a.norm_kind >= 0 && a.norm_kind <= 2,
               "ua2_linear: norm_w / norm_b / norm_kind invalid");
@@ -262,7 +273,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights*
             "ua2_linear: bias with the half-split QKV layout is not supported (columns are permuted at pack time)");
   UA2_CHECK(a.act_kind >= 0 && a.act_kind <= 2, "ua2_linear: bad act_kind %d", a.act_kind);
   if (a.epilogue == UA2_EPI_SWIGLU) {
-    UA2_CHECK(a.w1 != nullptr && (a.y != nullptr || a.y_packed != nullptr), "ua2_linear: SWIGLU needs w1 and y or y_packed");
+    UA2_CHECK(a.w1 != nullptr && (a.y != nullptr || a.y_packed != nullptr || y_rows), "ua2_linear: SWIGLU needs w1 and y, y_packed or y_h");
     UA2_CHECK(!a.y_packed || a.N % (a.dtype == UA2_BF16 ? 32 : 16) == 0, "ua2_linear: y_packed needs N %% chunk == 0");
   } else if (a.epilogue != UA2_EPI_GELU) {
     UA2_CHECK(!a.y_packed || a.y_norm_w || a.y_ln_w, "ua2_linear: y_packed is a SWIGLU / GELU output (or, with y_norm_w / y_ln_w, a RESIDUAL / STORE hand-over)");
@@ -287,7 +298,7 @@ int ua2_linear_launch(const ua2_linear_args& a, hipStream_t s, const Ua2Weights*
     UA2_CHECK(rc <= 0, "ua2_linear_w8_many: the fp8 weights-stationary kernel did not take the launch");
     return rc;
   }
-  if (g_force_general != 2 && demand != UA2_W_DECODE) {
+  if (g_force_general != 2 && demand != UA2_W_DECODE && !x_rows && !y_rows) {      // (bf16 operand rows: the decode kernel alone reads / writes them)
     const int rc = ua2_gemm_try_launch(a, s, g_force_general >= 3 ? g_force_general : 0, w8);  // many rows: packed operand, 128-row tiles
     if (rc <= 0) return rc;
   }

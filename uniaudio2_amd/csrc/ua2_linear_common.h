@@ -287,7 +287,9 @@ __device__ __forceinline__ float ua2_act_gelu(const ua2_linear_args& a, float x)
 // limit (chain + total accumulators), and with the emission's shuffles in their epilogue the allocator moved the totals
 // into scratch for the whole kernel (272 B/lane, the lm_head launch 222 -> 510 us) — the launcher picks the HO = true
 // instantiation only for launches that hand over.
-template <int DT, int EPI, int NT, bool HO = true>
+// ROWS = true (the decode kernel): a SWIGLU launch also serves y_h, the result as bf16 rows; compiled out of the many-row kernels, whose
+// launches never carry it (the launcher sees to that) and whose registers stay what they were.
+template <int DT, int EPI, int NT, bool HO = true, bool ROWS = false>
 __device__ __forceinline__ void linear_epilogue(const ua2_linear_args& a, const float (&vin)[NT], const int (&tile)[NT],
                                                 int row, int col, const EpiPre& p, int m0, int rows) {
   const int mr = m0 + row;
@@ -333,6 +335,7 @@ __device__ __forceinline__ void linear_epilogue(const ua2_linear_args& a, const 
     if (rvalid && n < a.N) {
       const float out = ua2_act_glu(a, v[0], v[1]);
       if (a.y) a.y[(size_t)mr * a.ldy + n] = out;
+      if constexpr (ROWS) if (a.y_h) store_elem<DT>(a.y_h, (size_t)mr * a.ldy + n, out);     // y's bf16 twin (y's stride): the x_h of a K = N launch of one row tile
       if (a.y_packed) store_packed_operand<DT>(a.y_packed, mr, n, a.N / Elem<DT>::KC, out);
     }
   } else if constexpr (EPI == UA2_EPI_GELU) {

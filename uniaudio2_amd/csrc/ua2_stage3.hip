@@ -77,6 +77,11 @@ struct ua2_stage3 {
   // redoes a tiny reduction after an ordinary kernel boundary: no flags, no counters, nothing to spin on.  UA2_NO_ARGMAX_FOLD=1, read
   // when the plan is created: off (A/B; one process can hold both plans)
   bool argmax_fold = false;
+  // Launches of one row tile of the decode kernel (bf16 plans, up to ua2_gemv_rows_preferred rows): the SwiGLU launch and the trunk's attention
+  // hand their result to the down- / O-projection as bf16 rows (ua2_linear_args.y_h / x_h under UA2_PRO_CAST, ua2_attn_args.y_h) — the RNE
+  // cast once in the producer instead of in every workgroup of the consumer, and no fp32 row in between.  The rows lie where the many-row
+  // form's packed operand would (act_ws, gemm_ws).  Same bits.  UA2_NO_ROW_OPERAND=1, read when the plan is created: off (A/B)
+  bool row_operand = false;
   int32_t npart_t, npart_a;
   int32_t topk = 1;            // 1 = greedy (fused arg-max partials); > 1 = ua2_sample_topk
   float temperature = 1.f;
@@ -130,10 +135,10 @@ void drop_graphs(ua2_stage3* h) {   // the only code that destroys recorded fram
 Ua2EnvInt g_l13_all{"UA2_L13_ALL", 0}, g_of_scaled{"UA2_OF_SCALED", 0}, g_no_scaled{"UA2_NO_SCALED", 0}, g_no_local_fuse{"UA2_NO_LOCAL_FUSE", 0} /* profiles/r1_notes.md */,
     g_no_packed_handover{"UA2_NO_PACKED_HANDOVER", 0}, g_defer_rows{"UA2_DEFER_ROWS", UA2_DEFER_CAP_ROWS}, g_no_defer{"UA2_NO_DEFER_TEXT_HEAD", 0};
 // Creation-time knobs: read from the environment when a plan is sized and created, so one process can hold plans of both forms.
-struct PlanKnobs { bool range_split, proj_table, qkv_table, scaled, argmax_fold, lossless; };
+struct PlanKnobs { bool range_split, proj_table, qkv_table, scaled, argmax_fold, lossless, row_operand; };
 PlanKnobs read_plan_knobs() {
   auto on = [](const char* name) { return getenv(name) != nullptr; };
-  return {on("UA2_RANGE_SPLIT"), !on("UA2_NO_PROJ_TABLE"), !on("UA2_NO_QKV_TABLE"), !on("UA2_NO_SCALED"), !on("UA2_NO_ARGMAX_FOLD"), !on("UA2_NO_LOSSLESS")};
+  return {on("UA2_RANGE_SPLIT"), !on("UA2_NO_PROJ_TABLE"), !on("UA2_NO_QKV_TABLE"), !on("UA2_NO_SCALED"), !on("UA2_NO_ARGMAX_FOLD"), !on("UA2_NO_LOSSLESS"), !on("UA2_NO_ROW_OPERAND")};
 }
 
 struct Carve {
@@ -379,11 +384,17 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     const int kc = dt == UA2_BF16 ? 32 : 16;
     const bool pack_o = !no_handover && R > ua2_gemv_rows_preferred(dt, qn) && qn % kc == 0;
     const bool pack_act = !no_handover && R > ua2_gemv_rows_preferred(dt, g.inter) && g.inter % kc == 0;
+    // one row tile of the decode kernel: the producer writes the bf16 rows its consumer stages (h->row_operand); never an order-free launch
+    const bool rows_ok = h->row_operand && order == UA2_SUM_ORDER_INVARIANT;
+    const bool rows_o = rows_ok && !o.local && !(o.grouped && h->n_groups > 0) && R <= ua2_gemv_rows_preferred(dt, qn) && qn % 32 == 0;   // the trunk's row-by-row attention
+    const bool rows_act = rows_ok && R <= ua2_gemv_rows_preferred(dt, g.inter) && g.inter % 32 == 0;
     if (!fuse_attn) {
       ua2_attn_args at;
       memset(&at, 0, sizeof(at));
       at.dtype = dt; at.R = R; at.q = h->q; at.row_pos = row_pos; at.row_seq = row_seq; at.kv = kv;
-      if (pack_o) at.y_packed = h->gemm_ws; else at.y = h->yattn;
+      if (pack_o) at.y_packed = h->gemm_ws;
+      else if (rows_o) { at.y_h = h->gemm_ws; at.ldh = qn; }
+      else at.y = h->yattn;
       if (o.grouped && !o.local && h->n_groups > 0) {
         at.group_rows = h->group_rows; at.group_seq = h->group_seq; at.group_nkeys = h->group_nkeys;
         at.n_groups = h->n_groups; at.group_q_tiles = h->group_q_tiles;
@@ -400,6 +411,7 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
       a.fold = *o.fold0;
     }
     if (pack_o && !fuse_attn) a.x_packed = h->gemm_ws;
+    if (rows_o) { a.x = nullptr; a.x_h = h->gemm_ws; }
     if (o.scaled) ho.produce(a, h->norms[gi][1][l]);              // x after attention -> norm_2 + fc_1 / fc_2
     a.sum_order = order; free_scratch(a);
     if (int rc = launch(a, 1)) return rc;
@@ -408,7 +420,9 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     a.dtype = dt; a.prologue = UA2_PRO_NORM; a.epilogue = UA2_EPI_SWIGLU;
     a.M = R; a.N = g.inter; a.K = C; a.x = x; a.ldx = C; a.norm_w = h->norms[gi][1][l]; a.eps = g.eps;
     a.w0 = h->ptrs[gi][2][l]; a.w1 = h->ptrs[gi][3][l]; a.ldy = g.inter;
-    if (pack_act) a.y_packed = h->act_ws; else a.y = h->act;
+    if (pack_act) a.y_packed = h->act_ws;
+    else if (rows_act) a.y_h = h->act_ws;
+    else a.y = h->act;
     if (o.scaled) ho.consume(a);
     a.sum_order = order;
     if (int rc = lin(h, a, s)) return rc;
@@ -418,6 +432,7 @@ int run_gpt(ua2_stage3* h, int gi, const ua2_gpt_desc& g, float* x, int R, const
     a.M = R; a.N = C; a.K = g.inter; a.x = h->act; a.ldx = g.inter; a.w0 = h->ptrs[gi][4][l];
     a.y = x; a.ldy = C; a.resid = x; a.ldr = C;
     if (pack_act) a.x_packed = h->act_ws;
+    if (rows_act) { a.x = nullptr; a.x_h = h->act_ws; }
     if (o.scaled) ho.produce(a, l + 1 < g.n_layer ? h->norms[gi][0][l + 1] : o.final_norm_w);   // x after the MLP -> the next layer's norm_1 + qkv
     a.sum_order = order; free_scratch(a);
     a.range_ws = h->range_ws; a.range_ws_bytes = h->range_ws_bytes;      // 33-64 rows, K = 8192: one K range per workgroup + an in-order combine (same bits)
@@ -661,6 +676,7 @@ extern "C" int ua2_stage3_create(const ua2_stage3_desc* d, ua2_stage3** out) {
               d->max_batch <= 64;
   h->npart_t = (d->vt + 15) / 16; h->npart_a = (d->va + 15) / 16;
   h->argmax_fold = knobs.argmax_fold;
+  h->row_operand = d->dtype == UA2_BF16 && knobs.row_operand;
   if (c.ptab_rows) {
     // The table is what the frame's own projection launches would write: same entry point, same arguments, rows in groups of up to 64
     // (decode kernel / weights-stationary kernel: a row's bits do not depend on its group).  Null stream, once per plan.

@@ -671,6 +671,7 @@ extern "C" int ua2_attn_relbias(const ua2_attn_args* ap, const int32_t* q_pos, c
   UA2_CHECK(a.R > 0, "ua2_attn_relbias: R=%d", a.R);
   UA2_CHECK(a.q && a.row_pos && (a.y || a.y_packed) && a.kv.k_pool && a.kv.v_pool && a.kv.page_table && q_pos && gate && rel_tab,
             "ua2_attn_relbias: NULL pointer argument");
+  UA2_CHECK(!a.y_h, "ua2_attn_relbias: y_h is an output of ua2_attn's row-by-row form");
   UA2_CHECK(a.kv.n_kv > 0 && a.kv.n_head == a.kv.n_kv, "ua2_attn_relbias: n_head=%d n_kv=%d (multi-head only)", a.kv.n_head, a.kv.n_kv);
   UA2_CHECK(a.kv.n_head <= 65535, "ua2_attn_relbias: n_head=%d exceeds the grid", a.kv.n_head);
   UA2_CHECK(a.kv.ring_pages == 0 && a.window <= 0, "ua2_attn_relbias: ring caches and windows are not served");

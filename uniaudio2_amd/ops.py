@@ -153,10 +153,11 @@ def linear(*, dtype, M, N, K, w0, prologue=PRO_CAST, epilogue=EPI_STORE, x=None,
     a = LinearArgs()
     a.dtype, a.prologue, a.epilogue = dtype_code(dtype), prologue, epilogue
     a.M, a.N, a.K = M, N, K
-    a.x, a.ldx = ptr(x), (ldx if ldx is not None else (x.shape[-1] if x is not None else 0))
+    # (PRO_CAST with x_h, EPI_SWIGLU with y_h: bf16 rows in x's / y's place, on x's / y's stride)
+    a.x, a.ldx = ptr(x), (ldx if ldx is not None else (x.shape[-1] if x is not None else (x_h.shape[-1] if x_h is not None else 0)))
     a.norm_w, a.eps = ptr(norm_w), eps
     a.w0, a.w1 = ptr(w0), ptr(w1)
-    a.y, a.ldy = ptr(y), (ldy if ldy is not None else (y.shape[-1] if y is not None else 0))
+    a.y, a.ldy = ptr(y), (ldy if ldy is not None else (y.shape[-1] if y is not None else (y_h.shape[-1] if y_h is not None else 0)))
     a.resid, a.ldr = ptr(resid), (ldr if ldr is not None else (resid.shape[-1] if resid is not None else 0))
     a.part_max, a.part_idx, a.forbid = ptr(part_max), ptr(part_idx), ptr(forbid)
     a.row_pos, a.row_seq = ptr(row_pos), ptr(row_seq)
@@ -252,10 +253,11 @@ def attn_groups(pos, seq, n_head, n_kv, device, q_tiles=None):
     return to(np.stack(rows)).contiguous(), to(gseq), to(nkeys), qt
 
 
-def attn(*, dtype, R, q, row_pos, row_seq, kv, y=None, window=0, groups=None, y_packed=None, flags=0):
+def attn(*, dtype, R, q, row_pos, row_seq, kv, y=None, window=0, groups=None, y_packed=None, flags=0, y_h=None):
     """y [R, n_head*hs] fp32 and / or y_packed: the same rows already in ua2_linear's operand order (its consumer then takes
-    them as x_packed and needs no prep launch)."""
+    them as x_packed and needs no prep launch); y_h [R, ldh] bf16: the same rows row-major (the x_h of a one-row-tile O-projection)."""
     a = AttnArgs()
+    a.y_h, a.ldh = ptr(y_h), (y_h.shape[-1] if y_h is not None else 0)
     a.flags = flags
     a.y_packed = ptr(y_packed)
     if groups is not None:
