@@ -2,8 +2,9 @@
 the AudioThinking encoder + FiLM + strided convs that turn SSL features into the three RVQ inputs,
 and the code -> latent stage: conditioning assembly, flow-matching DiT, guided Euler ODE.
 
-Plain PyTorch fp32 on the CPU, functional over reference state dicts (same keys); every function cites the reference
-file:line it follows (paths relative to /root/reference/tools/tokenizer/ReasoningCodec_film/).
+Plain PyTorch fp32 on the CPU (`dit_forward` also in float64: the anchor of tests/dit_refs.py), functional over reference
+state dicts (same keys); every function cites the reference file:line it follows (paths relative to
+/root/reference/tools/tokenizer/ReasoningCodec_film/).
 
 Pinning.  `encode_reasoning_query`, `fetch_codes_from_features`, `inference_codes` and `solve_euler` are checked
 against outputs of the reference's OWN code (tests/golden/codec_model_toy.npz, made by
@@ -260,32 +261,62 @@ def project_layer(sd, p, x, k=3):
     return F.linear(y * k ** -0.5, sd[p + "ffn_2.weight"], sd[p + "ffn_2.bias"])
 
 
-@torch.no_grad()
-def dit_forward(sd: Dict[str, torch.Tensor], hidden, timestep, heads: int, head_dim: int, eps: float = 1e-6):
-    """Transformer1DModel.forward (transformer_1d_flow.py:279-386) with norm_type='ada_norm_single',
-    activation 'gelu-approximate', attention_bias=True, no cross attention (models/model_config.json).
-    hidden (B, T, in_channels), timestep (B,) in [0, 1] -> (B, T, out_channels)."""
-    sd = {k: v.float() for k, v in sd.items()}
-    B, T, _ = hidden.shape
-    D = heads * head_dim
-    h = project_layer(sd, "proj_in.", hidden.float()) + sinusoidal_pos_embed(T, D)[None]                   # :332-338
-    emb = timestep_embedding(timestep)                                                                    # adaln_single :347
+def dit_timestep(sd, timestep, dt=torch.float32):
+    """adaln_single (transformer_1d_flow.py:87-115, :347): (ts (B, 6D), embedded timestep (B, D)).  The 512-entry vector is data of
+    the formula: fp32 (its argument reaches 1000), then widened to `dt`."""
+    emb = timestep_embedding(timestep).to(dt)
     emb = F.linear(F.silu(F.linear(emb, sd["adaln_single.emb.timestep_embedder.linear_1.weight"], sd["adaln_single.emb.timestep_embedder.linear_1.bias"])),
                    sd["adaln_single.emb.timestep_embedder.linear_2.weight"], sd["adaln_single.emb.timestep_embedder.linear_2.bias"])
-    ts = F.linear(F.silu(emb), sd["adaln_single.linear.weight"], sd["adaln_single.linear.bias"])           # (B, 6D)  :113
-    n_layers = 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("transformer_blocks."))
-    for i in range(n_layers):
-        p = f"transformer_blocks.{i}."
-        sh_a, sc_a, g_a, sh_m, sc_m, g_m = (sd[p + "scale_shift_table"][None] + ts.reshape(B, 6, -1)).chunk(6, dim=1)   # attention.py:308-310
-        n = F.layer_norm(h, (D,), None, None, eps) * (1 + sc_a) + sh_a                                     # :311-319
-        q, k, v = (F.linear(n, sd[p + f"attn1.to_{c}.weight"], sd[p + f"attn1.to_{c}.bias"]).view(B, T, heads, head_dim).transpose(1, 2)
-                   for c in "qkv")
-        att = torch.softmax(torch.einsum("bhid,bhjd->bhij", q, k) * head_dim ** -0.5, dim=-1)
-        o = torch.einsum("bhij,bhjd->bhid", att, v).transpose(1, 2).reshape(B, T, D)
-        h = g_a * F.linear(o, sd[p + "attn1.to_out.0.weight"], sd[p + "attn1.to_out.0.bias"]) + h           # :345-349
-        n = F.layer_norm(h, (D,), None, None, eps) * (1 + sc_m) + sh_m                                     # :388-390
-        f = F.gelu(F.linear(n, sd[p + "ff.net.0.proj.weight"], sd[p + "ff.net.0.proj.bias"]), approximate="tanh")
-        h = g_m * F.linear(f, sd[p + "ff.net.2.weight"], sd[p + "ff.net.2.bias"]) + h                      # :401-405
-    shift, scale = (sd["scale_shift_table"][None] + emb[:, None]).chunk(2, dim=1)                          # transformer_1d_flow.py:378
-    h = F.layer_norm(h, (D,), None, None, 1e-6) * (1 + scale) + shift                                      # :379-381
+    return F.linear(F.silu(emb), sd["adaln_single.linear.weight"], sd["adaln_single.linear.bias"]), emb       # :113
+
+
+def dit_block(sd, i, h, ts, heads, head_dim, dt=torch.float32, eps=1e-6):
+    """BasicTransformerBlock i (attention.py:308-405) from the residual stream h (B, T, D) and ts (B, 6D), both already in `dt`;
+    sd holds `dt` tensors."""
+    B, T, D = h.shape
+    p = f"transformer_blocks.{i}."
+    sh_a, sc_a, g_a, sh_m, sc_m, g_m = (sd[p + "scale_shift_table"][None] + ts.reshape(B, 6, -1)).chunk(6, dim=1)   # attention.py:308-310
+    n = F.layer_norm(h, (D,), None, None, eps) * (1 + sc_a) + sh_a                                     # :311-319
+    q, k, v = (F.linear(n, sd[p + f"attn1.to_{c}.weight"], sd[p + f"attn1.to_{c}.bias"]).view(B, T, heads, head_dim).transpose(1, 2)
+               for c in "qkv")
+    att = torch.softmax(torch.einsum("bhid,bhjd->bhij", q, k) * head_dim ** -0.5, dim=-1)
+    o = torch.einsum("bhij,bhjd->bhid", att, v).transpose(1, 2).reshape(B, T, D)
+    h = g_a * F.linear(o, sd[p + "attn1.to_out.0.weight"], sd[p + "attn1.to_out.0.bias"]) + h           # :345-349
+    n = F.layer_norm(h, (D,), None, None, eps) * (1 + sc_m) + sh_m                                     # :388-390
+    f = F.gelu(F.linear(n, sd[p + "ff.net.0.proj.weight"], sd[p + "ff.net.0.proj.bias"]), approximate="tanh")
+    return g_m * F.linear(f, sd[p + "ff.net.2.weight"], sd[p + "ff.net.2.bias"]) + h                   # :401-405
+
+
+def dit_final(sd, h, emb):
+    """Final modulation and proj_out (transformer_1d_flow.py:378-384) from the residual stream and the embedded timestep."""
+    shift, scale = (sd["scale_shift_table"][None] + emb[:, None]).chunk(2, dim=1)                          # :378
+    h = F.layer_norm(h, (h.shape[-1],), None, None, 1e-6) * (1 + scale) + shift                            # :379-381
     return project_layer(sd, "proj_out.", h)                                                              # :384
+
+
+def dit_layers(sd):
+    return 1 + max(int(k.split(".")[1]) for k in sd if k.startswith("transformer_blocks."))
+
+
+@torch.no_grad()
+def dit_forward(sd: Dict[str, torch.Tensor], hidden, timestep, heads: int, head_dim: int, eps: float = 1e-6, dt=torch.float32, taps=None):
+    """Transformer1DModel.forward (transformer_1d_flow.py:279-386) with norm_type='ada_norm_single',
+    activation 'gelu-approximate', attention_bias=True, no cross attention (models/model_config.json).
+    hidden (B, T, in_channels), timestep (B,) in [0, 1] -> (B, T, out_channels), evaluated in `dt` (float64: the anchor of
+    tests/dit_refs.py; the sinusoidal position table and the timestep vector stay fp32 data, widened).
+    taps: a list that receives h after proj_in + positions, h after every block, and the output."""
+    sd = {k: v.to(dt) for k, v in sd.items()}
+    B, T, _ = hidden.shape
+    D = heads * head_dim
+    h = project_layer(sd, "proj_in.", hidden.to(dt)) + sinusoidal_pos_embed(T, D).to(dt)[None]             # :332-338
+    ts, emb = dit_timestep(sd, timestep, dt)                                                              # adaln_single :347
+    if taps is not None:
+        taps.append(h)
+    for i in range(dit_layers(sd)):
+        h = dit_block(sd, i, h, ts, heads, head_dim, dt, eps)
+        if taps is not None:
+            taps.append(h)
+    y = dit_final(sd, h, emb)
+    if taps is not None:
+        taps.append(y)
+    return y

@@ -278,12 +278,16 @@ class Transformer1DModel(nn.Module):
         self._plan_gen = getattr(self, "_plan_gen", 0) + 1
         return self
 
-    def _forward_impl(self, hidden_states, emb):
+    def _forward_impl(self, hidden_states, emb, taps=None):
+        """taps (tests/dit_refs.py): a list that receives clones of the residual stream (B, T, D) after proj_in + positions and after
+        every block, then the output: the stages of oracle/codec_model_oracle.py dit_forward's taps."""
         B, T, Cin = hidden_states.shape
         D = self.inner_dim
         x = hidden_states.reshape(B * T, Cin).float().contiguous()
         h = self.proj_in.run(x, B, T)
         h = ops.ew_fma(h, c=self._pe[:T])                                     # + pos_embed (:338); the modulo broadcast repeats it per batch element
+        if taps is not None:
+            taps.append(h.view(B, T, D).clone())
         ts, e = self.adaln_single.run(emb)
         mod_all = ops.ew_fma(self._table_all, c=ts)                           # every block's table + timestep in one launch (was 3 per block)
         mod1_all = ops.ew_fma(mod_all, beta=1.0)
@@ -295,11 +299,16 @@ class Transformer1DModel(nn.Module):
                 o = (l + 1) * 6 * D
                 nxt = (mod1_all[o + D:o + 2 * D], mod_all[o:o + D])
             _, xp = blk.run(h, ts, self._kv, mod_all[l * 6 * D:(l + 1) * 6 * D], mod1_all[l * 6 * D:(l + 1) * 6 * D], x_packed=xp, nxt=nxt)
+            if taps is not None:
+                taps.append(h.view(B, T, D).clone())
         mod = ops.ew_fma(self._table, c=e)                                    # (2, D): scale_shift_table + embedded_timestep  :378
         shift, scale = mod[:D], mod[D:]
         hn = ops.layernorm_rows(h, None, None, 1e-6)                          # norm_out :379
         hm = ops.ew_fma(hn, b=ops.ew_fma(scale, beta=1.0), c=shift)           # * (1 + scale) + shift  :381
-        return self.proj_out.run(hm, B, T).view(B, T, self.out_channels)
+        y = self.proj_out.run(hm, B, T).view(B, T, self.out_channels)
+        if taps is not None:
+            taps.append(y.clone())
+        return y
 
     def step_embedding(self, timestep, dev):
         """sinusoid(t) on the device, cached per t (the Euler schedule revisits the same few times window after window)."""
@@ -325,11 +334,14 @@ class Transformer1DModel(nn.Module):
         self._kv = kv
 
     @torch.inference_mode()
-    def forward(self, hidden_states, timestep: float, use_graph: bool = True):
+    def forward(self, hidden_states, timestep: float, use_graph: bool = True, taps=None):
         """hidden_states (B, T, in_channels) fp32, one timestep for the whole batch -> (B, T, out_channels) fp32
         (transformer_1d_flow.py:279-386 `.sample`).  The ~400 launches of a step are captured once per (B, T) into a HIP
         graph and replayed (the Euler loop calls this 10-50 times per window with identical shapes; issued one by one from
-        Python the step was host-bound: 39 ms at the released size against ~8 ms of kernel time)."""
+        Python the step was host-bound: 39 ms at the released size against ~8 ms of kernel time).
+        taps: see _forward_impl; honoured only with use_graph=False outside a capture (a recorded step has no place for them)."""
+        if taps is not None and (use_graph or torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("Transformer1DModel: taps need use_graph=False outside a graph capture")
         if not self._ready:
             self.prepare()
         B, T, Cin = hidden_states.shape
@@ -346,7 +358,7 @@ class Transformer1DModel(nn.Module):
             return self._forward_impl(hidden_states, self.step_embedding(timestep, dev))
         emb = self.adaln_single.sinusoid(float(timestep))
         if not use_graph:
-            return self._forward_impl(hidden_states, emb.to(dev))
+            return self._forward_impl(hidden_states, emb.to(dev), taps)
         g = self._graphs.get((B, T))
         if g is None:
             x_in = torch.empty(B, T, Cin, dtype=torch.float32, device=dev)
