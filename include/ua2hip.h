@@ -347,7 +347,7 @@ int ua2_debug_force_general_linear(int on);
 
 /* Test hooks (ABI v9).  ua2_debug_kernel_launches: how many launches of a kernel family this process has issued so far —
  * "gemm2" (ua2_gemm2.hip, the order-free many-row GEMM), "gemm" (ua2_gemm.hip's tiled kernel), "skinny2", "skinny2_w8" (the weights-stationary kernel on fp8 weights), "gemv", "gemv_w8" (the decode kernel on fp8 weights), "gemv_l13" (the decode kernel on 13-bit images of its bf16 weights: such a launch counts under "gemv" as well), "rsplit" ([v10] the range split
- * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather), "score" (calls of ua2_stage3_score that issued their launches); -1 for an unknown
+ * of ua2_skinny.hip: main + combine count once), "text_flush" (calls of ua2_stage3_text_flush that issued their launches), "argmax" (launches of the two greedy tails: arg-max + embedding gather, arg-max + table gather), "score" (calls of ua2_stage3_score that issued their launches), "gemv_hot" / "attn_hot" (decode-kernel / ua2_attn row-by-row launches served by the form that takes its leading arguments as plain kernel parameters: counted besides their families); -1 for an unknown
  * name.  A test that claims "the order-free kernel ran" reads the counter on both sides of the call instead of trusting the
  * launcher's rules.  ua2_debug_refresh_env: the launchers read their UA2_* tuning / A-B environment variables ONCE (they used to
  * call getenv on every launch); a process that changes one of them afterwards (the tests do) calls this to have them read again. */

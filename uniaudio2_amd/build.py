@@ -12,7 +12,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libua2hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + os.environ.get("UA2_EXTRA_FLAGS", "").split()
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
+# Per file, in front of UA2_EXTRA_FLAGS (the last occurrence of an -mllvm option wins: UA2_EXTRA_FLAGS="-mllvm -amdgpu-kernarg-preload-count=0"
+# builds without).  Kernarg preload: the dispatcher places a kernel's leading 14 dwords of pointer / int parameters in user SGPRs, so the
+# decode kernels start with their hot arguments (csrc/ua2_gemv.hip GemvHot, csrc/ua2_attn.hip attn_fused_hot_kernel) instead of fetching them; profiles/hot_args.md.
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+FILE_FLAGS = {"ua2_gemv.hip": PRELOAD, "ua2_attn.hip": PRELOAD}
+EXTRA = os.environ.get("UA2_EXTRA_FLAGS", "").split()
 
 
 def sources():
@@ -40,7 +46,7 @@ def build_lib(force=False, verbose=True):
         # per-object: a source is recompiled when it, or any header, is newer than its object (force = everything)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), hdr_t):
             continue
-        procs.append((src, subprocess.Popen([HIPCC, *FLAGS, "-c", src, "-o", obj],
+        procs.append((src, subprocess.Popen([HIPCC, *FLAGS, *FILE_FLAGS.get(os.path.basename(src), []), *EXTRA, "-c", src, "-o", obj],
                                             stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     failed = False
     for src, p in procs:

@@ -30,6 +30,21 @@ constexpr int kMaxG = 4;  // query heads per kv head (Llama-3.2-3B: 3, local dec
 // Output is the normalised attention row in fp32 (input of the O-projection).
 constexpr int kFusedWaves = 8;
 
+// attn_fused_hot_kernel's ua2_attn_args, read through the kernel-argument pointer taken at the call: the empty asm keeps the compiler from
+// issuing their scalar loads at the kernel's entry, where a wait on them would stand in front of the first K / V load (ua2_gemv.hip cold_args).
+constexpr int kAttnHotBytes = 5 * 8 + 4 * 4;
+static_assert(kAttnHotBytes == 14 * 4 && kAttnHotBytes % alignof(ua2_attn_args) == 0, "the hot block is 14 dwords and ua2_attn_args follows it without padding");
+template <bool HOT>
+__device__ __forceinline__ const ua2_attn_args& attn_cold_args(const ua2_attn_args& a) {
+  if constexpr (HOT) {
+    const __attribute__((address_space(4))) char* kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp) : : "memory");
+    return *reinterpret_cast<const ua2_attn_args*>((const char*)(kp + kAttnHotBytes));
+  } else {
+    return a;
+  }
+}
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
   return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
@@ -53,8 +68,10 @@ __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp
 // with the prefetch), so that TWO workgroups share a CU — batched decode launches more workgroups than the device has CUs (64 rows x 8
 // kv heads = 512, 1024 rows = 8192) and each of them is a chain of dependent round trips (position -> page id -> K / V -> states
 // through LDS): occupancy, not lookahead, is what such a launch waits for.  Same arithmetic, same order: same bits.
-template <int DT, int HS, int kG, bool PF = true>
-__global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_kernel(const ua2_attn_args a) {
+// HOT: the instantiation of attn_fused_hot_kernel, whose `a` is built from its leading kernel parameters (registers, not memory: see
+// there); the outputs are read from the launch's ua2_attn_args once the keys have been walked.
+template <int DT, int HS, int kG, bool PF, bool HOT>
+__device__ __forceinline__ void attn_fused_body(const ua2_attn_args& a, const ua2_attn_args& a_cold) {
   constexpr int EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
   constexpr int LPR = HS / EPL, RPW = 64 / LPR;   // lanes per cache row, row groups per wave
   constexpr int UNR = (DT == UA2_BF16) ? 4 : 2;   // wave instructions per step (K and V each)
@@ -201,6 +218,7 @@ __global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_kerne
             make_float4(o_run[h][4 * e4], o_run[h][4 * e4 + 1], o_run[h][4 * e4 + 2], o_run[h][4 * e4 + 3]);
     }
   }
+  const ua2_attn_args& ao = attn_cold_args<HOT>(a_cold);      // y, y_h, ldh, y_packed
   __syncthreads();
   // merge, phase 1: wave h turns the NS (m, l) pairs of head h into normalised weights
   //   wgt[w] = exp(m_w - M) / sum_w exp(m_w - M) l_w        (0 for groups that saw no row)
@@ -241,10 +259,32 @@ __global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_kerne
     float acc = 0.f;
 #pragma unroll 8
     for (int w = 0; w < NS; ++w) acc += wgt[w * kMaxG + h] * st_o[((size_t)w * G + h) * HS + d];
-    if (a.y) a.y[((size_t)r * a.kv.n_head + (size_t)kvh * G + h) * HS + d] = acc;
-    if (a.y_h) store_elem<DT>(a.y_h, (size_t)r * a.ldh + (size_t)(kvh * G + h) * HS + d, acc);   // the O-projection's x_h (one row tile)
-    if (a.y_packed) store_packed_operand<DT>(a.y_packed, r, (kvh * G + h) * HS + d, a.kv.n_head * HS / Elem<DT>::KC, acc);
+    if (ao.y) ao.y[((size_t)r * a.kv.n_head + (size_t)kvh * G + h) * HS + d] = acc;
+    if (ao.y_h) store_elem<DT>(ao.y_h, (size_t)r * ao.ldh + (size_t)(kvh * G + h) * HS + d, acc);   // the O-projection's x_h (one row tile)
+    if (ao.y_packed) store_packed_operand<DT>(ao.y_packed, r, (kvh * G + h) * HS + d, a.kv.n_head * HS / Elem<DT>::KC, acc);
   }
+}
+
+template <int DT, int HS, int kG, bool PF = true>
+__global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_kernel(const ua2_attn_args a) {
+  attn_fused_body<DT, HS, kG, PF, false>(a, a);
+}
+
+// The same kernel with what it reads in front of its first K / V load as its FIRST parameters, 14 dwords of pointers and ints (as
+// ua2_gemv.hip's gemv_hot_kernel: one line of the kernel arguments, and what the dispatcher can preload into user SGPRs; a by-value struct
+// in front would prevent that).  Only the position -> page id -> K / V dereference remains a dependent chain.  Rows are their own
+// sequences (row_seq == NULL: every decode frame); other launches take attn_fused_kernel.
+template <int DT, int HS, int kG, bool PF = true>
+__global__ __launch_bounds__(kFusedWaves * 64, PF ? 2 : 4) void attn_fused_hot_kernel(const float* q, const int32_t* row_pos, const int32_t* page_table,
+                                                                              void* k_pool, void* v_pool, const int max_pages,
+                                                                              const unsigned heads, const int window, const int ring_pages,
+                                                                              const ua2_attn_args a_cold) {
+  ua2_attn_args a{};
+  a.q = q; a.row_pos = row_pos; a.row_seq = nullptr;
+  a.kv.k_pool = k_pool; a.kv.v_pool = v_pool; a.kv.page_table = page_table;
+  a.kv.max_pages = max_pages; a.kv.n_kv = (int)(heads & 0xffffu); a.kv.n_head = (int)(heads >> 16); a.kv.head_size = HS; a.kv.ring_pages = ring_pages;
+  a.window = window;
+  attn_fused_body<DT, HS, kG, PF, true>(a, a_cold);
 }
 
 template <int DT, int HS, int kG>
@@ -254,17 +294,32 @@ void launch_fused_g(const ua2_attn_args& a, hipStream_t s) {
   // more workgroups than CUs: the two-per-CU form (bf16: the fp32 kernel already fits twice)
   static const int dense_env = getenv("UA2_ATTN_DENSE") ? atoi(getenv("UA2_ATTN_DENSE")) : -1;      // A/B (read once): 0 = never, 1 = always
   const bool dense = DT == UA2_BF16 && (dense_env >= 0 ? dense_env != 0 : (int64_t)a.R * a.kv.n_kv > 256);
+  // the hot form (attn_fused_hot_kernel): rows that are their own sequences, head counts that fit 16 bits.  UA2_ATTN_NO_HOT=1: never (A/B, tests)
+  static Ua2EnvInt no_hot{"UA2_ATTN_NO_HOT", 0};
+  const bool hot = !a.row_seq && a.kv.n_kv <= 0xffff && a.kv.n_head <= 0xffff && !no_hot.get();
+  const unsigned heads = (unsigned)a.kv.n_kv | (unsigned)a.kv.n_head << 16;
+  auto go = [&](auto by_value, auto hot_form) {
+    constexpr auto kv = decltype(by_value)::value;
+    constexpr auto kh = decltype(hot_form)::value;
+    const dim3 grid(a.R, a.kv.n_kv), block(kFusedWaves * 64);
+    if (hot) {
+      ua2_allow_big_lds<kh>();
+      hipLaunchKernelGGL(kh, grid, block, smem, s, a.q, a.row_pos, a.kv.page_table, a.kv.k_pool, a.kv.v_pool, a.kv.max_pages, heads, a.window, a.kv.ring_pages, a);
+      ua2_count_launch(UA2_CNT_ATTN_HOT);
+    } else {
+      ua2_allow_big_lds<kv>();
+      hipLaunchKernelGGL(kv, grid, block, smem, s, a);
+    }
+  };
   if (dense) {
     if constexpr (DT == UA2_BF16 && kG <= 3) {          // four query heads per kv head do not fit 128 registers (80-164 B of scratch)
-      constexpr auto kern2 = attn_fused_kernel<DT, HS, kG, false>;
-      ua2_allow_big_lds<kern2>();
-      hipLaunchKernelGGL(kern2, dim3(a.R, a.kv.n_kv), dim3(kFusedWaves * 64), smem, s, a);
+      go(std::integral_constant<decltype(&attn_fused_kernel<DT, HS, kG, false>), &attn_fused_kernel<DT, HS, kG, false>>{},
+         std::integral_constant<decltype(&attn_fused_hot_kernel<DT, HS, kG, false>), &attn_fused_hot_kernel<DT, HS, kG, false>>{});
       return;
     }
   }
-  constexpr auto kern = attn_fused_kernel<DT, HS, kG>;
-  ua2_allow_big_lds<kern>();
-  hipLaunchKernelGGL(kern, dim3(a.R, a.kv.n_kv), dim3(kFusedWaves * 64), smem, s, a);
+  go(std::integral_constant<decltype(&attn_fused_kernel<DT, HS, kG>), &attn_fused_kernel<DT, HS, kG>>{},
+     std::integral_constant<decltype(&attn_fused_hot_kernel<DT, HS, kG>), &attn_fused_hot_kernel<DT, HS, kG>>{});
 }
 
 template <int DT, int HS>

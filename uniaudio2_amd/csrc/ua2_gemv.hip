@@ -190,6 +190,111 @@ __device__ __forceinline__ typename WFrag<W8>::type weight_load(const u32x4* wp,
   }
 }
 
+// ---- hot arguments: what a launch reads in front of its weight burst -------------------------------------------------------------------
+// ua2_linear_args is 700-odd bytes of kernel arguments, and the fields the path up to the burst reads lie in five or more 64-byte lines of
+// them: the kernels fetched them in two or three batches of scalar loads, each a round trip the burst stood behind.  The hot kernels
+// (gemv_hot_kernel) take those fields as their FIRST parameters instead, 14 dwords of pointers and packed ints: one line of the segment,
+// and what the dispatcher can place in user SGPRs before the wave starts (kernarg preload; uniaudio2_amd/build.py gives the option to this
+// file).  Everything else still comes from the ua2_linear_args that follows them, read behind the burst.  GemvHot is the decoded form
+// gemv_body works on; the by-value kernels (launches whose values do not fit the packed fields; the riders) fill it from ua2_linear_args.
+struct GemvHot {
+  const void *w0, *w1, *e0, *e1;   // weight stream(s): a.w0 / a.w1 or the image's q0 / q1; the image's side arrays
+  const void *x;                   // the operand rows: a.x_h (bf16 rows) or a.x
+  const void *p, *q;               // by form (hot_roles)
+  const int32_t* row_seq;          // QKV_ROPE; the hot kernels serve row_seq == NULL only
+  int K, N, M, nthreads, ldx, ldp, rt, norm_kind;
+};
+// the packed form, in kernel-parameter order: 4 pointers, the other three as offsets from w in 16-byte units, 3 dwords of ints
+struct GemvHotArgs {
+  const void *w, *x, *p, *q;
+  int o1, oe0, oe1;
+  unsigned kn, mw, ld;             // K | N << 16;  M | waves << 16 | rt << 21 | norm_kind << 26;  ldx | ldp << 16
+};
+
+// Which of a's fields a (prologue, epilogue) form reads in front of its burst besides the weights: the operand rows and their stride; p =
+// the sum-of-squares partials (SCALED), the norm weight (NORM) or the residual rows with their stride (RESIDUAL: never with those two);
+// q = the row positions (QKV_ROPE, LOCAL_ATTN) or the arg-max floor (STORE with partials).
+template <int PRO, int EPI>
+__host__ __device__ __forceinline__ void hot_roles(const ua2_linear_args& a, const void*& x, int& ldx, const void*& p, int& ldp, const void*& q) {
+  constexpr bool ROWH = PRO == UA2_PRO_SCALED || PRO == kProRowH;
+  x = ROWH ? static_cast<const void*>(a.x_h) : static_cast<const void*>(a.x);
+  ldx = PRO == UA2_PRO_SCALED ? a.ldh : a.ldx;                 // x_h in x's place (kProRowH): x's stride
+  p = nullptr; ldp = 0; q = nullptr;
+  if constexpr (PRO == UA2_PRO_SCALED) p = a.x_ssq;
+  else if constexpr (PRO == UA2_PRO_NORM) p = a.norm_w;
+  else if constexpr (EPI == UA2_EPI_RESIDUAL) { p = a.resid; ldp = a.ldr; }
+  if constexpr (EPI == UA2_EPI_QKV_ROPE || PRO == UA2_PRO_LOCAL_ATTN) q = a.row_pos;
+  else if constexpr (EPI == UA2_EPI_STORE) q = a.part_max ? static_cast<const void*>(a.forbid) : nullptr;
+}
+
+template <int PRO, int EPI>
+__device__ __forceinline__ GemvHot hot_from_args(const ua2_linear_args& a, const Ua2WImage* w8, int rt) {
+  GemvHot h;
+  h.w0 = w8 ? w8->q0 : a.w0; h.w1 = w8 ? w8->q1 : a.w1;
+  h.e0 = w8 ? w8->e0 : nullptr; h.e1 = w8 ? w8->e1 : nullptr;
+  hot_roles<PRO, EPI>(a, h.x, h.ldx, h.p, h.ldp, h.q);
+  h.row_seq = a.row_seq;
+  h.K = a.K; h.N = a.N; h.M = a.M; h.nthreads = blockDim.x; h.rt = rt; h.norm_kind = a.norm_kind;
+  return h;
+}
+
+template <int EPI, int W8>
+__device__ __forceinline__ GemvHot hot_unpack(const void* w, const void* x, const void* p, const void* q, int o1, int oe0, int oe1,
+                                              unsigned kn, unsigned mw, unsigned ld) {
+  auto at = [&](int o) { return static_cast<const void*>(static_cast<const char*>(w) + (ptrdiff_t)o * 16); };
+  GemvHot h;
+  h.w0 = w; h.w1 = EPI == UA2_EPI_SWIGLU ? at(o1) : nullptr;
+  h.e0 = W8 != 0 ? at(oe0) : nullptr; h.e1 = (W8 != 0 && EPI == UA2_EPI_SWIGLU) ? at(oe1) : nullptr;
+  h.x = x; h.p = p; h.q = q; h.row_seq = nullptr;
+  h.K = (int)(kn & 0xffffu); h.N = (int)(kn >> 16);
+  h.M = (int)(mw & 0xffffu); h.nthreads = (int)((mw >> 16) & 31u) * 64; h.rt = (int)((mw >> 21) & 31u); h.norm_kind = (int)(mw >> 26);
+  h.ldx = (int)(ld & 0xffffu); h.ldp = (int)(ld >> 16);
+  return h;
+}
+
+// Size of the hot block in the kernel arguments (4 pointers, 6 dwords): where gemv_hot_kernel's ua2_linear_args starts.
+constexpr int kHotBytes = 4 * 8 + 6 * 4;
+static_assert(kHotBytes == 14 * 4 && kHotBytes % alignof(ua2_linear_args) == 0, "the hot block is 14 dwords and ua2_linear_args follows it without padding");
+// The launch's ua2_linear_args for the code behind the burst.  Left to itself the compiler issues some of their scalar loads at the kernel's
+// entry, and a register one of them is still to land in is soon wanted for the hot block's address arithmetic: a wait on ALL of them in
+// front of the burst, which is what the hot block is there to remove (seen in the ISA of the q|k|v form; tools/kernel_entry.py).  So a HOT
+// instantiation reads them through the kernel-argument pointer taken HERE: the empty asm is opaque to the scheduler, no load through it
+// moves above this point.  (LOCAL_ATTN forms: their prologue reads the attention's geometry in front of the burst anyway; a0 as it is.)
+template <bool HOT>
+__device__ __forceinline__ const ua2_linear_args& cold_args(const ua2_linear_args& a0) {
+  if constexpr (HOT) {
+    const __attribute__((address_space(4))) char* kp = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp) : : "memory");
+    return *reinterpret_cast<const ua2_linear_args*>((const char*)(kp + kHotBytes));
+  } else {
+    return a0;
+  }
+}
+
+// LDS carve of a launch, one definition for the launcher and the hot kernels (the by-value kernels get both numbers as arguments): the
+// operand rows' stride in elements (+16 B per row: breaks the power-of-two row stride, LDS bank conflicts across rows) and the offset of the
+// reduction buffers behind the rows actually present.
+__host__ __device__ __forceinline__ int carve_a_stride(int nchunks, int kc, int bytes) { return nchunks * kc + 16 / bytes; }
+__host__ __device__ __forceinline__ int carve_red_off(int M, int rt, int a_stride, int bytes) {
+  return (int)(((size_t)(M < rt ? M : rt) * a_stride * bytes + 255) & ~(size_t)255);
+}
+
+// epilogue_prefetch_a (ua2_linear_common.h) on the hot block: the same loads into the same fields, no address from a cold argument
+template <int EPI>
+__device__ __forceinline__ void hot_prefetch_a(const GemvHot& h, int tile0, int row, int col, EpiPre& p, int m0) {
+  const int mr = m0 + row;
+  if (mr >= h.M) return;
+  const int n = tile0 * 16 + col;
+  if constexpr (EPI == UA2_EPI_STORE) {
+    if (h.q) p.forbid = static_cast<const int32_t*>(h.q)[mr];
+  } else if constexpr (EPI == UA2_EPI_RESIDUAL) {
+    if (n < h.N) p.resid = static_cast<const float*>(h.p)[(size_t)mr * h.ldp + n];
+  } else if constexpr (EPI == UA2_EPI_QKV_ROPE) {
+    p.pos = static_cast<const int32_t*>(h.q)[mr];
+    p.page = h.row_seq ? h.row_seq[mr] : mr;   // table row for now; resolved to a page id in stage B
+  }
+}
+
 // MR = multi-round: <= 8 waves per workgroup, several rounds of CPW chunks per wave, next round's
 // weights prefetched (double buffer); !MR = single burst: up to 16 waves, everything up front.
 // W8: 0 = the weights of a.w0 / a.w1 in the launch dtype; 1 = fp8 image, the wave's chunk range is a whole number of rounds of CPW
@@ -201,9 +306,11 @@ __device__ __forceinline__ typename WFrag<W8>::type weight_load(const u32x4* wp,
 // multi-round forms); 4 = any range of up to CPW chunks, a load set per chunk.  No scale: the decoded fragment IS the bf16 one.
 // FOLD (UA2_PRO_LOCAL_ATTN, W8 = 0): the launch carries a ua2_argmax_fold; an instantiation of its own, so that the plain launches keep
 // their registers (the CPW = 16 forms sit at the 128-register limit of a 16-wave workgroup).
-template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0, bool FOLD = false>
-__device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, const int a_stride, const int red_off, const int rt,
-                                          const int bx, const int by, const Ua2WImage* w8 = nullptr) {
+// HOT: the instantiation of gemv_hot_kernel.  a0 = the launch's ua2_linear_args as the path up to the burst may see them — in a HOT
+// instantiation only where a prologue cannot do without (the attention's geometry, LayerNorm's bias); behind the burst the body reads `a`.
+template <int DT, int PRO, int EPI, int CPW, bool MR, int W8 = 0, bool FOLD = false, bool HOT = false>
+__device__ __forceinline__ void gemv_body(const ua2_linear_args& a0, const GemvHot& h, char* smem, const int a_stride, const int red_off,
+                                          const int bx, const int by) {
   constexpr int KC = Elem<DT>::KC, EPL = Elem<DT>::EPL, BYTES = Elem<DT>::BYTES;
   constexpr int NT = (EPI == UA2_EPI_SWIGLU) ? 2 : 1;
   static_assert(W8 == 0 || DT == UA2_BF16, "fp8 weights and 13-bit images are bf16-plan options");
@@ -218,29 +325,31 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   float* mean_s = rstd_s + 16;                               // [16]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nthreads = blockDim.x, nw = nthreads >> 6;
+  const int nthreads = h.nthreads, nw = nthreads >> 6;   // not blockDim.x: that is a load from the hidden arguments, far behind the hot block
   const int i = lane & 15, g = lane >> 4;
+  const int rt = h.rt;
   const int m0 = by * rt;                    // rt rows per workgroup: a function of K and dtype only
-  const int rows = min(rt, a.M - m0);
+  const int rows = min(rt, h.M - m0);
 
-  const int nchunks = (a.K + KC - 1) / KC;
+  // Up to the burst every argument comes from h (the hot block); a's other fields are read behind it.
+  const int nchunks = (h.K + KC - 1) / KC;
   int tile[NT];
   const u32x4* wp[NT];
   if constexpr (L13) {                                         // [N/16][K/128] groups of kL13Group x 16 B (K % 128 == 0); the lane goes on in weight_load
     tile[0] = bx;
-    wp[0] = reinterpret_cast<const u32x4*>(w8->q0) + (size_t)bx * (nchunks >> 2) * kL13Group;
-    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(w8->q1) + (size_t)bx * (nchunks >> 2) * kL13Group; }
+    wp[0] = reinterpret_cast<const u32x4*>(h.w0) + (size_t)bx * (nchunks >> 2) * kL13Group;
+    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(h.w1) + (size_t)bx * (nchunks >> 2) * kL13Group; }
   } else if constexpr (W8 != 0) {                              // [N/16][K/64][64 lanes][16 B]: nchunks / 2 bursts per tile (K % 64 == 0)
     tile[0] = bx;
-    wp[0] = reinterpret_cast<const u32x4*>(w8->q0) + (size_t)bx * (nchunks >> 1) * 64 + lane;
-    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(w8->q1) + (size_t)bx * (nchunks >> 1) * 64 + lane; }
+    wp[0] = reinterpret_cast<const u32x4*>(h.w0) + (size_t)bx * (nchunks >> 1) * 64 + lane;
+    if constexpr (NT == 2) { tile[1] = bx; wp[1] = reinterpret_cast<const u32x4*>(h.w1) + (size_t)bx * (nchunks >> 1) * 64 + lane; }
   } else if constexpr (EPI == UA2_EPI_SWIGLU) {
     tile[0] = tile[1] = bx;
-    wp[0] = reinterpret_cast<const u32x4*>(a.w0) + (size_t)tile[0] * nchunks * 64 + lane;
-    wp[1] = reinterpret_cast<const u32x4*>(a.w1) + (size_t)tile[0] * nchunks * 64 + lane;
+    wp[0] = reinterpret_cast<const u32x4*>(h.w0) + (size_t)tile[0] * nchunks * 64 + lane;
+    wp[1] = reinterpret_cast<const u32x4*>(h.w1) + (size_t)tile[0] * nchunks * 64 + lane;
   } else {
     tile[0] = bx;
-    wp[0] = reinterpret_cast<const u32x4*>(a.w0) + (size_t)tile[0] * nchunks * 64 + lane;
+    wp[0] = reinterpret_cast<const u32x4*>(h.w0) + (size_t)tile[0] * nchunks * 64 + lane;
   }
   // chunk range of this wave; rounds of CPW chunks (exactly one round for the model's shapes)
   const int c0 = (wave * nchunks) / nw, c1 = ((wave + 1) * nchunks) / nw;
@@ -251,31 +360,33 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   // while the weights are still streaming), never behind it.
   constexpr int XPT = 2;  // float4 per thread kept in registers on the single-row fast path
   constexpr bool ROWH = PRO == UA2_PRO_SCALED || PRO == kProRowH;     // the operand arrives as bf16 rows (a.x_h)
-  const bool one = (PRO != UA2_PRO_LOCAL_ATTN) && !ROWH && (rows == 1) && (a.K <= XPT * 4 * nthreads);
+  const bool one = (PRO != UA2_PRO_LOCAL_ATTN) && !ROWH && (rows == 1) && (h.K <= XPT * 4 * nthreads);
   // UA2_PRO_SCALED: the operand row(s) arrive already rounded (RNE_bf16(x (.) w), written by the producer of x): a 16-byte
   // copy into the LDS tile — no statistics, no conversion, one barrier.  The first row's piece goes out before the weights.
   // kProRowH (UA2_PRO_CAST with x_h): the same copy of RNE_bf16(x), rounded once by x's producer instead of in every workgroup —
   // half the operand bytes in front of the burst; no statistics and no row scale.
   u32x4 xh0 = u32x4{0u, 0u, 0u, 0u};
-  const int ldxh = (PRO == kProRowH) ? a.ldx : a.ldh;              // x_h in x's place: x's stride
+  const int ldxh = h.ldx;                                          // kProRowH (x_h in x's place): x's stride; SCALED: ldh (hot_roles)
   if constexpr (ROWH) {
-    if (tid * 8 < a.K) xh0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)m0 * ldxh + tid * 8);
+    if (tid * 8 < h.K) xh0 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(h.x) + (size_t)m0 * ldxh + tid * 8);
   }
   float4 xv[XPT], nv[XPT], nb[XPT];
-  const bool ln = (PRO == UA2_PRO_NORM) && a.norm_kind == UA2_NORM_LAYERNORM;
+  const bool ln = (PRO == UA2_PRO_NORM) && h.norm_kind == UA2_NORM_LAYERNORM;
+  const float* x_f = static_cast<const float*>(h.x);               // !ROWH: a.x
+  const float* norm_w = static_cast<const float*>(h.p);            // UA2_PRO_NORM: a.norm_w
   if (one) {
-    const float* xr = a.x + (size_t)m0 * a.ldx;
+    const float* xr = x_f + (size_t)m0 * h.ldx;
 #pragma unroll
     for (int it = 0; it < XPT; ++it) {
       const int k = (tid + it * nthreads) * 4;
       xv[it] = make_float4(0.f, 0.f, 0.f, 0.f);
       nv[it] = make_float4(1.f, 1.f, 1.f, 1.f);
       nb[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (k < a.K) {
+      if (k < h.K) {
         xv[it] = *reinterpret_cast<const float4*>(xr + k);
         if constexpr (PRO == UA2_PRO_NORM) {
-          nv[it] = *reinterpret_cast<const float4*>(a.norm_w + k);
-          if (ln) nb[it] = *reinterpret_cast<const float4*>(a.norm_b + k);
+          nv[it] = *reinterpret_cast<const float4*>(norm_w + k);
+          if (ln) nb[it] = *reinterpret_cast<const float4*>(a0.norm_b + k);
         }
       }
     }
@@ -283,10 +394,10 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   EpiPre pre;
   static_assert(!FOLD || (PRO == UA2_PRO_LOCAL_ATTN && EPI == UA2_EPI_RESIDUAL && W8 == 0), "ua2_argmax_fold: the O-projection of the local attention");
   // (FOLD: the residual is a table row, known once the prologue has the id)
-  if (tid < 256 && !FOLD) epilogue_prefetch_a<DT, EPI>(a, tile[0], tid >> 4, tid & 15, pre, m0);
+  if (tid < 256 && !FOLD) hot_prefetch_a<EPI>(h, tile[0], tid >> 4, tid & 15, pre, m0);
   float ssqv[16];                                        // UA2_PRO_SCALED: the row's sum-of-squares partials, requested before the burst
   if constexpr (PRO == UA2_PRO_SCALED) {
-    if (tid < 256) scaled_ssq_request(a, m0 + min(tid >> 4, rows - 1), tid & 15, ssqv);
+    if (tid < 256) scaled_ssq_request(static_cast<const float*>(h.p), h.K, h.M, m0 + min(tid >> 4, rows - 1), tid & 15, ssqv);
   }
   // fp8 weights: exponent of this thread's epilogue column (16 bytes per tile, padded to 16 columns: in bounds for every thread).  Every
   // thread loads it, not just the 256 epilogue threads: a load under a lane predicate ends in a wait in front of the weight burst
@@ -294,18 +405,24 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
 #pragma unroll
   for (int t = 0; t < NT; ++t) wexp[t] = 0;
   if constexpr (FP8) {
-    wexp[0] = static_cast<const int8_t*>(w8->e0)[bx * 16 + (tid & 15)];
-    if constexpr (NT == 2) wexp[1] = static_cast<const int8_t*>(w8->e1)[bx * 16 + (tid & 15)];
+    wexp[0] = static_cast<const int8_t*>(h.e0)[bx * 16 + (tid & 15)];
+    if constexpr (NT == 2) wexp[1] = static_cast<const int8_t*>(h.e1)[bx * 16 + (tid & 15)];
   }
   // 13-bit image: the tile's base byte (workgroup-uniform, needed at decode time only), spread to the four bytes of a dword
   unsigned base4[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) base4[t] = 0u;
   if constexpr (L13) {
-    base4[0] = (unsigned)static_cast<const uint8_t*>(w8->e0)[bx] * 0x01010101u;
-    if constexpr (NT == 2) base4[1] = (unsigned)static_cast<const uint8_t*>(w8->e1)[bx] * 0x01010101u;
+    base4[0] = (unsigned)static_cast<const uint8_t*>(h.e0)[bx] * 0x01010101u;
+    if constexpr (NT == 2) base4[1] = (unsigned)static_cast<const uint8_t*>(h.e1)[bx] * 0x01010101u;
   }
 
+  // Every other argument, for the code behind the burst.  Single-round forms: requested HERE and not before (cold_args) — the scalar loads
+  // go out with the weights and land under them; nothing up to the end of the burst reads one, so nothing in front of it waits for them.
+  // Multi-round forms: left to the compiler, which issues some at the kernel's entry.  Pinned, their round trip stood between the first
+  // burst and the barrier, i.e. in front of the SECOND round's loads, and the frame measured slower (profiles/hot_args.md: the trunk
+  // q|k|v 8.33 -> 8.71 us per launch); the price is one wait in front of the burst in the q|k|v forms (four before the hot block).
+  const ua2_linear_args a = cold_args < HOT && !MR && PRO != UA2_PRO_LOCAL_ATTN > (a0);
   WF wf[NT][NL];
   auto burst = [&]() {
 #pragma unroll
@@ -317,19 +434,19 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     if constexpr (FOLD) {
       auto on_id = [&](size_t row) {
         const int n = tile[0] * 16 + (tid & 15);
-        if (tid < 16 && n < a.N) pre.resid = a.fold.tab_y[row * a.N + n];       // epilogue row 0 (M == 1)
+        if (tid < 16 && n < h.N) pre.resid = a0.fold.tab_y[row * h.N + n];       // epilogue row 0 (M == 1)
       };
       const bool writer = bx == 0 && by == 0;
-      switch (a.kv.head_size) {
-        case 32: local_attn_fold_prologue<DT, 32>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
-        case 64: local_attn_fold_prologue<DT, 64>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
-        default: local_attn_fold_prologue<DT, 128>(a, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+      switch (a0.kv.head_size) {
+        case 32: local_attn_fold_prologue<DT, 32>(a0, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+        case 64: local_attn_fold_prologue<DT, 64>(a0, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
+        default: local_attn_fold_prologue<DT, 128>(a0, a_lds, ssq, wave, nw, lane, writer, burst, on_id); break;
       }
     } else
-    switch (a.kv.head_size) {
-      case 32: local_attn_prologue<DT, 32>(a, a_lds, m0, wave, nw, lane, burst); break;
-      case 64: local_attn_prologue<DT, 64>(a, a_lds, m0, wave, nw, lane, burst); break;
-      default: local_attn_prologue<DT, 128>(a, a_lds, m0, wave, nw, lane, burst); break;
+    switch (a0.kv.head_size) {
+      case 32: local_attn_prologue<DT, 32>(a0, a_lds, m0, wave, nw, lane, burst); break;
+      case 64: local_attn_prologue<DT, 64>(a0, a_lds, m0, wave, nw, lane, burst); break;
+      default: local_attn_prologue<DT, 128>(a0, a_lds, m0, wave, nw, lane, burst); break;
     }
   } else {
     burst();
@@ -358,7 +475,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
     // outstanding load: the LDS write, the barrier and the first MFMA stood behind the last weight fragment (the ISA showed vmcnt(0)).
     if (tid * 8 < kpad) *reinterpret_cast<u32x4*>(a_lds + (size_t)tid * 8 * BYTES) = xh0;
     for (int r0 = 0; r0 < rows; ++r0) {        // what is left: further pieces of a long row, further rows (they queue behind the burst)
-      const unsigned short* xr = reinterpret_cast<const unsigned short*>(a.x_h) + (size_t)(m0 + r0) * ldxh;
+      const unsigned short* xr = reinterpret_cast<const unsigned short*>(h.x) + (size_t)(m0 + r0) * ldxh;
       for (int k = (r0 == 0 ? nthreads : 0) * 8 + tid * 8; k < kpad; k += nthreads * 8)
         *reinterpret_cast<u32x4*>(a_lds + ((size_t)r0 * a_stride + k) * BYTES) = *reinterpret_cast<const u32x4*>(xr + k);
     }
@@ -382,7 +499,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
         float cs = 0.f, sd = 0.f;
 #pragma unroll
         for (int it = 0; it < XPT; ++it)
-          if ((tid + it * nthreads) * 4 < a.K) centred4(cs, sd, xv[it], st.mean);
+          if ((tid + it * nthreads) * 4 < h.K) centred4(cs, sd, xv[it], st.mean);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
         __syncthreads();                       // every thread has read the first pass's partials
@@ -399,7 +516,7 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       if (k < nchunks * KC) {                             // also zero-fills the K padding of the last chunk
         float4 t = xv[it];
         if constexpr (PRO == UA2_PRO_NORM) {
-          if (k < a.K) {
+          if (k < h.K) {
             t.x = norm_apply(a, t.x, nv[it].x, nb[it].x, st);
             t.y = norm_apply(a, t.y, nv[it].y, nb[it].y, st);
             t.z = norm_apply(a, t.z, nv[it].z, nb[it].z, st);
@@ -412,9 +529,9 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
   } else {
     if constexpr (PRO == UA2_PRO_NORM) {
       for (int r0 = 0; r0 < rows; ++r0) {  // pass 1: sum and sum of squares per row
-        const float* xr = a.x + (size_t)(m0 + r0) * a.ldx;
+        const float* xr = x_f + (size_t)(m0 + r0) * h.ldx;
         float ss = 0.f, sm = 0.f;
-        for (int k = tid * 4; k < a.K; k += nthreads * 4) {
+        for (int k = tid * 4; k < h.K; k += nthreads * 4) {
           const float4 t = *reinterpret_cast<const float4*>(xr + k);
           ss = sumsq4(ss, t);
           sm = sum4(sm, t);
@@ -433,10 +550,10 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       __syncthreads();
       if (ln) {                                // second pass per row (norm_stat_centred), the first pass's order
         for (int r0 = 0; r0 < rows; ++r0) {
-          const float* xr = a.x + (size_t)(m0 + r0) * a.ldx;
+          const float* xr = x_f + (size_t)(m0 + r0) * h.ldx;
           const float mean = mean_s[r0];
           float cs = 0.f, sd = 0.f;
-          for (int k = tid * 4; k < a.K; k += nthreads * 4) centred4(cs, sd, *reinterpret_cast<const float4*>(xr + k), mean);
+          for (int k = tid * 4; k < h.K; k += nthreads * 4) centred4(cs, sd, *reinterpret_cast<const float4*>(xr + k), mean);
 #pragma unroll
           for (int o = 32; o >= 1; o >>= 1) { cs += __shfl_xor(cs, o); sd += __shfl_xor(sd, o); }
           if (lane == 0) { ssq[wave * 16 + r0] = cs; ssum[wave * 16 + r0] = sd; }
@@ -454,15 +571,15 @@ __device__ __forceinline__ void gemv_body(const ua2_linear_args& a, char* smem, 
       }
     }
     for (int r0 = 0; r0 < rows; ++r0) {
-      const float* xr = a.x + (size_t)(m0 + r0) * a.ldx;
+      const float* xr = x_f + (size_t)(m0 + r0) * h.ldx;
       NormStat st{0.f, 1.f, 0.f};
       if constexpr (PRO == UA2_PRO_NORM) { st.rstd = rstd_s[r0]; st.mean = mean_s[r0]; if (ln) st.mean_lo = ssum[r0]; }
       for (int k = tid * 4; k < nchunks * KC; k += nthreads * 4) {
         float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (k < a.K) {
+        if (k < h.K) {
           t = *reinterpret_cast<const float4*>(xr + k);
           if constexpr (PRO == UA2_PRO_NORM) {
-            const float4 w = *reinterpret_cast<const float4*>(a.norm_w + k);
+            const float4 w = *reinterpret_cast<const float4*>(norm_w + k);
             float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ln) b = *reinterpret_cast<const float4*>(a.norm_b + k);
             t.x = norm_apply(a, t.x, w.x, b.x, st);
@@ -562,7 +679,20 @@ template <int DT, int PRO, int EPI, int CPW, bool MR, bool FOLD = false>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_kernel(const ua2_linear_args a, const int a_stride,
                                                               const int red_off, const int rt) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<DT, PRO, EPI, CPW, MR, 0, FOLD>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y);
+  gemv_body<DT, PRO, EPI, CPW, MR, 0, FOLD>(a, hot_from_args<PRO, EPI>(a, nullptr, rt), smem, a_stride, red_off, blockIdx.x, blockIdx.y);
+}
+
+// The hot form of the three kernels below and above (W8 as gemv_body's): the hot block first — pointers and ints only, a by-value struct in
+// front of them would keep the dispatcher from preloading any — then ua2_linear_args for everything read behind the burst.  The image's
+// pointers travel in the hot block, so there is no Ua2WImage parameter.
+template <int DT, int PRO, int EPI, int CPW, bool MR, int W8, bool FOLD = false>
+__global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_hot_kernel(const void* hw, const void* hx, const void* hp, const void* hq,
+                                                                  const int o1, const int oe0, const int oe1, const unsigned kn,
+                                                                  const unsigned mw, const unsigned ld, const ua2_linear_args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const GemvHot h = hot_unpack<EPI, W8>(hw, hx, hp, hq, o1, oe0, oe1, kn, mw, ld);
+  const int a_stride = carve_a_stride((h.K + Elem<DT>::KC - 1) / Elem<DT>::KC, Elem<DT>::KC, Elem<DT>::BYTES);
+  gemv_body<DT, PRO, EPI, CPW, MR, W8, FOLD, true>(a, h, smem, a_stride, carve_red_off(h.M, h.rt, a_stride, Elem<DT>::BYTES), blockIdx.x, blockIdx.y);
 }
 
 // the same launch on the fp8 image of its weight(s): bf16 activations in LDS, bf16 MFMA, half the weight bytes
@@ -570,7 +700,7 @@ template <int PRO, int EPI, int CPW, bool MR, int W8>
 __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_w8_kernel(const ua2_linear_args a, const int a_stride,
                                                                  const int red_off, const int rt, const Ua2WImage w8) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
+  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, hot_from_args<PRO, EPI>(a, &w8, rt), smem, a_stride, red_off, blockIdx.x, blockIdx.y);
 }
 
 // ... and on the lossless 13-bit image of the bf16 weights themselves (W8 = 3 / 4): 13/16 of the bytes, the same bits
@@ -579,7 +709,7 @@ __global__ __launch_bounds__(MR ? 512 : kMaxWaves * 64) void gemv_l13_kernel(con
                                                                   const int red_off, const int rt, const Ua2WImage w8) {
   static_assert(W8 == 3 || W8 == 4, "the 13-bit forms");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, smem, a_stride, red_off, rt, blockIdx.x, blockIdx.y, &w8);
+  gemv_body<UA2_BF16, PRO, EPI, CPW, MR, W8>(a, hot_from_args<PRO, EPI>(a, &w8, rt), smem, a_stride, red_off, blockIdx.x, blockIdx.y);
 }
 
 // ---- riders: a second, independent one-row-tile GEMV carried by the idle CUs of a launch that cannot fill the device -----------
@@ -661,7 +791,7 @@ template <int PRO, int EPI, int CPW, int CPWR>
 __global__ __launch_bounds__(kMaxWaves * 64) void gemv_rider_kernel(const ua2_linear_args a, const int a_stride, const int red_off, const int rt,
                                                                     const ua2_linear_args ra, const int tile0, const int tile1, const int host_gx) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if ((int)blockIdx.x < host_gx) gemv_body<UA2_BF16, PRO, EPI, CPW, false>(a, smem, a_stride, red_off, rt, blockIdx.x, 0);
+  if ((int)blockIdx.x < host_gx) gemv_body<UA2_BF16, PRO, EPI, CPW, false>(a, hot_from_args<PRO, EPI>(a, nullptr, rt), smem, a_stride, red_off, blockIdx.x, 0);
   else rider_body<CPWR>(ra, smem, tile0, tile1, (int)blockIdx.x - host_gx);
 }
 
@@ -741,6 +871,42 @@ void launch_one(std::initializer_list<int> counters, const ua2_linear_args& a, c
   for (const int c : counters) ua2_count_launch(c);
 }
 
+// The hot block of a launch (GemvHotArgs), or false where a value does not fit its packed field — 16 bits for K, N, M and the strides, a
+// 16-byte-aligned distance of less than 2^31 x 16 B from the first weight pointer for the second one and the side arrays (the plan's images
+// lie in one allocation), row_seq == NULL — and the launch takes the by-value kernel.  UA2_GEMV_NO_HOT=1: every launch does (A/B, tests).
+template <int PRO, int EPI>
+bool pack_hot(const ua2_linear_args& a, const Launch& l, bool mr, const Ua2WImage* img, GemvHotArgs& h) {
+  static Ua2EnvInt off{"UA2_GEMV_NO_HOT", 0};
+  if ((off.get() & 1) || (mr && (off.get() & 2))) return false;
+  int ldx = 0, ldp = 0;
+  hot_roles<PRO, EPI>(a, h.x, ldx, h.p, ldp, h.q);
+  if (EPI == UA2_EPI_QKV_ROPE && a.row_seq) return false;
+  h.w = img ? img->q0 : a.w0;
+  auto rel = [&](const void* p, int& o) {
+    o = 0;
+    if (!p) return true;
+    const long long d = static_cast<const char*>(p) - static_cast<const char*>(h.w);
+    if (d % 16 != 0 || d / 16 > INT32_MAX || d / 16 < INT32_MIN) return false;
+    o = (int)(d / 16);
+    return true;
+  };
+  const bool two = EPI == UA2_EPI_SWIGLU;
+  if (!rel(two ? (img ? img->q1 : a.w1) : nullptr, h.o1) || !rel(img ? img->e0 : nullptr, h.oe0) || !rel(img && two ? img->e1 : nullptr, h.oe1)) return false;
+  auto u16 = [](int v) { return v >= 0 && v <= 0xffff; };
+  if (!u16(a.K) || !u16(a.N) || !u16(a.M) || !u16(ldx) || !u16(ldp) || a.norm_kind < 0 || a.norm_kind > 3 || l.waves > 31 || l.rt > 31) return false;
+  h.kn = (unsigned)a.K | (unsigned)a.N << 16;
+  h.mw = (unsigned)a.M | (unsigned)l.waves << 16 | (unsigned)l.rt << 21 | (unsigned)a.norm_kind << 26;
+  h.ld = (unsigned)ldx | (unsigned)ldp << 16;
+  return true;
+}
+template <auto Kern>
+void launch_hot(std::initializer_list<int> counters, const ua2_linear_args& a, const Launch& l, const GemvHotArgs& h) {
+  ua2_allow_big_lds<Kern>();
+  hipLaunchKernelGGL(Kern, l.grid, dim3(l.waves * 64), l.smem, l.s, h.w, h.x, h.p, h.q, h.o1, h.oe0, h.oe1, h.kn, h.mw, h.ld, a);
+  for (const int c : counters) ua2_count_launch(c);
+  ua2_count_launch(UA2_CNT_GEMV_HOT);     // besides the families the launch counts in: which form served it
+}
+
 // chunks one load (set) of an image form carries: a K that is no whole number of them has no image
 constexpr int image_group(Ua2WForm form) { return form == UA2_W_L13 ? 4 : 2; }
 
@@ -789,12 +955,11 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nu
   const Geometry geo = pick_geometry(nchunks, gx, NT);
   Launch l;
   l.waves = geo.waves; l.s = s;
-  // +16 B per row: breaks the power-of-two row stride (LDS bank conflicts across rows)
-  l.a_stride = nchunks * KC + 16 / BYTES;
+  l.a_stride = carve_a_stride(nchunks, KC, BYTES);
   l.rt = rows_per_tile(a.dtype, a.K);
   // LDS is sized for the rows actually present (occupancy: two single-row workgroups share a CU);
   // the size changes nothing a row computes
-  l.red_off = (int)(((size_t)(a.M < l.rt ? a.M : l.rt) * l.a_stride * BYTES + 255) & ~(size_t)255);
+  l.red_off = carve_red_off(a.M, l.rt, l.a_stride, BYTES);
   l.smem = (size_t)l.red_off + (size_t)(kMaxWaves * NT * 256 + 2 * kMaxWaves * 16 + 32) * sizeof(float);
   l.grid = dim3(gx, ua2_ceil_div(a.M, l.rt));
   const bool mr = geo.waves <= 8 && geo.waves * geo.cpw < nchunks;
@@ -809,6 +974,11 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nu
   }
   const bool fold = FOLD && a.fold.part_max;     // ua2_argmax_fold (never with an image: launch_dt)
   if (fold && (a.M != 1 || geo.cpw > 8)) return 1;
+  // the hot form (gemv_hot_kernel): the bf16 pairs of the decode frame, the same set as the images'; the by-value kernels serve the rest
+  GemvHotArgs hot;
+  // (LOCAL_ATTN on an image stays by-value: its prologue reads the attention's geometry from ua2_linear_args in front of the burst in
+  // either form, and the hot form measured 0.15 us per launch SLOWER inside the frame, twice: profiles/hot_args.md §3)
+  const bool is_hot = IMAGE && !(PRO == UA2_PRO_LOCAL_ATTN && w8 != 0) && pack_hot<PRO, EPI>(a, l, mr, w8 ? &w->img : nullptr, hot);
   int rc = 1;
   with_rounds<NT>(geo, mr, [&](auto cpw, auto multi) {
     constexpr int CPW = decltype(cpw)::value;
@@ -816,6 +986,21 @@ int launch_cpw(const ua2_linear_args& a, hipStream_t s, const Ua2Weights* w = nu
     rc = 0;
     if constexpr (IMAGE) {
       constexpr bool FALLBACK = CPW == 4 && !MR;     // the only geometry of forms 2 / 4 (image_form)
+      if (is_hot && w8 == 0) {
+        if constexpr (FOLD && CPW <= 8)
+          if (fold) return launch_hot<gemv_hot_kernel<DT, PRO, EPI, CPW, MR, 0, true>>({UA2_CNT_GEMV}, a, l, hot);
+        return launch_hot<gemv_hot_kernel<DT, PRO, EPI, CPW, MR, 0>>({UA2_CNT_GEMV}, a, l, hot);
+      }
+      if constexpr (PRO != UA2_PRO_LOCAL_ATTN) if (is_hot) switch (w8) {
+        case 1: return launch_hot<gemv_hot_kernel<DT, PRO, EPI, CPW, MR, 1>>({UA2_CNT_GEMV_W8}, a, l, hot);
+        case 3: return launch_hot<gemv_hot_kernel<DT, PRO, EPI, CPW, MR, 3>>({UA2_CNT_GEMV, UA2_CNT_GEMV_L13}, a, l, hot);
+        case 2:
+          if constexpr (FALLBACK) return launch_hot<gemv_hot_kernel<DT, PRO, EPI, 4, false, 2>>({UA2_CNT_GEMV_W8}, a, l, hot);
+          rc = 1; return;
+        case 4:
+          if constexpr (FALLBACK) return launch_hot<gemv_hot_kernel<DT, PRO, EPI, 4, false, 4>>({UA2_CNT_GEMV, UA2_CNT_GEMV_L13}, a, l, hot);
+          rc = 1; return;
+      }
       switch (w8) {
         case 1: return launch_one<gemv_w8_kernel<PRO, EPI, CPW, MR, 1>>({UA2_CNT_GEMV_W8}, a, l, w->img);
         // bf16 weights through the decode kernel: a "gemv" launch as well (the counter's readers count launches of the frame)

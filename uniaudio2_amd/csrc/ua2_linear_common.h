@@ -165,12 +165,17 @@ __device__ __forceinline__ float ssq_tile16(float v) {
 // One order for every kernel: lane c of the row's 16-lane group adds partials c, c + 16, ... ascending, the 16 chains meet
 // in the butterfly xor 1, 2, 4, 8 — a row's scale does not depend on the row count or the kernel.  K <= 4096.
 // NPL = partials per lane the caller holds (>= ceil(K / 256); 16 covers every K): fewer registers where K is a compile-time fact
+// (x_ssq, K, M as values: the decode kernel has them in registers before the rest of its arguments, ua2_gemv.hip GemvHot)
 template <int NPL>
-__device__ __forceinline__ void scaled_ssq_request(const ua2_linear_args& a, int mr, int c, float (&v)[NPL]) {
-  const int nparts = a.K >> 4;
-  const float* p = a.x_ssq + (size_t)min(max(mr, 0), a.M - 1) * nparts;
+__device__ __forceinline__ void scaled_ssq_request(const float* x_ssq, int K, int M, int mr, int c, float (&v)[NPL]) {
+  const int nparts = K >> 4;
+  const float* p = x_ssq + (size_t)min(max(mr, 0), M - 1) * nparts;
 #pragma unroll
   for (int i = 0; i < NPL; ++i) v[i] = p[min(c + 16 * i, nparts - 1)];   // clamped, not predicated: a load under a lane predicate ends in a wait per load
+}
+template <int NPL>
+__device__ __forceinline__ void scaled_ssq_request(const ua2_linear_args& a, int mr, int c, float (&v)[NPL]) {
+  scaled_ssq_request(a.x_ssq, a.K, a.M, mr, c, v);
 }
 template <int NPL>
 __device__ __forceinline__ float scaled_rstd_reduce(const ua2_linear_args& a, int c, const float (&v)[NPL]) {
